@@ -21,8 +21,20 @@ channels; each rank takes 8 sub-bands (`sharding.SubbandShard`; all 64 at
 --gpus 8), results are concatenated along the sub-band axis with one
 all-gather (`sharding.gather_subbands`).
 
-Both workloads print the rate with outputs left sharded (`value`) and, for
-more than one rank, the rate including the gather (`with_gather`).
+Both workloads print the rate with outputs left sharded (`value`) and, with
+``--full`` for more than one rank, the rate including the gather
+(`with_gather`).
+
+A plain run sets up, warms up, times ``--steps`` steps and prints the result
+line.  ``--full`` adds everything else the benchmark measures or checks:
+`roofline` (per-pass HIP-event timing inside the timed region, the passes
+isolated, HBM traffic from rocprofv3 child runs), `cpu_baseline`, `host_path`,
+`verified` and `with_gather`; without it those fields are null.
+``--dump-outputs DIR`` writes a fixed, seeded sample of the spectra the last
+timed step produced as ``DIR/spectra.npy`` (float32, the complex values as a
+trailing (re, im) axis) and their row numbers as ``DIR/spectra_index.npy``
+(float64); with more than one rank every rank writes its own pair, suffixed
+``_rank<r>``.  The input is seeded, so two builds compare output for output.
 
 Launching.  Under torchrun (WORLD_SIZE set) this process is one rank.  Plain
 ``python bench.py --gpus N`` with N > 1 starts the N ranks itself: the parent
@@ -31,9 +43,10 @@ RANK/LOCAL_RANK/WORLD_SIZE/MASTER_* set, relays rank 0's JSON line and exits
 non-zero if any rank fails.  BBT_BENCH_BACKEND=gloo rehearses the multi-rank
 path on a box with fewer GPUs than ranks.
 
-After timing, outside the timed region, the result of the timed call shape is
-compared with the CPU oracle at the first blocks, a mid-batch seam and the last
-blocks (`verified`); the run fails if that check fails.
+With ``--full``, after timing and outside the timed region, the result of the
+timed call shape is compared with the CPU oracle at the first blocks, a
+mid-batch seam and the last blocks (`verified`); the run fails if that check
+fails.
 """
 import argparse
 import gc
@@ -92,8 +105,17 @@ def parse():
     ap.add_argument('--no-traffic', action='store_true',
                     help='do not measure roofline.traffic with rocprofv3 child runs (N = 1); replay the '
                          'figure on file under profiles/ instead')
+    ap.add_argument('--full', action='store_true',
+                    help='also measure and check what the headline figure does not need: roofline (kernel '
+                         'timing, isolated passes, HBM traffic), CPU baseline, host path, the oracle check and, '
+                         'for N > 1, the steps that end with the all-gather; the --no-* switches apply to these')
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                    help='write a fixed, seeded sample of the last timed step\'s spectra to DIR/*.npy')
     ap.add_argument('--traffic-child', action='store_true', help=argparse.SUPPRESS)
-    return ap.parse_args()
+    args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error('--steps must be at least 1 and --warmup at least 0')
+    return args
 
 
 # ---------------------------------------------------------------------------
@@ -115,7 +137,7 @@ def measure_traffic(args):
     spec.loader.exec_module(rdb)
     tmp = tempfile.mkdtemp(prefix='bbt_traffic_', dir='/tmp')
     child = [sys.executable, os.path.abspath(__file__), '--traffic-child', '--workload', args.workload,
-             '--steps', '2', '--warmup', '1', '--no-cpu', '--no-verify', '--no-host-path', '--no-traffic',
+             '--steps', '2', '--warmup', '1', '--full', '--no-cpu', '--no-verify', '--no-host-path', '--no-traffic',
              '--no-kernel-timing']
     child += ['--blocks', str(min(args.blocks or 96, 96))] if args.workload == 'headline' else \
         ['--blocks', str(args.blocks or 8), '--subbands-per-rank', str(args.subbands_per_rank)]
@@ -490,6 +512,25 @@ def verify_config4(x, z, freq_mhz, n_blocks, n_spec, spf):
                      f'first block seam and the end of the first two blocks; tolerance {TOL_REL_L2:g} / {TOL_MAX:g}')
 
 
+DUMP_BYTES = 32 << 20                # the whole job's share of --dump-outputs (float32 spectra)
+
+
+def dump_outputs(directory, z, rank, world):
+    """A fixed, seeded sample of the spectra of one step -- always the first and the last spectrum --
+    as float32 (row, ..., re/im) plus the row numbers as float64; DUMP_BYTES over all ranks."""
+    n_spec = z.shape[0]
+    row_bytes = 2 * 4 * int(np.prod(z.shape[1:]))
+    k = max(2, min(n_spec, DUMP_BYTES // (world * row_bytes)))
+    rng = np.random.default_rng(20240 + rank)
+    idx = np.unique(np.concatenate([[0, n_spec - 1], rng.choice(n_spec, k - 2, replace=False)]))
+    spectra = np.stack([z[int(s):int(s) + 1].to_host()[0] for s in idx])
+    suffix = f'_rank{rank}' if world > 1 else ''
+    os.makedirs(directory, exist_ok=True)
+    np.save(os.path.join(directory, f'spectra{suffix}.npy'),
+            np.ascontiguousarray(spectra.view(np.float32).reshape(spectra.shape + (2,))))
+    np.save(os.path.join(directory, f'spectra_index{suffix}.npy'), idx.astype(np.float64))
+
+
 # ---------------------------------------------------------------------------
 def _inject(what):
     """BBT_BENCH_INJECT=bcast,gather: make that collective fail on every rank (tests of the
@@ -784,16 +825,16 @@ def run_rank(args):
         ch.seek(0)
         return ch.read_device(n_spec)
 
-    # Per-kernel timing of the overlap-save passes: HIP events on the stream
-    # each pass is launched on, recorded inside the timed region itself, in the
-    # normal multi-lane schedule (what rocprofv3 --kernel-trace sees as well).
+    # --full: per-kernel timing of the overlap-save passes: HIP events on the
+    # stream each pass is launched on, recorded inside the timed region itself,
+    # in the normal multi-lane schedule (what rocprofv3 --kernel-trace sees as well).
     plan = dd._get_plan()
     for _ in range(args.warmup):
         step()
     gc.collect()        # CPython's full collection over torch's object graph is a ~50 ms pause;
     gc.disable()        # the steps allocate no cycles, so none is due inside the timed region
     fence()
-    if not args.no_kernel_timing:
+    if args.full and not args.no_kernel_timing:
         plan.timing_enable(1)
     t0 = time.perf_counter()
     for _ in range(args.steps):
@@ -806,7 +847,49 @@ def run_rank(args):
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
     value = world * samples_per_step * args.steps / elapsed / 1e6
-    n_steps_timed = args.steps
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, z, rank, world)
+    path_gbps = value * 1e6 / world * alg_bytes / 1e9
+    roofline_path = dict(bound='hbm', achieved=round(path_gbps, 1), peak=HBM_PEAK_GBPS, unit='GB/s',
+                         frac=round(path_gbps / HBM_PEAK_GBPS, 4),
+                         input_msamples_per_s=round(value * dd._ih_samples_per_frame / spf, 1),
+                         note='whole path per GPU: alg_bytes_per_unit x valid samples / wall time; '
+                              'input_msamples_per_s = value / eta (all GPUs)')
+    roofline = verified = with_gather = cpu = host = None
+    if args.full:
+        roofline, verified, with_gather, cpu, host = full_measurements(
+            args, torch, dist, bt, sharding, comm, backend, dev, coll_dev, world, rank, step, fence, plan, x, z,
+            blocks, n_spec, spf, alg_bytes, samples_per_step, freq if args.workload == 'config4' else None)
+
+    failed = bool(verified and not verified['all_ranks_ok'])
+    if rank == 0:
+        line = dict(
+            metric='Msamples/s through Dedisperse(DM=100)+Channelize(1k ch), 2-pol c64'
+            if args.workload == 'headline' else
+            'M complete samples/s (sub-bands x 2 pol per sample) through Dedisperse(DM=557)+Channelize(64)',
+            value=round(value, 1), unit='Msamples/s', n_gpus=world, steps=args.steps,
+            warmup=args.warmup, ms_per_step=round(elapsed / args.steps * 1e3, 4),
+            higher_is_better=True, scaling='weak', vs_baseline=None, dtype='c64',
+            data='synthetic',
+            config=dict(workload=workload, blocks_per_step_per_gpu=blocks,
+                        n_fft=N_FFT if args.workload == 'headline' else C4_NFFT, n_chan=n_chan,
+                        streams_per_gpu=streams,
+                        valid_samples_per_step_per_gpu=samples_per_step,
+                        outputs='left sharded on the ranks (value); with_gather includes the all-gather',
+                        sharding=sharding_note),
+            roofline=roofline, roofline_path=roofline_path, cpu_baseline=cpu, verified=verified,
+            with_gather=with_gather, host_path=host)
+        print(json.dumps(line), flush=True)
+    if world > 1:
+        dist.destroy_process_group()
+    if failed:
+        print('bench.py: verification against the oracle FAILED', file=sys.stderr)
+        sys.exit(3)
+
+
+def full_measurements(args, torch, dist, bt, sharding, comm, backend, dev, coll_dev, world, rank, step, fence,
+                      plan, x, z, blocks, n_spec, spf, alg_bytes, samples_per_step, freq):
+    """--full, after the timed steps: (roofline, verified, with_gather, cpu_baseline, host_path)."""
     if args.no_kernel_timing:               # A/B switch: time the kernels in extra steps instead
         plan.timing_enable(1)
         n_steps_timed = max(3, args.steps // 2)
@@ -878,12 +961,6 @@ def run_rank(args):
                          'BBT_OSM_TIMING_STRIDE-th launch, `launches` of them); isolated = one stream, '
                          'nothing else running; achieved = alg_bytes_per_unit x valid samples per launch '
                          '/ avg launch duration of the dominant pass')
-    path_gbps = value * 1e6 / world * alg_bytes / 1e9
-    roofline_path = dict(bound='hbm', achieved=round(path_gbps, 1), peak=HBM_PEAK_GBPS, unit='GB/s',
-                         frac=round(path_gbps / HBM_PEAK_GBPS, 4),
-                         input_msamples_per_s=round(value * dd._ih_samples_per_frame / spf, 1),
-                         note='whole path per GPU: alg_bytes_per_unit x valid samples / wall time; '
-                              'input_msamples_per_s = value / eta (all GPUs)')
 
     # ---- outputs gathered: time steps that end with the collective
     with_gather = None
@@ -902,38 +979,14 @@ def run_rank(args):
             host = host_path(bt, torch)
         except Exception as exc:            # (reported, never fails the resident number)
             host = dict(error=f'{type(exc).__name__}: {exc}'[:300])
-
-    failed = bool(verified and not verified['all_ranks_ok'])
-    if rank == 0:
-        line = dict(
-            metric='Msamples/s through Dedisperse(DM=100)+Channelize(1k ch), 2-pol c64'
-            if args.workload == 'headline' else
-            'M complete samples/s (sub-bands x 2 pol per sample) through Dedisperse(DM=557)+Channelize(64)',
-            value=round(value, 1), unit='Msamples/s', n_gpus=world, steps=args.steps,
-            warmup=args.warmup, ms_per_step=round(elapsed / args.steps * 1e3, 4),
-            higher_is_better=True, scaling='weak', vs_baseline=None, dtype='c64',
-            data='synthetic',
-            config=dict(workload=workload, blocks_per_step_per_gpu=blocks,
-                        n_fft=N_FFT if args.workload == 'headline' else C4_NFFT, n_chan=n_chan,
-                        streams_per_gpu=streams,
-                        valid_samples_per_step_per_gpu=samples_per_step,
-                        outputs='left sharded on the ranks (value); with_gather includes the all-gather',
-                        sharding=sharding_note),
-            roofline=roofline, roofline_path=roofline_path, cpu_baseline=cpu, verified=verified,
-            with_gather=with_gather, host_path=host)
-        print(json.dumps(line), flush=True)
-    if world > 1:
-        dist.destroy_process_group()
-    if failed:
-        print('bench.py: verification against the oracle FAILED', file=sys.stderr)
-        sys.exit(3)
+    return roofline, verified, with_gather, cpu, host
 
 
 def main():
     args = parse()
     if 'WORLD_SIZE' not in os.environ and args.gpus > 1:
         sys.exit(launch_ranks(args))
-    if (int(os.environ.get('WORLD_SIZE', '1')) == 1 and not args.no_traffic and not args.traffic_child
+    if (args.full and int(os.environ.get('WORLD_SIZE', '1')) == 1 and not args.no_traffic and not args.traffic_child
             and not os.environ.get('BBT_BENCH_DRYRUN')):
         args.traffic_live = measure_traffic(args)          # (children; this process has not touched the GPU yet)
     run_rank(args)

@@ -3288,7 +3288,7 @@ def test_bench_two_ranks_share_this_gpu():
     env = dict(os.environ, BBT_BENCH_BACKEND='gloo')
     env.pop('WORLD_SIZE', None)
     r = subprocess.run([sys.executable, os.path.join(root, 'bench.py'), '--gpus', '2', '--steps', '2',
-                        '--warmup', '1', '--blocks', '24', '--no-cpu'], env=env, capture_output=True,
+                        '--warmup', '1', '--blocks', '24', '--full', '--no-cpu'], env=env, capture_output=True,
                        text=True, timeout=900)
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith('{')]
@@ -3303,13 +3303,65 @@ def test_bench_two_ranks_share_this_gpu():
     # figure is reported missing -- and the sharded value stands, verified on every rank
     env['BBT_BENCH_INJECT'] = 'bcast,gather'
     r = subprocess.run([sys.executable, os.path.join(root, 'bench.py'), '--gpus', '2', '--steps', '2',
-                        '--warmup', '1', '--blocks', '24', '--no-cpu'], env=env, capture_output=True,
+                        '--warmup', '1', '--blocks', '24', '--full', '--no-cpu'], env=env, capture_output=True,
                        text=True, timeout=900)
     assert r.returncode == 0, r.stderr[-2000:]
     d = json.loads([ln for ln in r.stdout.splitlines() if ln.startswith('{')][0])
     assert d['n_gpus'] == 2 and d['value'] > 0 and d['verified']['ok'] and d['verified']['all_ranks_ok']
     assert 'injected gather failure' in d['with_gather']['error']
     assert 'the broadcast failed' in d['config']['sharding']
+
+
+def test_bench_plain_run_dumps_its_outputs(tmp_path):
+    """A plain `python bench.py` run times exactly --steps steps, leaves what only --full measures
+    null, and --dump-outputs writes a seeded sample of the last timed step's spectra: float32
+    (row, channel, pol, re/im) with float64 row numbers; the first spectrum matches the oracle on the
+    benchmark's own seeded input (regenerated with torch in a child process: torch stays out of this
+    one, whose HIP runtime the library already holds)."""
+    import json
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    env = dict(os.environ)
+    env.pop('WORLD_SIZE', None)
+    out = tmp_path / 'dump'
+    r = subprocess.run([sys.executable, os.path.join(root, 'bench.py'), '--gpus', '1', '--steps', '3',
+                        '--warmup', '1', '--blocks', '24', '--dump-outputs', str(out)], env=env,
+                       capture_output=True, text=True, timeout=600)
+    assert r.returncode == 0, r.stderr[-2000:]
+    lines = [ln for ln in r.stdout.splitlines() if ln.startswith('{')]
+    assert len(lines) == 1
+    d = json.loads(lines[0])
+    assert d['steps'] == 3 and d['warmup'] == 1 and d['ms_per_step'] > 0 and d['value'] > 0
+    assert d['unit'] == 'Msamples/s' and d['higher_is_better'] is True and d['dtype'] == 'c64'
+    assert all(d[k] is None for k in ('roofline', 'verified', 'cpu_baseline', 'host_path', 'with_gather'))
+    spectra = np.load(out / 'spectra.npy')
+    index = np.load(out / 'spectra_index.npy')
+    n_spec = (24 * 836100 // 1024 // 512) * 512
+    assert spectra.dtype == np.float32 and index.dtype == np.float64
+    assert spectra.shape == (len(index), 1024, 2, 2) and spectra.nbytes + index.nbytes <= 64 << 20
+    assert index[0] == 0 and index[-1] == n_spec - 1 and np.all(np.diff(index) > 0)
+    assert np.all(np.isfinite(spectra)) and np.any(spectra != 0)
+    # the benchmark's input: torch.randn of (n_in, 2 pol, re/im) from a cuda:0 generator seeded 12345
+    script = '''
+import sys
+import numpy as np
+import torch
+sys.path.insert(0, %r)
+from oracle import bbt_oracle as orc
+n_fft = 2**20
+gen = torch.Generator(device="cuda:0")
+gen.manual_seed(12345)
+x = torch.randn((23 * 836100 + n_fft, 2, 2), generator=gen, device="cuda:0", dtype=torch.float32)
+xin = torch.view_as_complex(x[:n_fft]).cpu().numpy()
+g = orc.disperse_geometry(16e6, 1000., 1, -100.)
+h = orc.chirp(n_fft, 16e6, 1000., 1, -100., g["reference_frequency"])
+y = orc.disperse_block(xin, h, g["pad_start"], n_fft - g["pad_start"] - g["pad_end"])
+np.save(sys.argv[1], np.fft.fft(y[:1024].astype(np.complex128), axis=0))
+''' % root
+    want_file = tmp_path / 'want.npy'
+    done = subprocess.run([sys.executable, '-c', script, str(want_file)], env=env, capture_output=True, text=True,
+                          timeout=300)
+    assert done.returncode == 0, done.stderr[-2000:]
+    assert rel_l2(spectra[0, ..., 0] + 1j * spectra[0, ..., 1], np.load(want_file)) < 1e-6
 
 
 def test_default_arguments_at_full_scale_golden(golden):

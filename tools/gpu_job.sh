@@ -3,7 +3,7 @@
 # Every job writes under gpurun_out/$TAG/ (default tag: the job's name) and joins its GPU steps with
 # `&&`-like logic where a failure should stop the rest (status lines go to $OUT/status.txt).
 #
-#   suite                     whole GPU test suite (-x), then the default bench.py
+#   suite                     whole GPU test suite (-x), then bench.py --full
 #   tests   K=<expr> [F=<files>] [T=<s>]     selected tests (pytest -k) of test_gpu_parity.py or files F
 #   stress  SEEDS="0 1 .."    the randomised tests under many BBT_TEST_SEEDs + the padding regression + tools/soak_reads.py
 #   ab      A=<lib> B=<lib> [ARGS=..] [N=3]  alternating headline runs of two library builds
@@ -14,6 +14,7 @@
 #   chain   LABEL=<label>     kernel trace of one chain of tools/default_device_reads.py -> tools/chain_timeline.py
 #   prof3   NAME=<n> CMD=".." kernel stats + FETCH_SIZE + WRITE_SIZE (three separate runs) of a command
 #   sq      [CMD=..]          SQ counters (two passes of 8) of a command (default: headline, 96 blocks)
+#   gloo2                     bench.py --full rehearsal of two ranks sharing this GPU (gloo)
 #   evidence                  round-end: suite, profiles of every config, timeline, SQ counters, bench
 #                             lines, next rows, generic lengths, host path (then: tools/summarise.sh)
 set -o pipefail
@@ -56,6 +57,9 @@ sq () {   # name, command...
       timeout -k 10 400 rocprofv3 --pmc $C1 -d $OUT/prof/$name/sq1 -o run -- "$@" > $OUT/prof/$name/sq1.log 2>&1; say "$name sq1 rc=$?"
       timeout -k 10 400 rocprofv3 --pmc $C2 -d $OUT/prof/$name/sq2 -o run -- "$@" > $OUT/prof/$name/sq2.log 2>&1; say "$name sq2 rc=$?" )
 }
+gloo2 () {
+    BBT_BENCH_BACKEND=gloo timeout -k 10 300 python3 bench.py --full --gpus 2 --steps 5 --blocks 192 --no-cpu --no-host-path > $OUT/bench_gloo2.json 2> $OUT/bench_gloo2.err; say "gloo2 rc=$?"
+}
 suite () {
     timeout -k 10 1100 python3 -m pytest tests -m gpu -q -x > $OUT/pytest.log 2>&1; local rc=$?
     say "pytest rc=$rc"; tail -3 $OUT/pytest.log
@@ -64,7 +68,7 @@ suite () {
 
 case $JOB in
 suite)
-    suite && timeout -k 10 600 python3 bench.py > $OUT/bench.json 2> $OUT/bench.err && value $OUT/bench.json bench ;;
+    suite && timeout -k 10 600 python3 bench.py --full > $OUT/bench.json 2> $OUT/bench.err && value $OUT/bench.json bench ;;
 tests)
     timeout -k 10 ${T:-900} python3 -m pytest ${F:-tests/test_gpu_parity.py} -m gpu -q -x ${K:+-k "$K"} > $OUT/log.txt 2>&1; say "tests rc=$?"
     tail -15 $OUT/log.txt ;;
@@ -79,7 +83,7 @@ ab|envab)
     for r in $(seq 1 ${N:-3}); do
         for v in A B; do
             if [ $JOB = ab ]; then e="BBT_HIP_LIB=${!v}"; else n=ENV_$v; e="${!n}"; fi
-            env $e timeout -k 10 300 python3 bench.py --no-cpu --no-verify --no-host-path --no-traffic --steps 20 $ARGS > $OUT/$v$r.json 2> $OUT/$v$r.err || { say "$v$r failed"; tail -5 $OUT/$v$r.err; exit 1; }
+            env $e timeout -k 10 300 python3 bench.py --full --no-cpu --no-verify --no-host-path --no-traffic --steps 20 $ARGS > $OUT/$v$r.json 2> $OUT/$v$r.err || { say "$v$r failed"; tail -5 $OUT/$v$r.err; exit 1; }
             value $OUT/$v$r.json "$v ($e)"
         done
     done ;;
@@ -111,6 +115,8 @@ prof3)
     prof3 ${NAME:?NAME} $CMD ;;
 sq)
     sq ${NAME:-headline} ${CMD:-python3 $R/bench.py --steps 2 --warmup 1 --blocks 96 --no-cpu --no-verify --no-host-path --no-traffic} ;;
+gloo2)
+    gloo2 ;;
 evidence)
     suite || exit 1
     prof3 headline python3 $R/bench.py --steps 4 --warmup 1 --no-cpu --no-verify --no-host-path --no-traffic
@@ -120,10 +126,10 @@ evidence)
     sq headline python3 $R/bench.py --steps 2 --warmup 1 --blocks 96 --no-cpu --no-verify --no-host-path --no-traffic
     for c in config1 config2 config3 config5; do timeout -k 10 200 python3 tools/bench_one.py $c; done > $OUT/bench_one.jsonl 2> $OUT/bench_one.err
     cat $OUT/bench_one.jsonl
-    timeout -k 10 600 python3 bench.py > $OUT/bench.json 2> $OUT/bench.err; say "bench rc=$?"
-    timeout -k 10 500 python3 bench.py --workload config4 --steps 3 --warmup 2 --blocks 4 > $OUT/bench_c4.json 2> $OUT/bench_c4.err; say "c4 rc=$?"
+    timeout -k 10 600 python3 bench.py --full > $OUT/bench.json 2> $OUT/bench.err; say "bench rc=$?"
+    timeout -k 10 500 python3 bench.py --full --workload config4 --steps 3 --warmup 2 --blocks 4 > $OUT/bench_c4.json 2> $OUT/bench_c4.err; say "c4 rc=$?"
     timeout -k 10 900 python3 tools/bench_next.py > $OUT/next_rows.jsonl 2> $OUT/next_rows.err; say "next rc=$?"
-    BBT_BENCH_BACKEND=gloo timeout -k 10 300 python3 bench.py --gpus 2 --steps 5 --blocks 192 --no-cpu --no-host-path > $OUT/bench_gloo2.json 2> $OUT/bench_gloo2.err; say "gloo2 rc=$?"
+    gloo2
     timeout -k 10 300 python3 tools/bench_generic.py > $OUT/generic.txt 2>&1; say "generic rc=$?"
     timeout -k 10 300 python3 tools/bench_host_path.py --blocks 192 --run 16 > $OUT/host_path.jsonl 2> $OUT/host_path.err; say "host rc=$?"
     timeout -k 10 300 python3 tools/pcie_probe.py > $OUT/pcie.txt 2>&1; say "pcie rc=$?"
