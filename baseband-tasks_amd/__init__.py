@@ -20,7 +20,7 @@ from .channelize import Channelize, Dechannelize
 from .pfb import (sinc_hamming, PolyphaseFilterBank, PolyphaseFilterBankSamples,
                   InversePolyphaseFilterBank)
 from .functions import Square, Power
-from .integration import Integrate
+from .integration import Integrate, Fold, PulseStack
 from .ingest import RawFrameStream, open_vdif, open_dada
 from . import hip
 from . import hdf5

@@ -609,9 +609,19 @@ class _TimeSlice(Base):
         self.ih = ih
         self._first = start
         self.meta = getattr(ih, 'meta', {})
+        # (streams whose samples are not evenly spaced in time -- pulse-phase bins -- tell
+        # the time of every offset themselves)
+        self._time_from_ih = bool(getattr(ih, '_time_from_offsets', False))
+        start_time = (ih._tell_time(start) if self._time_from_ih
+                      else _stream_start(ih) + start / _stream_rate(ih))
         super().__init__((stop - start,) + tuple(ih.shape[1:]),
-                         _stream_start(ih) + start / _stream_rate(ih), _stream_rate(ih),
+                         start_time, _stream_rate(ih),
                          samples_per_frame=ih.samples_per_frame, dtype=ih.dtype)
+
+    def _tell_time(self, offset):
+        if self._time_from_ih:
+            return self.ih._tell_time(self._first + offset)
+        return super()._tell_time(offset)
 
     def read(self, count=None, out=None):
         count = self._prepare_read(count, out)

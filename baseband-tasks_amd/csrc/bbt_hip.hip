@@ -23,10 +23,11 @@
 #include "big_kernels.hpp"
 #include "gen2_host.hpp"
 #include "rtc.hpp"
+#include "fold_kernels.hpp"
 
 using namespace bbt;
 
-#define BBT_VERSION 152
+#define BBT_VERSION 153
 
 // ---------------------------------------------------------------------------
 // errors
@@ -2982,6 +2983,72 @@ extern "C" int bbt_detect_power_axis(const void* in_dev, void* out_dev, int64_t 
                        (const float2*)in_dev, (float*)out_dev, (long long)n_out, (long long)step, outer, inner,
                        average ? 1.0f / (float)step : 1.0f);
     HIP_TRY(hipGetLastError());
+    return 0;
+}
+
+// ---------------------------------------------------------------------------
+// folding by a run table (fold_kernels.hpp)
+extern "C" int bbt_fold_runs(const void* in_dev, void* out_dev, int64_t n_in, int64_t n_elem, int mode,
+                             const int64_t* slot_ptr_dev, const int64_t* run_begin_dev,
+                             const int64_t* run_end_dev, int64_t n_slot, const float* scale_dev,
+                             int accumulate, void* work_dev, int64_t work_floats, bbt_stream stream) {
+    ARG_TRY(in_dev && out_dev && slot_ptr_dev && run_begin_dev && run_end_dev,
+            "bbt_fold_runs: null argument");
+    ARG_TRY(n_in >= 0 && n_elem >= 1 && n_slot >= 0 && work_floats >= 0, "bbt_fold_runs: bad sizes");
+    ARG_TRY(mode >= 0 && mode <= 2, "bbt_fold_runs: mode must be 0 (square), 1 (power) or 2 (sum)");
+    ARG_TRY(mode != 1 || n_elem % 2 == 0,
+            "bbt_fold_runs: power needs (X, Y) pairs, n_elem=%lld is odd", (long long)n_elem);
+    ARG_TRY(accumulate == 0 || accumulate == 1, "bbt_fold_runs: accumulate must be 0 or 1");
+    ARG_TRY(mode != 1 || ((uintptr_t)in_dev & 15) == 0, "bbt_fold_runs: power needs 16-byte aligned input");
+    ARG_TRY(work_floats == 0 || work_dev, "bbt_fold_runs: work_floats > 0 needs a work area");
+    if (n_slot == 0) return 0;
+    // units: what one lane loads per sample (16 bytes where the row and the address allow)
+    const long long in_bytes = mode == 2 ? 4 : 8;
+    const long long elems_per_vec = 16 / in_bytes;
+    const bool vec = mode == 1 || (n_elem % elems_per_vec == 0 && ((uintptr_t)in_dev & 15) == 0);
+    const long long n_unit = vec ? n_elem / elems_per_vec : n_elem;
+    const int outw = mode == 1 ? 4 : (mode == 0 ? (vec ? 2 : 1) : (vec ? 4 : 1));
+    const long long n_out_f = n_unit * outw;
+    int lg_tc = 0;
+    while (lg_tc < 8 && (1ll << lg_tc) < n_unit) ++lg_tc;
+    const int tt = 256 >> lg_tc;
+    const long long tiles = (n_unit + (1ll << lg_tc) - 1) >> lg_tc;
+    // split of each slot's samples over workgroups, from the arguments only: about 2048
+    // workgroups in all (8 per CU), at most 64 shares, at least ~64 samples per lane on average,
+    // and no more shares than the work area holds
+    const long long base = tiles * n_slot;
+    long long split = (2048 + base - 1) / base;
+    split = std::min(split, 64ll);
+    split = std::min(split, std::max(1ll, (long long)(n_in / (n_slot * tt * 64ll))));
+    split = std::min(split, std::max(1ll, (long long)(work_floats / (n_slot * n_out_f))));
+    if (!work_dev) split = 1;
+    ARG_TRY(base * split < (1ll << 31), "bbt_fold_runs: too many slots x columns for one call");
+    hipStream_t st = (hipStream_t)stream;
+    float* out = (float*)out_dev;
+    float* dst = split == 1 ? out : (float*)work_dev;
+    const float* prev = split == 1 && accumulate ? out : nullptr;
+    const float* sc = split == 1 ? scale_dev : nullptr;
+    const long long stride = n_slot * n_out_f;
+    const dim3 grid((unsigned)(base * split)), block(256);
+#define BBT_FOLD_LAUNCH(M, V)                                                                            \
+    hipLaunchKernelGGL((k_fold_gather<M, V>), grid, block, 0, st, in_dev, dst, (long long)n_in, n_unit,  \
+                       lg_tc, tiles, (long long)n_slot, (int)split, (const long long*)slot_ptr_dev,      \
+                       (const long long*)run_begin_dev, (const long long*)run_end_dev, prev, sc, stride)
+    if (mode == 1) BBT_FOLD_LAUNCH(1, 1);
+    else if (mode == 0 && vec) BBT_FOLD_LAUNCH(0, 1);
+    else if (mode == 0) BBT_FOLD_LAUNCH(0, 0);
+    else if (vec) BBT_FOLD_LAUNCH(2, 1);
+    else BBT_FOLD_LAUNCH(2, 0);
+#undef BBT_FOLD_LAUNCH
+    HIP_TRY(hipGetLastError());
+    if (split > 1) {
+        const long long total = n_slot * n_out_f;
+        ARG_TRY((total + 255) / 256 < (1ll << 31), "bbt_fold_runs: too many output elements for one call");
+        hipLaunchKernelGGL(k_fold_combine, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st,
+                           (const float*)work_dev, out, (long long)n_slot, n_out_f, (int)split, stride,
+                           scale_dev, accumulate);
+        HIP_TRY(hipGetLastError());
+    }
     return 0;
 }
 

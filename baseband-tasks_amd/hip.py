@@ -94,6 +94,7 @@ SIGNATURES = {
     'bbt_pfb_plan_destroy': [_vp],
     'bbt_pfb_execute': [_vp, _vp, _vp, _i64, _vp],
     'bbt_detect_integrate': [_vp, _vp, _i64, _i64, _i64, _int, _int, _vp],
+    'bbt_fold_runs': [_vp, _vp, _i64, _i64, _int, _vp, _vp, _vp, _i64, _vp, _int, _vp, _i64, _vp],
     'bbt_shift_plan_create': [_pvp, _int, _int, _pi32],
     'bbt_shift_plan_destroy': [_vp],
     'bbt_shift_execute': [_vp, _vp, _vp, _i64, _vp],
@@ -114,7 +115,7 @@ SIGNATURES = {
 }
 
 #: oldest libbbt_hip.so whose entry points and argument meanings this binding assumes
-MIN_LIB_VERSION = 152
+MIN_LIB_VERSION = 153
 
 _lib = None
 _lock = threading.Lock()
@@ -701,6 +702,49 @@ def detect_integrate(in_dev, out_dev, n_out, step, n_elem, mode, average=True):
     """Square (mode 0) / Power (1) / plain sum (2) over ``step`` samples."""
     check(lib().bbt_detect_integrate(in_dev.ptr_to_read(), out_dev.ptr, int(n_out), int(step), int(n_elem),
                                      int(mode), int(bool(average)), _stream))
+
+
+#: shares a slot of `fold_runs` may be split into (bounds its work area)
+FOLD_MAX_SPLIT = 64
+
+
+def fold_runs(in_dev, out_dev, n_elem, mode, slot_ptr, run_begin, run_end, scale=None,
+              accumulate=False):
+    """Sum (after detection ``mode``, as `detect_integrate`) the input samples of every run of
+    every slot into rows of ``out_dev`` (see bbt_fold_runs in include/bbt_hip.h).
+
+    ``slot_ptr`` (n_slot + 1), ``run_begin`` / ``run_end`` are host int64 arrays (checked
+    against the input here, then uploaded); ``scale`` an optional float32 array (n_slot)."""
+    slot_ptr = np.ascontiguousarray(slot_ptr, dtype=np.int64)
+    run_begin = np.ascontiguousarray(run_begin, dtype=np.int64)
+    run_end = np.ascontiguousarray(run_end, dtype=np.int64)
+    n_slot = len(slot_ptr) - 1
+    n_in = in_dev.shape[0] if in_dev.shape else 0
+    if n_slot < 0 or run_begin.shape != run_end.shape or slot_ptr[0] != 0 or slot_ptr[-1] != len(run_begin):
+        raise ValueError("fold_runs: slot_ptr does not describe the runs")
+    if n_slot == 0:
+        return out_dev
+    if np.any(np.diff(slot_ptr) < 0):
+        raise ValueError("fold_runs: slot_ptr must not decrease")
+    if len(run_begin) and (run_begin.min() < 0 or run_end.max() > n_in or np.any(run_end < run_begin)):
+        raise ValueError("fold_runs: runs outside the input")
+    n_out_f = 2 * int(n_elem) if mode == 1 else int(n_elem)
+    if out_dev.size * (2 if out_dev.dtype.kind == 'c' else 1) != n_slot * n_out_f:
+        raise ValueError("fold_runs: output is not n_slot rows of the mode's width")
+    if in_dev.size * (2 if in_dev.dtype.kind == 'c' else 1) != n_in * int(n_elem) * (1 if mode == 2 else 2):
+        raise ValueError("fold_runs: input is not n_in samples of n_elem elements")
+    n_runs = len(run_begin)
+    table = DeviceArray.from_host(np.concatenate([slot_ptr, run_begin, run_end]))
+    tptr = table.ptr
+    sc = DeviceArray.from_host(np.ascontiguousarray(scale, dtype=np.float32)) if scale is not None else None
+    work_floats = min(FOLD_MAX_SPLIT * n_slot * n_out_f, 1 << 24)
+    work = DeviceArray((work_floats,), np.float32) if work_floats >= 2 * n_slot * n_out_f else None
+    check(lib().bbt_fold_runs(in_dev.ptr_to_read(), out_dev.ptr, int(n_in), int(n_elem), int(mode),
+                              tptr, tptr + 8 * (n_slot + 1), tptr + 8 * (n_slot + 1 + n_runs),
+                              int(n_slot), sc.ptr if sc is not None else None, int(bool(accumulate)),
+                              work.ptr if work is not None else None,
+                              int(work_floats) if work is not None else 0, _stream))
+    return out_dev
 
 
 def detect_power_axis(in_dev, out_dev, n_out, step, outer, inner, average=True):

@@ -61,6 +61,11 @@ class Time:
     comparisons; enough for `start_time`, `time`, `stop_time` and
     `seek(Time)` of the stream interface (base.py:286-310, 331-341).
     Leap seconds are ignored (as in ``datetime``).
+
+    ``t + ndarray_of_seconds`` gives an array-valued time (``sec`` an int64 array,
+    ``frac`` a float array): ``t_array - t_scalar`` (float64 seconds), ``.unix`` and
+    ``.jd1_jd2()`` then work elementwise, as a pulse-phase callable needs them
+    (see `~baseband_tasks_amd.integration.Fold`).  Scalar arithmetic is unchanged.
     """
     __slots__ = ('sec', 'frac')
 
@@ -110,7 +115,8 @@ class Time:
 
     def jd1_jd2(self):
         """Julian date as two doubles whose sum is exact to the float: whole days (as
-        ``x.5``) and the fraction of the day -- the pair astropy's `Time` stores."""
+        ``x.5``) and the fraction of the day -- the pair astropy's `Time` stores
+        (elementwise for an array-valued time)."""
         days, rest = divmod(self.sec, 86400)
         return 2440587.5 + days, (rest + self.frac) / 86400.
 
@@ -123,14 +129,54 @@ class Time:
 
     def __add__(self, seconds):
         seconds = to_seconds(seconds)
+        if isinstance(seconds, np.ndarray) or isinstance(self.sec, np.ndarray):
+            return self._add_array(seconds)
         whole = math.floor(seconds)
         return Time(self.sec + int(whole), self.frac + (seconds - whole))
+
+    # -- array-valued times: ``t0 + ndarray_of_seconds`` (what a phase callable receives) --
+    @classmethod
+    def _from_arrays(cls, sec, frac):
+        """Elementwise (integer seconds, fraction) with the fraction brought into [0, 1)."""
+        frac = np.asarray(frac, dtype=float)
+        carry = np.floor(frac)
+        self = object.__new__(cls)
+        self.sec = np.asarray(sec, dtype=np.int64) + carry.astype(np.int64)
+        self.frac = frac - carry
+        return self
+
+    def _add_array(self, seconds):
+        seconds = np.asarray(seconds, dtype=float)
+        whole = np.floor(seconds)
+        return Time._from_arrays(self.sec + whole.astype(np.int64), self.frac + (seconds - whole))
+
+    @property
+    def shape(self):
+        return np.shape(self.sec)
+
+    @property
+    def isscalar(self):
+        return not isinstance(self.sec, np.ndarray)
+
+    def __len__(self):
+        if self.isscalar:
+            raise TypeError("scalar Time has no len()")
+        return len(self.sec)
+
+    def __getitem__(self, item):
+        if self.isscalar:
+            raise TypeError("scalar Time cannot be indexed")
+        sec, frac = self.sec[item], self.frac[item]
+        if np.ndim(sec) == 0:
+            return Time(int(sec), float(frac))
+        return Time._from_arrays(sec, frac)
 
     __radd__ = __add__
 
     def __sub__(self, other):
         if isinstance(other, Time) or hasattr(other, 'isot'):
-            other = Time(other)
+            if not isinstance(other, Time):
+                other = Time(other)
             return (self.sec - other.sec) + (self.frac - other.frac)
         return self.__add__(-to_seconds(other))
 
@@ -150,6 +196,8 @@ class Time:
         return hash(self._key())
 
     def __repr__(self):
+        if not self.isscalar:
+            return "<Time array shape=%s first=%s>" % (self.shape, self[0].isot if self.sec.size else None)
         return "Time('%s')" % self.isot
 
     __str__ = __repr__

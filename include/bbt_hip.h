@@ -335,6 +335,25 @@ int bbt_detect_integrate(const void* in_dev, void* out_dev, int64_t n_out, int64
 int bbt_detect_power_axis(const void* in_dev, void* out_dev, int64_t n_out, int64_t step, int outer,
                           int inner, int average, bbt_stream stream);
 
+/* ---- folding by a run table --------------------------------------------------
+ * Replaces Fold._integrate (integration.py:380-395) and, for a phase step,
+ * Integrate._integrate (270-303).  Output slot j (a (row, phase bin) of a fold,
+ * an output sample of a phase integration) owns runs slot_ptr[j] ..
+ * slot_ptr[j+1]-1; run r covers input samples [run_begin[r], run_end[r]) of
+ * `in` (n_in complete samples; all int64 arrays in device memory):
+ *   acc[j, :] = (accumulate ? out[j, :] : 0) + sum_{runs r of j} sum_{t in r} f(in[t, :])
+ *   out[j, :] = scale ? scale[j] * acc[j, :] : acc[j, :]
+ * f and the layouts as bbt_detect_integrate's modes 0, 1, 2 (out has n_slot
+ * rows).  No atomics: the sums depend only on the arguments.  A slot's samples
+ * may be split over up to work_floats / (n_slot * output floats per row)
+ * workgroups whose shares go to `work` (device, float32; NULL / 0: no split)
+ * and are added in a fixed order; pass `scale` (1/count, NaN for count 0) with
+ * the last chunk of a row only. */
+int bbt_fold_runs(const void* in_dev, void* out_dev, int64_t n_in, int64_t n_elem, int mode,
+                  const int64_t* slot_ptr_dev, const int64_t* run_begin_dev,
+                  const int64_t* run_end_dev, int64_t n_slot, const float* scale_dev, int accumulate,
+                  void* work_dev, int64_t work_floats, bbt_stream stream);
+
 /* ---- integer sample shifts -------------------------------------------------
  * Replaces ShiftSamples.task (sampling.py:424-425, data[self._indices]), the
  * base of DisperseSamples / DedisperseSamples (dispersion.py:193-298):

@@ -1,0 +1,367 @@
+"""`Fold`, `PulseStack` and ``Integrate(phase=...)`` on the GPU: the reference's
+TestFold, TestIntegratePhase and TestPulseStack (baseband_tasks/tests/
+test_integration.py:286-520) in this package's units, the golden vectors of the
+real reference (tests/golden/fold_vectors.npz), and randomised parity against a
+NumPy fold in float64."""
+import os
+
+import numpy as np
+import pytest
+
+import baseband_tasks_amd as bt
+from baseband_tasks_amd import hip
+from baseband_tasks_amd import units as u
+from baseband_tasks_amd.fold_table import unwrapped_bin
+
+pytestmark = pytest.mark.gpu
+
+
+def close(a, b):
+    """float32 sums times a float32 1/count: equal to the reference's float64 means to rtol 1e-6."""
+    return np.allclose(a, b, rtol=1e-6, atol=0, equal_nan=True)
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+T0 = bt.Time('2010-11-12T13:14:15')
+RATE = 10. * u.kHz
+PERIOD = 125
+F0 = 1. / (PERIOD / RATE)
+N_PHASE = 50
+
+
+def phase(t):
+    return F0 * (t - T0)
+
+
+class TwoPart:
+    """A phase with ``.int`` and ``.frac`` (astropy ``Phase``-like)."""
+
+    def __init__(self, cycles):
+        self.int = np.floor(cycles)
+        self.frac = cycles - self.int
+
+
+def phase2(t):
+    return TwoPart(phase(t))
+
+
+@pytest.fixture(scope='module')
+def pulsar():
+    data = np.repeat(np.where(np.arange(16000) % PERIOD == 0, 10., 0.125)[:, None], 2, axis=1)
+    sh = bt.HostStream(data.astype(np.float32), T0, RATE, samples_per_frame=200, pin=False)
+    return sh, data
+
+
+# -- the reference's TestFold --------------------------------------------------------
+@pytest.mark.parametrize('ph', [phase, phase2])
+def test_step_shorter_than_period(pulsar, ph):
+    sh, _ = pulsar
+    fh = bt.Fold(sh, N_PHASE, ph, 10 * u.ms, average=False)
+    fr = fh.read(3)
+    c, d = fr['count'][..., 0], fr['data']
+    assert np.all(c.sum(1) == 100)
+    assert np.all((c[0, :40] == 3) | (c[0, :40] == 2))
+    assert np.all(c[0, 41:] == 0)
+    assert np.all(c[1, :30] != 0) and np.all(c[1, 40:] != 0) and np.all(c[1, 31:39] == 0)
+    assert np.all(c[2, :20] != 0) and np.all(c[2, 30:] != 0) and np.all(c[2, 21:29] == 0)
+    assert np.all(d[:, (0, 1, -1)].sum(1) > 10)
+    assert np.all(d[:, 2:49] <= 0.125 * 3)
+
+
+def test_step_longer_than_period(pulsar):
+    sh, _ = pulsar
+    step = 30 * u.ms
+    fh = bt.Fold(sh, N_PHASE, phase, step, average=False)
+    fr = fh.read(10)
+    c, d = fr['count'], fr['data']
+    assert np.all(c[..., 0].sum(1) == 300)
+    pulse = d[:, (0, 1, -1)].sum(1) / c[:, (0, 1, -1)].sum(1)
+    assert np.all(np.abs(pulse - 10. / 7.5 - 0.125) < 0.5)
+    assert np.allclose(d[:, 2:-1] / c[:, 2:-1], 0.125)
+    fh2 = bt.Fold(sh, N_PHASE, phase, step, start=sh.start_time + step, average=False)
+    fr2 = fh2.read(9)
+    assert close(fr2["data"], fr["data"][1:]) and np.all(fr2["count"] == fr["count"][1:])
+
+
+def test_folding_with_averaging(pulsar):
+    sh, _ = pulsar
+    fh = bt.Fold(sh, N_PHASE, phase, step=26 * u.ms, samples_per_frame=20, average=True)
+    fr = fh.read(10)
+    assert close(fr[:, 2:-1], 0.125)
+
+
+def test_non_integer_sample_rate_ratio(pulsar):
+    sh, _ = pulsar
+    step = 1. / 3.
+    fr = bt.Fold(sh, N_PHASE, phase, step).read()
+    assert close(fr[:, 2:-1], 0.125)
+    fr1 = bt.Fold(sh, N_PHASE, phase, step, start=T0 + step).read()
+    assert close(fr1, fr[1:])
+    fr2 = bt.Fold(sh, N_PHASE, phase, step, start=T0 + 2 * step).read()
+    assert close(fr2, fr[2:])
+
+
+def _expected_fold(data, first, n_phase, ph):
+    times = T0 + (first + np.arange(len(data))) / RATE
+    i_phase = unwrapped_bin(ph(times), n_phase) % n_phase
+    return np.bincount(i_phase, data, minlength=n_phase) / np.bincount(i_phase, minlength=n_phase)
+
+
+def test_read_whole_file(pulsar):
+    sh, data = pulsar
+    fh = bt.Fold(sh, N_PHASE, phase)
+    assert abs(fh.stop_time - sh.stop_time) < 1e-9
+    fr = fh.read(1)
+    assert close(fr[:, 2:-1], 0.125)
+    np.testing.assert_allclose(fr[0, :, 0], _expected_fold(data[:, 0], 0, N_PHASE, phase), rtol=1e-6)
+
+
+def test_read_part(pulsar):
+    sh, data = pulsar
+    start = T0 + 10000 / RATE
+    fh = bt.Fold(sh, N_PHASE, phase, average=False, start=start)
+    assert abs(fh.start_time - start) < 1e-9
+    fr = fh.read(1)
+    assert np.all(fr['count'].sum((0, 1)) == 6000)
+    average = fr['data'][0] / fr['count'][0]
+    assert close(average[2:-1], 0.125)
+    np.testing.assert_allclose(average[:, 0], _expected_fold(data[10000:, 0], 10000, N_PHASE, phase),
+                               rtol=1e-6)
+
+
+# -- TestIntegratePhase / TestPulseStack ----------------------------------------------
+@pytest.mark.parametrize('samples_per_frame', (1, 160))
+@pytest.mark.parametrize('ph', [phase, phase2])
+def test_integrate_phase(pulsar, samples_per_frame, ph):
+    sh, data = pulsar
+    ref = data.reshape(-1, 5, 2).mean(1)
+    fh = bt.Integrate(sh, 1. / 25, ph, samples_per_frame=samples_per_frame)
+    assert fh.start_time == sh.start_time and fh.stop_time == sh.stop_time
+    assert fh.sample_rate == 25 and fh.samples_per_frame == samples_per_frame
+    assert close(fh.read(20), ref[:20])
+    fh.seek(250)
+    assert close(fh.read(75), ref[250:325])
+    assert close(fh.read(), ref[325:])
+
+
+@pytest.mark.parametrize('samples_per_frame', (1, 16))
+def test_pulse_stack(pulsar, samples_per_frame):
+    sh, data = pulsar
+    ref = data.reshape(-1, 25, 5, 2).mean(2)
+    fh = bt.PulseStack(sh, 25, phase, samples_per_frame=samples_per_frame)
+    assert fh.start_time == sh.start_time and fh.stop_time == sh.stop_time
+    assert fh.sample_rate == 1. and fh.samples_per_frame == samples_per_frame
+    fh.seek(5)
+    assert abs(fh.time - (T0 + 5 / F0)) < 1e-9
+    fh.seek(0)
+    assert close(fh.read(2), ref[:2])
+    fh.seek(10)
+    assert close(fh.read(3), ref[10:13])
+    assert close(fh.read(), ref[13:])
+
+
+@pytest.mark.parametrize('samples_per_frame', (1, 16))
+def test_pulse_stack_sliced_input(pulsar, samples_per_frame):
+    sh, data = pulsar
+    ref = data[-360:-110].reshape(-1, 25, 5, 2).mean(2)
+    fh = bt.PulseStack(sh[-360:-10], 25, phase, samples_per_frame=samples_per_frame)
+    assert fh.shape == ref.shape
+    assert close(fh.read(), ref)
+
+
+def test_pulse_stack_offset(pulsar):
+    sh, data = pulsar
+    ref = data[124:-1].reshape(-1, 25, 5, 2).mean(2)
+    fh = bt.PulseStack(sh, 25, phase, start=124)
+    assert abs(fh.start_time - T0 - 124 / RATE) < 1e-9
+    assert abs(fh.stop_time - (sh.stop_time - 1 / RATE)) < 1e-9
+    assert close(fh.read(2), ref[:2])
+    fh.seek(10)
+    assert abs(fh.time - T0 - 124 / RATE - 10 / F0) < 1e-9
+    assert close(fh.read(), ref[10:])
+
+
+@pytest.mark.parametrize('item', [slice(10, 100), slice(-10, None), slice(None, 10), slice(None)])
+def test_pulse_stack_slice(pulsar, item):
+    sh, data = pulsar
+    fh = bt.PulseStack(sh, 25, phase, start=124)
+    sliced = fh[item]
+    start, stop, _ = item.indices(fh.shape[0])
+    expected = T0 + 124 / RATE + start / F0
+    assert abs(sliced.start_time - expected) < 1e-9
+    assert abs(sliced.stop_time - (T0 + 124 / RATE + stop / F0)) < 1e-9
+    sliced.seek(5)
+    assert abs(sliced.time - (sliced.start_time + 5 / F0)) < 1e-9
+    sliced.seek(0)
+    ref = data[124:-1].reshape(-1, 25, 5, 2).mean(2)[item]
+    assert sliced.shape == ref.shape
+    np.testing.assert_allclose(sliced.read(), ref, rtol=1e-6)
+
+
+def test_integrate_stack(pulsar):
+    sh, _ = pulsar
+    fh = bt.PulseStack(sh, 25, phase)
+    data = fh.read(3)
+    ih = bt.Integrate(fh, 3)
+    np.testing.assert_allclose(ih.read(1), data.mean(0, keepdims=True), rtol=1e-6)
+
+
+# -- randomised parity against NumPy --------------------------------------------------
+def numpy_fold(x, edges, n_phase, ph, rate, t0):
+    """float64 fold of x[edges[0]:edges[-1]] with the per-row times of the reference."""
+    n_row = len(edges) - 1
+    out = np.zeros((n_row, n_phase) + x.shape[1:], np.complex128 if x.dtype.kind == 'c' else np.float64)
+    cnt = np.zeros((n_row, n_phase), np.int64)
+    for r in range(n_row):
+        n = np.arange(edges[r], edges[r + 1])
+        t = (t0 + edges[r] / rate) + (n - edges[r]) / rate
+        b = unwrapped_bin(ph(t), n_phase) % n_phase
+        np.add.at(out[r], b, x[n])
+        np.add.at(cnt[r], b, 1)
+    return out, cnt
+
+
+def _stream(rng, n, shape, dtype):
+    x = rng.standard_normal((n,) + shape)
+    if np.dtype(dtype).kind == 'c':
+        x = x + 1j * rng.standard_normal((n,) + shape)
+    return x.astype(dtype)
+
+
+def _spin_phase(f0, f1, t0):
+    def ph(t):
+        dt = t - t0
+        return 0.37 + f0 * dt + 0.5 * f1 * dt * dt
+    return ph
+
+
+@pytest.mark.parametrize('kind', ['float32', 'complex64', 'square', 'power'])
+def test_random_parity(kind):
+    rng = np.random.default_rng(hash(kind) % 2**32)
+    n, rate, n_phase = 50000, 1e5, 37
+    shape = (3,) if kind in ('float32', 'complex64') else (2, 2)
+    dtype = np.float32 if kind == 'float32' else np.complex64
+    x = _stream(rng, n, shape, dtype)
+    ph = _spin_phase(173.3, -3e-2, T0)
+    sh = bt.HostStream(x, T0, rate, samples_per_frame=1000, pin=False,
+                       polarization=np.array(['X', 'Y']) if kind == 'power' else None)
+    if kind == 'square':
+        src, xx = bt.Square(sh), np.abs(x.astype(np.complex128)) ** 2
+    elif kind == 'power':
+        src = bt.Power(sh)
+        X, Y = x[..., 0].astype(np.complex128), x[..., 1].astype(np.complex128)
+        xy = X * Y.conj()
+        xx = np.stack([abs(X) ** 2, abs(Y) ** 2, xy.real, xy.imag], axis=-1)
+    else:
+        src, xx = sh, x.astype(np.complex128 if kind == 'complex64' else np.float64)
+    fh = bt.Fold(src, n_phase, ph, 0.07, average=False)
+    fr = fh.read()
+    edges = fh._get_offsets(np.arange(fh.shape[0] + 1))
+    ref, cnt = numpy_fold(xx, edges, n_phase, ph, rate, T0)
+    np.testing.assert_array_equal(fr['count'].reshape(fr['count'].shape[:2] + (-1,))[..., 0], cnt)
+    np.testing.assert_allclose(fr['data'], ref, rtol=1e-5, atol=1e-5 * np.abs(ref).max())
+    # averaged: sums / counts, NaN where empty
+    avg = bt.Fold(src, n_phase, ph, 0.07).read()
+    with np.errstate(invalid='ignore', divide='ignore'):
+        expect = ref / cnt.reshape(cnt.shape + (1,) * (ref.ndim - 2))
+    np.testing.assert_allclose(avg, expect, rtol=1e-5, atol=1e-5 * np.nanmax(np.abs(expect)))
+
+
+def test_chunks_and_framing_do_not_change_the_result():
+    rng = np.random.default_rng(7)
+    x = _stream(rng, 40000, (4,), np.float32)
+    ph = _spin_phase(91.7, 1e-1, T0)
+    sh = bt.HostStream(x, T0, 1e5, samples_per_frame=500, pin=False)
+    base = bt.Fold(sh, 64, ph, 0.05, average=False).read()
+    for spf in (1, 3, 16):
+        fh = bt.Fold(sh, 64, ph, 0.05, average=False, samples_per_frame=spf)
+        fr = fh.read()
+        np.testing.assert_array_equal(fr['count'], base['count'])
+        np.testing.assert_allclose(fr['data'], base['data'], rtol=1e-6, atol=1e-6)
+    small = bt.Fold(sh, 64, ph, None, average=False)
+    small.fold_budget = 3001 * 16                   # many chunks, edges inside runs
+    one = bt.Fold(sh, 64, ph, None, average=False).read()
+    fr = small.read()
+    np.testing.assert_array_equal(fr['count'], one['count'])
+    np.testing.assert_allclose(fr['data'], one['data'], rtol=1e-5, atol=1e-4)
+
+
+def test_read_device_and_repeatability():
+    rng = np.random.default_rng(3)
+    x = _stream(rng, 30000, (8,), np.complex64)
+    ph = _spin_phase(55.5, 0., T0)
+    sh = bt.HostStream(x.reshape(30000, 4, 2), T0, 1e5, samples_per_frame=1000, pin=False,
+                       polarization=np.array(['X', 'Y']))
+    fh = bt.Fold(bt.Power(sh), 256, ph, 0.1)
+    first = fh.read()
+    fh.invalidate_cache()
+    fh.seek(0)
+    dev = fh.read_device()
+    assert isinstance(dev, hip.DeviceArray) and dev.shape == first.shape
+    second = dev.to_host()
+    np.testing.assert_array_equal(second.view(np.uint32), first.view(np.uint32))
+    fh2 = bt.Fold(bt.Power(sh), 256, ph, 0.1)
+    np.testing.assert_array_equal(fh2.read().view(np.uint32), first.view(np.uint32))
+
+
+def test_long_bins_accuracy():
+    """>= 2^22 samples per bin: float32 sums stay within rel-L2 1e-5 of float64."""
+    n = 1 << 24
+    rng = np.random.default_rng(11)
+    x = (1. + 0.1 * rng.standard_normal((n, 2))).astype(np.float32)
+    ds = bt.DeviceStream(hip.DeviceArray.from_host(x), T0, 1e6)
+    fh = bt.Fold(ds, 4, lambda t: (t - T0) * (1. / 16.777216), average=False)
+    fr = fh.read()
+    cnt = fr['count'][0, :, 0]
+    assert cnt.sum() == n and cnt.min() >= 1 << 22
+    edges = np.concatenate(([0], np.cumsum(cnt)))
+    ref = np.array([x[edges[i]:edges[i + 1]].astype(np.float64).sum(0) for i in range(4)])
+    err = np.linalg.norm(fr['data'][0] - ref) / np.linalg.norm(ref)
+    assert err < 1e-5, err
+
+
+def test_channelized_chain_against_numpy():
+    """Fold(Power(Channelize(Dedisperse(ds)))) against the same chain's spectra folded in NumPy."""
+    rng = np.random.default_rng(5)
+    n, rate = 1 << 16, 1e6
+    x = (rng.standard_normal((n, 2)) + 1j * rng.standard_normal((n, 2))).astype(np.complex64)
+    ds = bt.HostStream(x, T0, rate, samples_per_frame=1 << 14, frequency=400e6, sideband=1,
+                       polarization=np.array(['X', 'Y']), pin=False)
+    ch = bt.Channelize(bt.Dedisperse(ds, 0.5), 64)
+    spectra = ch.read().astype(np.complex128)                        # (m, 64, 2)
+    X, Y = spectra[..., 0], spectra[..., 1]
+    xy = X * Y.conj()
+    power = np.stack([abs(X) ** 2, abs(Y) ** 2, xy.real, xy.imag], axis=-1)
+    ph = _spin_phase(31.25, 0., T0)
+    fh = bt.Fold(bt.Power(ch), 16, ph, average=False)
+    fr = fh.read()
+    edges = fh._get_offsets(np.arange(fh.shape[0] + 1))
+    ref, cnt = numpy_fold(power, edges, 16, ph, ch.sample_rate, ch.start_time)
+    np.testing.assert_array_equal(fr['count'][:, :, 0, 0], cnt)
+    np.testing.assert_allclose(fr['data'], ref, rtol=1e-4, atol=1e-5 * np.abs(ref).max())
+
+
+# -- golden vectors of the real reference ------------------------------------------------
+GOLDEN = os.path.join(ROOT, 'tests', 'golden', 'fold_vectors.npz')
+
+
+def _golden_cases():
+    if not os.path.exists(GOLDEN):
+        return []
+    with np.load(GOLDEN, allow_pickle=False) as g:
+        return sorted({k.split('/')[0] for k in g.files if k.startswith('case')})
+
+
+@pytest.mark.parametrize('case', _golden_cases())
+def test_golden(case):
+    from test_fold_host import golden_task           # (the host test file rebuilds each case)
+    with np.load(GOLDEN, allow_pickle=False) as g:
+        task, expected = golden_task(g, case)
+        got = task.read()
+        if expected.dtype.names:
+            np.testing.assert_array_equal(got['count'], expected['count'])
+            np.testing.assert_allclose(got['data'], expected['data'], rtol=1e-5,
+                                       atol=1e-5 * np.abs(expected['data']).max())
+        else:
+            np.testing.assert_array_equal(np.isnan(got), np.isnan(expected))
+            np.testing.assert_allclose(got, expected, rtol=1e-5, equal_nan=True,
+                                       atol=1e-5 * np.nanmax(np.abs(expected)))
