@@ -21,6 +21,7 @@ from .pfb import (sinc_hamming, PolyphaseFilterBank, PolyphaseFilterBankSamples,
                   InversePolyphaseFilterBank)
 from .functions import Square, Power
 from .integration import Integrate, Fold, PulseStack
+from .conversion import Real2Complex
 from .ingest import RawFrameStream, open_vdif, open_dada
 from . import hip
 from . import hdf5

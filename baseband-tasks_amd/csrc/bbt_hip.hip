@@ -24,10 +24,11 @@
 #include "gen2_host.hpp"
 #include "rtc.hpp"
 #include "fold_kernels.hpp"
+#include "r2c_kernels.hpp"
 
 using namespace bbt;
 
-#define BBT_VERSION 153
+#define BBT_VERSION 154
 
 // ---------------------------------------------------------------------------
 // errors
@@ -3051,6 +3052,218 @@ extern "C" int bbt_fold_runs(const void* in_dev, void* out_dev, int64_t n_in, in
     }
     return 0;
 }
+
+// ---------------------------------------------------------------------------
+// Real2Complex (r2c_kernels.hpp)
+struct bbt_r2c_plan {
+    std::mutex mu;                  // one call at a time: the work buffers belong to the running call
+    int device = 0;
+    int64_t M = 0;
+    int S = 0;
+    bool one_pass = false;
+    bool big = false;               // M = 16384: the four-stage one-workgroup transform (big_kernels.hpp)
+    cf* big_tw = nullptr;           // its table (shared)
+    // one pass: G / M and the transform's stages (run-time specialised kernel, or the general one)
+    cf* resp = nullptr;
+    GenGeo g = {}, gr = {};
+    cf* wn = nullptr;
+    cf* wnr = nullptr;
+    bool rtc = false;
+    G2Plan q, qr;
+    cf* qw = nullptr;
+    cf* qwr = nullptr;
+    hipFunction_t k2 = nullptr;
+    // multi-level: odd rows of four slots -> two-stream blocks, convolved by an overlap-save plan
+    bbt_osm_plan* osm = nullptr;
+    int64_t cap = 0;                // blocks the work buffers may hold
+    int64_t alloc = 0;              // blocks they hold now (allocated by the first call that needs them)
+    float* work_in = nullptr;
+    float* work_out = nullptr;
+    hipEvent_t ev_done = nullptr;   // end of the previous call (on whatever stream it ran)
+    bool ev_done_set = false;
+};
+
+static void r2c_release(bbt_r2c_plan* p) {
+    if (!p) return;
+    int cur = 0;
+    const bool switched = hipGetDevice(&cur) == hipSuccess && cur != p->device && hipSetDevice(p->device) == hipSuccess;
+    if (p->ev_done_set) (void)hipEventSynchronize(p->ev_done);
+    if (p->osm) bbt_osm_plan_destroy(p->osm);
+    if (p->resp) (void)hipFree(p->resp);
+    if (p->work_in) (void)hipFree(p->work_in);
+    if (p->work_out) (void)hipFree(p->work_out);
+    if (p->ev_done) (void)hipEventDestroy(p->ev_done);
+    if (switched) (void)hipSetDevice(cur);
+    delete p;
+}
+
+// G[j] = -i W_2M^j for 0 < j < M, G[0] = 0 (FFT-natural order), times `scale`; in double
+static std::vector<cf> r2c_response(int64_t M, double scale) {
+    std::vector<cf> h((size_t)M);
+    h[0] = make_float2(0.f, 0.f);
+    for (int64_t j = 1; j < M; ++j) {
+        const double a = -M_PI * (double)j / (double)M;
+        h[(size_t)j] = make_float2((float)(sin(a) * scale), (float)(-cos(a) * scale));
+    }
+    return h;
+}
+
+extern "C" {
+
+int bbt_r2c_plan_create(bbt_r2c_plan** plan, int64_t n_out, int n_stream) {
+    return bbt_r2c_plan_create_ex(plan, n_out, n_stream, 0);
+}
+
+int bbt_r2c_plan_create_ex(bbt_r2c_plan** plan, int64_t n_out, int n_stream, int flags) {
+    ARG_TRY(plan, "bbt_r2c_plan_create: null plan");
+    ARG_TRY((flags & ~BBT_R2C_MULTI_LEVEL) == 0, "bbt_r2c_plan_create: unknown flags %d", flags);
+    *plan = nullptr;
+    ARG_TRY(n_stream >= 1, "bbt_r2c_plan_create: n_stream=%d must be at least 1", n_stream);
+    ARG_TRY(n_out >= 2 && is_7smooth(n_out),
+            "bbt_r2c_plan_create: n_out=%lld must be 2^a 3^b 5^c 7^d and at least 2", (long long)n_out);
+    bbt_r2c_plan* p = new bbt_r2c_plan;
+    auto bail = [&](int rc) { r2c_release(p); return rc; };
+    if (hipGetDevice(&p->device) != hipSuccess) return bail(fail("bbt_r2c_plan_create: hipGetDevice failed"));
+    p->M = n_out;
+    p->S = n_stream;
+    const bool multi = flags & BBT_R2C_MULTI_LEVEL;
+    p->big = n_out == 16384 && !multi;
+    p->one_pass = (n_out <= BBT_GEN_MAX_LEN || p->big) && !multi;
+    if (p->big) {
+        if (get_big_table((int)n_out, &p->big_tw)) return bail(1);
+        if (upload(&p->resp, r2c_response(n_out, 1.0 / (double)n_out))) return bail(1);
+    } else if (p->one_pass) {
+        if (!factor_7smooth(n_out, &p->g)) return bail(fail("bbt_r2c_plan_create: cannot factor %lld", (long long)n_out));
+        if (get_gen_table(&p->g, &p->wn) || get_reversed(p->g, &p->gr, &p->wnr)) return bail(1);
+        if (upload(&p->resp, r2c_response(n_out, 1.0 / (double)n_out))) return bail(1);
+        if (rtc_mode()) {
+            bool ok = g2_plan((int)n_out, 1, &p->q, g2_pmax(BBT_G2_KIND_ROW));
+            if (ok) p->qr = g2_reversed(p->q);
+            ok = ok && p->q.threads() <= 1024 && std::max(p->q.lds_elems, p->qr.lds_elems) * 8 <= 96 * 1024;
+            if (!ok) fail("no stage list within a workgroup for %lld", (long long)n_out);
+            if (ok) {
+                const std::string w = p->q.threads() >= 448 ? "4" : "0";
+                const std::string src = "#include \"gen2_kernels.hpp\"\n" + g2_trait_source("GA", p->q) +
+                                        g2_trait_source("GB", p->qr) + "BBT_G2_KERNEL_R2C(k_r2c, GA, GB, " + w + ")\n";
+                ok = !g2_build(src, {"k_r2c"}, &p->k2);
+            }
+            if (ok) ok = !(get_g2_table(p->q, &p->qw) || get_g2_table(p->qr, &p->qwr));
+            if (!ok && rtc_mode() == 2) return bail(1);
+            if (!ok) g2_warn_once("bbt_r2c_plan_create");
+            p->rtc = ok;
+        }
+    } else {
+        // two real streams a, b of a transform are one complex stream of the plan (a + i b)
+        const std::vector<cf> h = r2c_response(n_out, 1.0);
+        if (bbt_osm_plan_create(&p->osm, n_out, 2, 1, h.data(), 0, nullptr)) {
+            const std::string why = g_err;
+            return bail(fail("bbt_r2c_plan_create: no overlap-save plan for n_out=%lld: %s", (long long)n_out,
+                             why.c_str()));
+        }
+        // work buffers of at most 256 MiB each (one block at least)
+        p->cap = std::max<int64_t>(1, (int64_t(256) << 20) / (n_out * 16));
+    }
+    if (hipEventCreateWithFlags(&p->ev_done, hipEventDisableTiming) != hipSuccess)
+        return bail(fail("bbt_r2c_plan_create: hipEventCreateWithFlags failed"));
+    *plan = p;
+    return 0;
+}
+
+int bbt_r2c_plan_destroy(bbt_r2c_plan* p) {
+    r2c_release(p);
+    return 0;
+}
+
+int bbt_r2c_plan_info(const bbt_r2c_plan* p, int* one_pass, int64_t* workspace_bytes) {
+    ARG_TRY(p, "bbt_r2c_plan_info: null plan");
+    if (one_pass) *one_pass = p->one_pass ? 1 : 0;
+    if (workspace_bytes) {
+        int64_t ws = 2 * p->alloc * p->M * 16;
+        if (p->osm) {
+            int64_t w = 0;
+            int chunk, n1, n2;
+            if (bbt_osm_plan_info(p->osm, &w, &chunk, &n1, &n2) == 0) ws += w;
+        }
+        *workspace_bytes = ws;
+    }
+    return 0;
+}
+
+int bbt_r2c_execute(bbt_r2c_plan* p, const void* in_dev, void* out_dev, int64_t n_frames, bbt_stream stream) {
+    ARG_TRY(p && in_dev && out_dev, "bbt_r2c_execute: null argument");
+    ARG_TRY(n_frames >= 0, "bbt_r2c_execute: n_frames=%lld", (long long)n_frames);
+    if (n_frames == 0) return 0;
+    std::lock_guard<std::mutex> lock(p->mu);
+    hipStream_t st = (hipStream_t)stream;
+    const long long M = p->M, S = p->S, n_slot = n_frames * S, n_group = (n_slot + 3) / 4;
+    ARG_TRY(n_group < (1ll << 31), "bbt_r2c_execute: too many frames x streams for one call");
+    {   // (the sink reads the even input rows after other workgroups have written their output)
+        const uintptr_t i0 = (uintptr_t)in_dev, i1 = i0 + (uintptr_t)(n_frames * 2 * M * S * 4);
+        const uintptr_t o0 = (uintptr_t)out_dev, o1 = o0 + (uintptr_t)(n_frames * M * S * 8);
+        ARG_TRY(i1 <= o0 || o1 <= i0, "bbt_r2c_execute: in_dev and out_dev must not overlap");
+    }
+    if (p->ev_done_set) HIP_TRY(hipStreamWaitEvent(st, p->ev_done, 0));
+    const float* in = (const float*)in_dev;
+    float2* out = (float2*)out_dev;
+    if (p->one_pass) {
+        // 16-byte accesses where four slots are neighbouring streams, 8-byte ones for pairs
+        const uintptr_t al = (uintptr_t)in_dev | (uintptr_t)out_dev;
+        const int vec = (S % 4 == 0 && (al & 15) == 0) ? 4 : (S % 2 == 0 && (al & 15) == 0) ? 2 : 1;
+        if (p->big) {
+            constexpr size_t lds = BigGeo<16384>::LDS_ELEMS * sizeof(v2);
+#define BBT_R2C_BIG(V)                                                                                      \
+    do {                                                                                                    \
+        if (ensure_dyn_lds((const void*)k_r2c_big<16384, V>, lds)) return 1;                               \
+        hipLaunchKernelGGL((k_r2c_big<16384, V>), dim3((unsigned)n_group), dim3(16384 / 16), lds, st, in, out, \
+                           (int)S, (long long)n_slot, (const cf*)p->resp, (const cf*)p->big_tw);            \
+    } while (0)
+            if (vec == 4) BBT_R2C_BIG(4);
+            else if (vec == 2) BBT_R2C_BIG(2);
+            else BBT_R2C_BIG(1);
+#undef BBT_R2C_BIG
+            HIP_TRY(hipGetLastError());
+        } else if (p->rtc) {
+            if (g2_launch(p->k2, dim3((unsigned)n_group), dim3(p->q.threads()), st, in, out, (int)S,
+                          (long long)n_slot, vec, (const cf*)p->resp, (const cf*)p->qw, (const cf*)p->qwr))
+                return 1;
+        } else {
+            const size_t lds = (size_t)M * sizeof(f4);
+            if (ensure_dyn_lds((const void*)k_r2c_gen, lds)) return 1;
+            hipLaunchKernelGGL(k_r2c_gen, dim3((unsigned)n_group), dim3(gen_threads((int)M)), lds, st, in, out,
+                               (int)S, (long long)n_slot, vec, (const cf*)p->resp, p->g, p->wn, p->gr, p->wnr);
+            HIP_TRY(hipGetLastError());
+        }
+    } else {
+        const int64_t need = std::min<int64_t>(p->cap, n_group);
+        if (need > p->alloc) {
+            // (a previous call may still use the smaller buffers: hipFree waits for the device)
+            if (p->work_in) HIP_TRY(hipFree(p->work_in));
+            if (p->work_out) HIP_TRY(hipFree(p->work_out));
+            p->work_in = p->work_out = nullptr;
+            p->alloc = 0;
+            HIP_TRY(hipMalloc((void**)&p->work_in, (size_t)(need * M * 16)));
+            HIP_TRY(hipMalloc((void**)&p->work_out, (size_t)(need * M * 16)));
+            p->alloc = need;
+        }
+        for (int64_t g0 = 0; g0 < n_group; g0 += p->alloc) {
+            const int64_t ng = std::min<int64_t>(p->alloc, n_group - g0);
+            const long long total = M * 4 * ng;
+            const dim3 grid((unsigned)std::min<long long>((total + 255) / 256, 1 << 16));
+            hipLaunchKernelGGL(k_r2c_gather, grid, dim3(256), 0, st, in, p->work_in, M, (int)S,
+                               (long long)n_slot, (long long)g0, (long long)ng);
+            HIP_TRY(hipGetLastError());
+            if (bbt_osm_execute_regular(p->osm, p->work_in, p->work_out, ng, 0, 0, M, 0, stream)) return 1;
+            hipLaunchKernelGGL(k_r2c_combine, grid, dim3(256), 0, st, in, (const float*)p->work_out, out,
+                               M, (int)S, (long long)n_slot, (long long)g0, (long long)ng);
+            HIP_TRY(hipGetLastError());
+        }
+    }
+    HIP_TRY(hipEventRecord(p->ev_done, st));
+    p->ev_done_set = true;
+    return 0;
+}
+
+}  // extern "C"
 
 // ---------------------------------------------------------------------------
 // integer sample shifts

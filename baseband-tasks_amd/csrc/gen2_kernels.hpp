@@ -7,6 +7,7 @@
 //   k_g2_col         N = N1 x N2: column transforms over n1 for a tile of G::ct columns
 //   k_g2_row         row k1: four-step twiddle, forward over n2, * H, inverse, conjugate twiddle
 //   k_g2_fft_rows    Channelize.task / Dechannelize.task (reference channelize.py:73-74, 164-165)
+//   k_g2_r2c         Real2Complex.task (reference conversion.py:77-101), M <= 8192 in one workgroup
 //
 // These are the kernels' BODIES (device functions templated on the geometry traits); the
 // __global__ entry points are defined per geometry by the BBT_G2_KERNEL_* macros at the end, in
@@ -122,6 +123,19 @@ __device__ __forceinline__ void g2_fft_rows(v2* lds, const float2* __restrict__ 
     g2_fft_open<G, SIGN>(lds, wn, tid, src, dst);
 }
 
+// Real2Complex, one pass (gen_functors.hpp R2cOddSrc / R2cEvenDst): workgroup w transforms the
+// four real (frame, stream) slots 4w .. 4w + 3 of n_slot = frames x S; resp = G / M (same for all).
+template <class G, class GR>
+__device__ __forceinline__ void g2_r2c(v2* lds, const float* __restrict__ in, float2* __restrict__ out, int S,
+                                       long long n_slot, int vec, const cf* __restrict__ resp,
+                                       const cf* __restrict__ wn, const cf* __restrict__ wnr) {
+    const R2cSlots sl = r2c_slots(in, out, G::n, S, n_slot, blockIdx.x, vec);
+    R2cOddSrc src{sl};
+    GenRespMul mul{resp, resp, true};
+    R2cEvenDst dst{sl};
+    g2_conv_open<G, GR>(lds, wn, wnr, threadIdx.x, src, mul, dst);
+}
+
 }  // namespace bbt
 
 // ---- geometry traits from macros, and the entry points -------------------------------------
@@ -160,4 +174,11 @@ __device__ __forceinline__ void g2_fft_rows(v2* lds, const float2* __restrict__ 
             int S, int cp, long long n_fft, float scale, const bbt::cf* __restrict__ wn) {                 \
         __shared__ bbt::v2 lds[bbt::G2Info<G>::LDS];                                                        \
         bbt::g2_fft_rows<G, SIGN>(lds, in, out, S, cp, n_fft, scale, wn);                                   \
+    }
+#define BBT_G2_KERNEL_R2C(NAME, G, GR, W)                                                                  \
+    extern "C" __global__ BBT_G2_BOUNDS(G, W) void NAME(const float* __restrict__ in, float2* __restrict__ out, \
+            int S, long long n_slot, int vec, const bbt::cf* __restrict__ resp,                            \
+            const bbt::cf* __restrict__ wn, const bbt::cf* __restrict__ wnr) {                              \
+        __shared__ bbt::v2 lds[BBT_G2_LDS2(G, GR)];                                                         \
+        bbt::g2_r2c<G, GR>(lds, in, out, S, n_slot, vec, resp, wn, wnr);                                    \
     }

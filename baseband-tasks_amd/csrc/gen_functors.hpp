@@ -193,4 +193,90 @@ struct GenScaledDst {
     }
 };
 
+// ---- Real2Complex (reference conversion.py:77-101): the source and sink of the one-pass route ----
+// A frame of 2M real samples x of one stream gives M complex ones,
+//   out[m] = (-1)^m (x[2m] + i (g (*) x_o)[m]),  x_o[m] = x[2m + 1],  g (*): circular convolution of
+//   length M with the real g = ifft(G), G[j] = -i W_2M^j (j > 0), G[0] = 0  (include/bbt_hip.h).
+// Four real (frame, stream) slots go through one transform of a stream pair: slots 0, 1 are the
+// real and imaginary part of stream A, slots 2, 3 those of stream B.  Slot k reads its frame's rows
+// at p[k] + row * S floats (nullptr: no slot, zeros) and writes complex64 rows at q[k] + m * S.
+//   vec 4: the four slots are neighbouring streams of one frame (16-byte loads and stores);
+//   vec 2: slots 0, 1 and 2, 3 are neighbouring pairs (8-byte loads);  vec 1: one float at a time.
+struct R2cSlots {
+    const float* p[4];
+    float2* q[4];
+    long long S;
+    int vec;
+};
+__device__ __forceinline__ R2cSlots r2c_slots(const float* in, float2* out, long long M, int S, long long n_slot,
+                                              long long group, int vec) {
+    R2cSlots sl;
+    sl.S = S;
+    sl.vec = vec;
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+        const long long t = group * 4 + k, f = t / S, s = t - f * S;
+        const bool live = t < n_slot;
+        sl.p[k] = live ? in + (f * 2 * M) * S + s : nullptr;
+        sl.q[k] = live ? out + (f * M) * S + s : nullptr;
+    }
+    return sl;
+}
+// the odd rows x_o of the four slots: stream A = x_o^0 + i x_o^1, stream B = x_o^2 + i x_o^3
+struct R2cOddSrc {
+    R2cSlots sl;
+    template <int R>
+    __device__ __forceinline__ void load(int j, int m, c2 (&v)[R]) const {
+#pragma unroll
+        for (int r = 0; r < R; ++r) {
+            const long long off = (2ll * (j + r * m) + 1) * sl.S;
+            if (sl.vec == 4) {
+                const float4 x = *reinterpret_cast<const float4*>(sl.p[0] + off);
+                v[r] = c2{v2{x.x, x.z}, v2{x.y, x.w}};
+            } else if (sl.vec == 2) {
+                const float2 a = *reinterpret_cast<const float2*>(sl.p[0] + off);
+                const float2 b = sl.p[2] ? *reinterpret_cast<const float2*>(sl.p[2] + off) : make_float2(0.f, 0.f);
+                v[r] = c2{v2{a.x, b.x}, v2{a.y, b.y}};
+            } else {
+                float x[4];
+#pragma unroll
+                for (int k = 0; k < 4; ++k) x[k] = sl.p[k] ? sl.p[k][off] : 0.f;
+                v[r] = c2{v2{x[0], x[2]}, v2{x[1], x[3]}};
+            }
+        }
+    }
+};
+// the even rows and the result: out[m] = (-1)^m (x[2m] + i y[m]), y of slot k from the transform
+// (re A, im A, re B, im B).  The real part is the input sample itself, sign flipped or not.
+struct R2cEvenDst {
+    R2cSlots sl;
+    template <int R>
+    __device__ __forceinline__ void store(int j, int m, c2 (&v)[R]) const {
+#pragma unroll
+        for (int r = 0; r < R; ++r) {
+            const int i = j + r * m;
+            const float sg = (i & 1) ? -1.f : 1.f;
+            const long long ie = 2ll * i * sl.S, io = (long long)i * sl.S;
+            const float y[4] = {v[r].re.x, v[r].im.x, v[r].re.y, v[r].im.y};
+            if (sl.vec == 4) {
+                const float4 x = *reinterpret_cast<const float4*>(sl.p[0] + ie);
+                float4* o = reinterpret_cast<float4*>(sl.q[0] + io);
+                o[0] = make_float4(sg * x.x, sg * y[0], sg * x.y, sg * y[1]);
+                o[1] = make_float4(sg * x.z, sg * y[2], sg * x.w, sg * y[3]);
+            } else if (sl.vec == 2) {
+                const float2 a = *reinterpret_cast<const float2*>(sl.p[0] + ie);
+                *reinterpret_cast<float4*>(sl.q[0] + io) = make_float4(sg * a.x, sg * y[0], sg * a.y, sg * y[1]);
+                if (sl.p[2]) {
+                    const float2 b = *reinterpret_cast<const float2*>(sl.p[2] + ie);
+                    *reinterpret_cast<float4*>(sl.q[2] + io) = make_float4(sg * b.x, sg * y[2], sg * b.y, sg * y[3]);
+                }
+            } else {
+#pragma unroll
+                for (int k = 0; k < 4; ++k)
+                    if (sl.p[k]) sl.q[k][io] = make_float2(sg * sl.p[k][ie], sg * y[k]);
+            }
+        }
+    }
+};
+
 }  // namespace bbt

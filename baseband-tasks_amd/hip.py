@@ -101,6 +101,11 @@ SIGNATURES = {
     'bbt_fir_plan_create': [_pvp, _int, _int, _vp],
     'bbt_fir_plan_destroy': [_vp],
     'bbt_fir_execute': [_vp, _vp, _vp, _i64, _vp],
+    'bbt_r2c_plan_create': [_pvp, _i64, _int],
+    'bbt_r2c_plan_create_ex': [_pvp, _i64, _int, _int],
+    'bbt_r2c_plan_destroy': [_vp],
+    'bbt_r2c_plan_info': [_vp, C.POINTER(_int), _pi64],
+    'bbt_r2c_execute': [_vp, _vp, _vp, _i64, _vp],
     'bbt_real_op': [_vp, _vp, _int, _i64, _int, _int, _vp],
     'bbt_chirp': [_vp, _i64, _int, C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_double),
                   C.c_double, C.c_double, C.c_double, _vp],
@@ -115,7 +120,7 @@ SIGNATURES = {
 }
 
 #: oldest libbbt_hip.so whose entry points and argument meanings this binding assumes
-MIN_LIB_VERSION = 153
+MIN_LIB_VERSION = 154
 
 _lib = None
 _lock = threading.Lock()
@@ -995,6 +1000,27 @@ class ChanPlan(_Plan):
 
     def execute(self, in_dev, out_dev, n_spectra):
         check(lib().bbt_chan_execute(self._h, in_dev.ptr_to_read(), out_dev.ptr, int(n_spectra), _stream))
+
+
+class R2CPlan(_Plan):
+    """Real2Complex of frames of 2 n_out float32 samples of n_stream streams into n_out complex64
+    samples each (bbt_r2c_*)."""
+    _destroy = 'bbt_r2c_plan_destroy'
+
+    def __init__(self, n_out, n_stream, multi_level=False):
+        """multi_level: the three-step route for any length (BBT_R2C_MULTI_LEVEL)."""
+        super().__init__()
+        self.n_out, self.n_stream = int(n_out), int(n_stream)
+        check(lib().bbt_r2c_plan_create_ex(C.byref(self._h), self.n_out, self.n_stream, 1 if multi_level else 0))
+
+    def info(self):
+        one, ws = _int(), _i64()
+        check(lib().bbt_r2c_plan_info(self._h, C.byref(one), C.byref(ws)))
+        return dict(one_pass=bool(one.value), workspace_bytes=ws.value)
+
+    def execute(self, in_dev, out_dev, n_frames):
+        """in_dev: (n_frames * 2 n_out, n_stream) float32 -> out_dev: (n_frames * n_out, n_stream) complex64."""
+        check(lib().bbt_r2c_execute(self._h, in_dev.ptr_to_read(), out_dev.ptr, int(n_frames), _stream))
 
 
 class PfbPlan(_Plan):

@@ -13,6 +13,7 @@
  *               channelize.py:73-74, 164-165  (fft over groups of n samples)
  *   bbt_pfb_*   PolyphaseFilterBankSamples.ppf + Channelize.task
  *               pfb.py:91-100 (definition), 145-154 (Fourier form)
+ *   bbt_r2c_*   Real2Complex.task             conversion.py:77-101
  *
  * Conventions
  *   - every function returns 0 on success, non-zero on failure;
@@ -44,6 +45,7 @@ typedef struct bbt_chan_plan bbt_chan_plan;
 typedef struct bbt_pfb_plan bbt_pfb_plan;
 typedef struct bbt_shift_plan bbt_shift_plan;
 typedef struct bbt_fir_plan bbt_fir_plan;
+typedef struct bbt_r2c_plan bbt_r2c_plan;
 typedef struct bbt_comm bbt_comm;
 
 /* ---- library / device ------------------------------------------------- */
@@ -353,6 +355,38 @@ int bbt_fold_runs(const void* in_dev, void* out_dev, int64_t n_in, int64_t n_ele
                   const int64_t* slot_ptr_dev, const int64_t* run_begin_dev,
                   const int64_t* run_end_dev, int64_t n_slot, const float* scale_dev, int accumulate,
                   void* work_dev, int64_t work_floats, bbt_stream stream);
+
+/* ---- real streams to complex baseband: Real2Complex ---------------------------
+ * Replaces Real2Complex.task (conversion.py:77-101): every frame of 2 M real samples of each of
+ * the S streams (fft, one-sided spectrum, ifft, times exp(-i pi n / 2), every second sample) gives
+ * M complex ones.  Computed as the exact identity, with x_e[m] = x[2m], x_o[m] = x[2m + 1]:
+ *   out[m] = (-1)^m (x_e[m] + i (g (*) x_o)[m]),  fft(g) = G: G[0] = 0, G[j] = -i exp(-i pi j / M)
+ * ((*): circular convolution of length M; g is real).  The real part is the input sample itself;
+ * four real (frame, stream) slots -- frame-major, stream innermost -- share one complex transform
+ * pair of M points forward and back.
+ *   n_out      M: any 2^a 3^b 5^c 7^d with 2 <= M <= 8192, and 16384, runs in one pass (one
+ *              workgroup per four slots; each input and output byte moved once); longer M -- what
+ *              bbt_osm_plan_create accepts for n_fft, powers of two up to 2^24 and two factors
+ *              <= 8192 -- gather the odd rows into a work buffer, convolve them with an
+ *              overlap-save plan (response G, hop M) and combine (three steps).  Other lengths
+ *              are refused.
+ *   n_stream   S >= 1, any (one stream: four consecutive frames share a transform)
+ * in_dev: (n_frames * 2 M, S) float32; out_dev: (n_frames * M, S) complex64 -- the same number
+ * of bytes, but they must not overlap (the even input rows are read after other workgroups have
+ * written their output; overlapping ranges are refused).  Asynchronous on
+ * `stream`.  A plan runs one execute call at a time (a mutex on the host; on the device a call
+ * first waits for the end of the previous one, which may have run on another stream); calls on
+ * different plans are independent.  one_pass: 1 for the one-pass route; workspace_bytes: device
+ * memory the plan holds for its work buffers (allocated by the first call that needs them). */
+int bbt_r2c_plan_create(bbt_r2c_plan** plan, int64_t n_out, int n_stream);
+/* The same with flags: BBT_R2C_MULTI_LEVEL takes the three-step route for any length (tests run
+ * both routes on one length); bbt_r2c_plan_create is flags = 0. */
+#define BBT_R2C_MULTI_LEVEL 1
+int bbt_r2c_plan_create_ex(bbt_r2c_plan** plan, int64_t n_out, int n_stream, int flags);
+int bbt_r2c_plan_destroy(bbt_r2c_plan* plan);
+int bbt_r2c_plan_info(const bbt_r2c_plan* plan, int* one_pass, int64_t* workspace_bytes);
+int bbt_r2c_execute(bbt_r2c_plan* plan, const void* in_dev, void* out_dev, int64_t n_frames,
+                    bbt_stream stream);
 
 /* ---- integer sample shifts -------------------------------------------------
  * Replaces ShiftSamples.task (sampling.py:424-425, data[self._indices]), the
