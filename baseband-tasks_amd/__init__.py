@@ -22,6 +22,9 @@ from .pfb import (sinc_hamming, PolyphaseFilterBank, PolyphaseFilterBankSamples,
 from .functions import Square, Power
 from .integration import Integrate, Fold, PulseStack
 from .conversion import Real2Complex
+from .shaping import (ChangeSampleShapeBase, ChangeSampleShape, Reshape, Transpose, ReshapeAndTranspose,
+                      GetItem, GetSlice)
+from .combining import CombineStreamsBase, CombineStreams, Concatenate, Stack
 from .ingest import RawFrameStream, open_vdif, open_dada
 from . import hip
 from . import hdf5

@@ -325,10 +325,20 @@ class Base:
     def __getitem__(self, item):
         if isinstance(item, tuple) and len(item) == 1:
             item = item[0]
+        if isinstance(item, tuple):
+            # a time slice with a sample item (reference base.py:475-478)
+            if not isinstance(item[0], slice):
+                raise NotImplementedError(
+                    "only slices along the time axis are supported here "
+                    "(use shaping.GetItem to index the samples alone).")
+            if item[0].indices(self.shape[0])[2] != 1:
+                raise NotImplementedError("strided time slices are outside the accelerated path.")
+            from .shaping import GetSlice
+            return GetSlice(self, item)
         if not isinstance(item, slice):
             raise NotImplementedError(
                 "only slices along the time axis are supported here "
-                "(shaping.GetItem/GetSlice are outside the accelerated path).")
+                "(use shaping.GetItem to index the samples alone).")
         return _TimeSlice(self, item)
 
     def __array__(self, dtype=None, copy=None):

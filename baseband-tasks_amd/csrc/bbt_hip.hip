@@ -25,10 +25,11 @@
 #include "rtc.hpp"
 #include "fold_kernels.hpp"
 #include "r2c_kernels.hpp"
+#include "gather_kernels.hpp"
 
 using namespace bbt;
 
-#define BBT_VERSION 154
+#define BBT_VERSION 155
 
 // ---------------------------------------------------------------------------
 // errors
@@ -3260,6 +3261,306 @@ int bbt_r2c_execute(bbt_r2c_plan* p, const void* in_dev, void* out_dev, int64_t 
     }
     HIP_TRY(hipEventRecord(p->ev_done, st));
     p->ev_done_set = true;
+    return 0;
+}
+
+}  // extern "C"
+
+// ---------------------------------------------------------------------------
+// shaping and combining: index maps (gather_kernels.hpp)
+struct bbt_gather_plan {
+    int device = 0;
+    int n_src = 0, eb = 0, route = 0;
+    int64_t R = 0;                          // output row, elements
+    std::vector<int64_t> src_row;           // source rows, elements
+    std::vector<int> used;                  // used sources, ascending (kernel slot u -> source)
+    int64_t n_runs = 0;
+    // element map (direct route, and the fall-back of the other two): (slot, byte offset)
+    int2* tab_elem = nullptr;
+    long long* stride_dev = nullptr;        // source rows in bytes, per slot
+    // run copy: the same per 16-byte unit
+    int2* tab16 = nullptr;
+    // tile
+    int T = 0, lds_bytes = 0;
+    std::vector<GatherTileSrc> tile_src;    // per slot
+    std::vector<int> tile_lo;               // start of the staged stretch in the source row, bytes
+    std::vector<char> tile_vec;             // stretch is whole 16-byte pieces
+    GatherTileSrc* tile_src_dev = nullptr;
+    int2* tab_tile = nullptr;
+    // host copies, uploaded by the first execute call (a plan can be made, and its route asked for,
+    // without a device)
+    std::mutex mu;
+    bool uploaded = false;
+    std::vector<long long> h_stride;
+    std::vector<int2> h_elem, h_16, h_tile;
+};
+
+static int gather_upload_all(bbt_gather_plan* p);
+
+static void gather_release(bbt_gather_plan* p) {
+    if (!p) return;
+    int cur = 0;
+    const bool switched = hipGetDevice(&cur) == hipSuccess && cur != p->device && hipSetDevice(p->device) == hipSuccess;
+    if (p->tab_elem) (void)hipFree(p->tab_elem);
+    if (p->stride_dev) (void)hipFree(p->stride_dev);
+    if (p->tab16) (void)hipFree(p->tab16);
+    if (p->tile_src_dev) (void)hipFree(p->tile_src_dev);
+    if (p->tab_tile) (void)hipFree(p->tab_tile);
+    if (switched) (void)hipSetDevice(cur);
+    delete p;
+}
+
+template <typename V> static int gather_upload(V** dst, const std::vector<V>& h) {
+    HIP_TRY(hipMalloc((void**)dst, std::max<size_t>(h.size(), 1) * sizeof(V)));
+    if (!h.empty()) HIP_TRY(hipMemcpy(*dst, h.data(), h.size() * sizeof(V), hipMemcpyHostToDevice));
+    return 0;
+}
+
+// LDS layout of a tile of T samples (gather_kernels.hpp); returns the bytes it takes
+static int gather_tile_layout(int eb, int T, const std::vector<int>& len, std::vector<GatherTileSrc>* out) {
+    const int G = eb < 4 ? 4 : eb, rowsh = eb >= 8 ? 8 : 7, bank_row = 1 << rowsh;
+    int np = 1;
+    while (np < (int)len.size() && np < bank_row / G) np *= 2;
+    int64_t end = 0;
+    for (size_t u = 0; u < len.size(); ++u) {
+        GatherTileSrc s = {};
+        s.len = len[u];
+        const int padded = len[u] + (len[u] >> rowsh) * G;
+        s.pitch = (padded + G - 1) / G * G;
+        const int64_t base = (end + bank_row - 1) / bank_row * bank_row + (int64_t)(u % np) * (bank_row / np);
+        end = base + (int64_t)T * s.pitch;
+        if (end > (1 << 30)) return 1 << 30;
+        s.lds_base = (int)base;
+        if (out) out->push_back(s);
+    }
+    return (int)end;
+}
+
+extern "C" {
+
+int bbt_gather_plan_create(bbt_gather_plan** plan, int n_src, const int64_t* src_row_elems, int64_t out_row_elems,
+                           const int32_t* map_src, const int64_t* map_elem, int elem_bytes) {
+    return bbt_gather_plan_create_ex(plan, n_src, src_row_elems, out_row_elems, map_src, map_elem, elem_bytes,
+                                     BBT_GATHER_AUTO);
+}
+
+int bbt_gather_plan_create_ex(bbt_gather_plan** plan, int n_src, const int64_t* src_row_elems, int64_t out_row_elems,
+                              const int32_t* map_src, const int64_t* map_elem, int elem_bytes, int route) {
+    ARG_TRY(plan, "bbt_gather_plan_create: null plan");
+    *plan = nullptr;
+    ARG_TRY(src_row_elems && map_src && map_elem, "bbt_gather_plan_create: null argument");
+    ARG_TRY(n_src >= 1 && n_src <= BBT_GATHER_MAX_SRC, "bbt_gather_plan_create: n_src=%d must be 1 to %d", n_src,
+            BBT_GATHER_MAX_SRC);
+    ARG_TRY(elem_bytes == 1 || elem_bytes == 2 || elem_bytes == 4 || elem_bytes == 8 || elem_bytes == 16,
+            "bbt_gather_plan_create: elem_bytes=%d must be 1, 2, 4, 8 or 16", elem_bytes);
+    ARG_TRY(route >= BBT_GATHER_AUTO && route <= BBT_GATHER_DIRECT, "bbt_gather_plan_create: unknown route %d", route);
+    const int eb = elem_bytes;
+    const int64_t R = out_row_elems;
+    ARG_TRY(R >= 1 && R * eb < (int64_t(1) << 31), "bbt_gather_plan_create: out_row_elems=%lld must be at least 1 "
+            "and the row below 2 GiB", (long long)R);
+    for (int s = 0; s < n_src; ++s)
+        ARG_TRY(src_row_elems[s] >= 1 && src_row_elems[s] * eb < (int64_t(1) << 31),
+                "bbt_gather_plan_create: src_row_elems[%d]=%lld must be at least 1 and the row below 2 GiB", s,
+                (long long)src_row_elems[s]);
+    std::vector<int> slot((size_t)n_src, -1);
+    for (int64_t j = 0; j < R; ++j) {
+        ARG_TRY(map_src[j] >= 0 && map_src[j] < n_src, "bbt_gather_plan_create: map_src[%lld]=%d out of range (%d sources)",
+                (long long)j, (int)map_src[j], n_src);
+        ARG_TRY(map_elem[j] >= 0 && map_elem[j] < src_row_elems[map_src[j]],
+                "bbt_gather_plan_create: map_elem[%lld]=%lld out of range (source %d has rows of %lld)", (long long)j,
+                (long long)map_elem[j], (int)map_src[j], (long long)src_row_elems[map_src[j]]);
+        slot[(size_t)map_src[j]] = 0;
+    }
+    bbt_gather_plan* p = new bbt_gather_plan;
+    auto bail = [&](int rc) { gather_release(p); return rc; };
+    p->n_src = n_src;
+    p->eb = eb;
+    p->R = R;
+    p->src_row.assign(src_row_elems, src_row_elems + n_src);
+    for (int s = 0; s < n_src; ++s)
+        if (slot[(size_t)s] == 0) {
+            slot[(size_t)s] = (int)p->used.size();
+            p->used.push_back(s);
+        }
+    const size_t nu = p->used.size();
+    // runs: maximal stretches where source and element advance together
+    struct Run { int64_t out, elem, len; int u; };
+    std::vector<Run> runs;
+    std::vector<int64_t> lo(nu, INT64_MAX), hi(nu, 0);
+    for (int64_t j = 0; j < R; ++j) {
+        const int u = slot[(size_t)map_src[j]];
+        if (!runs.empty() && runs.back().u == u && runs.back().elem + runs.back().len == map_elem[j]) ++runs.back().len;
+        else runs.push_back({j, map_elem[j], 1, u});
+        lo[(size_t)u] = std::min(lo[(size_t)u], map_elem[j]);
+        hi[(size_t)u] = std::max(hi[(size_t)u], map_elem[j] + 1);
+    }
+    p->n_runs = (int64_t)runs.size();
+    bool run_ok = (R * eb) % 16 == 0;
+    for (size_t u = 0; u < nu && run_ok; ++u) run_ok = (p->src_row[(size_t)p->used[u]] * eb) % 16 == 0;
+    for (size_t r = 0; r < runs.size() && run_ok; ++r)
+        run_ok = (runs[r].out * eb) % 16 == 0 && (runs[r].elem * eb) % 16 == 0 && (runs[r].len * eb) % 16 == 0;
+    // tile: the stretch of each source row the map uses, widened to whole 16-byte pieces where the row allows
+    std::vector<int> len(nu);
+    int64_t staged = 0;
+    p->tile_lo.resize(nu);
+    p->tile_vec.resize(nu);
+    for (size_t u = 0; u < nu; ++u) {
+        int64_t b0 = lo[u] * eb, b1 = hi[u] * eb;
+        const bool vec = (p->src_row[(size_t)p->used[u]] * eb) % 16 == 0;
+        if (vec) {
+            b0 = b0 / 16 * 16;
+            b1 = (b1 + 15) / 16 * 16;
+        }
+        p->tile_lo[u] = (int)b0;
+        p->tile_vec[u] = vec ? 1 : 0;
+        len[u] = (int)(b1 - b0);
+        staged += b1 - b0;
+    }
+    // T: a multiple of the fewest samples whose output is whole 16-byte chunks (m), as many as fit
+    // half the budget if those are eight at least (more workgroups per CU), else the whole budget
+    int m = 1;
+    while ((m * R * eb) % 16) m *= 2;
+    int T = 0;
+    for (int budget = BBT_GATHER_LDS_BYTES / 2; budget <= BBT_GATHER_LDS_BYTES && !T; budget *= 2)
+        for (int t = 512 / m * m; t >= m; t -= m)
+            if (gather_tile_layout(eb, t, len, nullptr) <= budget) {
+                if (t >= 8 || budget == BBT_GATHER_LDS_BYTES) T = t;
+                break;
+            }
+    const bool tile_ok = T >= 1;
+    if (route == BBT_GATHER_RUN_COPY && !run_ok)
+        return bail(fail("bbt_gather_plan_create: the run-copy route needs runs, rows and offsets of whole 16-byte units"));
+    if (route == BBT_GATHER_TILE && !tile_ok)
+        return bail(fail("bbt_gather_plan_create: the rows used (%lld bytes per sample) leave no tile in %d "
+                         "bytes of LDS", (long long)staged, BBT_GATHER_LDS_BYTES));
+    if (route == BBT_GATHER_AUTO)
+        // (a tile stages whole stretches: not worth it where the map uses less than a quarter of them)
+        route = run_ok ? BBT_GATHER_RUN_COPY : (tile_ok && staged <= 4 * R * eb) ? BBT_GATHER_TILE : BBT_GATHER_DIRECT;
+    p->route = route;
+    std::vector<long long> stride(nu);
+    for (size_t u = 0; u < nu; ++u) stride[u] = (long long)(p->src_row[(size_t)p->used[u]] * eb);
+    std::vector<int2> te((size_t)R);
+    for (int64_t j = 0; j < R; ++j) te[(size_t)j] = make_int2(slot[(size_t)map_src[j]], (int)(map_elem[j] * eb));
+    p->h_stride = stride;
+    p->h_elem = te;
+    if (route == BBT_GATHER_RUN_COPY) {
+        std::vector<int2> t16((size_t)(R * eb / 16));
+        for (size_t q = 0; q < t16.size(); ++q) t16[q] = te[q * (size_t)(16 / eb)];
+        p->h_16 = t16;
+    } else if (route == BBT_GATHER_TILE) {
+        p->T = T;
+        p->lds_bytes = gather_tile_layout(eb, T, len, &p->tile_src);
+        const int G = eb < 4 ? 4 : eb, rowsh = eb >= 8 ? 8 : 7;
+        for (size_t u = 0; u < nu; ++u) p->tile_src[u].stride = stride[u];
+        std::vector<int2> tt((size_t)R);
+        for (int64_t j = 0; j < R; ++j) {
+            const int u = te[(size_t)j].x, r = te[(size_t)j].y - p->tile_lo[(size_t)u];
+            tt[(size_t)j] = make_int2(p->tile_src[(size_t)u].lds_base + r + (r >> rowsh) * G, p->tile_src[(size_t)u].pitch);
+        }
+        p->h_tile = tt;
+    }
+    *plan = p;
+    return 0;
+}
+
+}  // extern "C"
+
+static int gather_upload_all(bbt_gather_plan* p) {
+    std::lock_guard<std::mutex> lock(p->mu);
+    if (p->uploaded) return 0;
+    HIP_TRY(hipGetDevice(&p->device));
+    if (gather_upload(&p->stride_dev, p->h_stride) || gather_upload(&p->tab_elem, p->h_elem)) return 1;
+    if (p->route == BBT_GATHER_RUN_COPY && gather_upload(&p->tab16, p->h_16)) return 1;
+    if (p->route == BBT_GATHER_TILE &&
+        (gather_upload(&p->tile_src_dev, p->tile_src) || gather_upload(&p->tab_tile, p->h_tile)))
+        return 1;
+    p->uploaded = true;
+    return 0;
+}
+
+extern "C" {
+
+int bbt_gather_plan_destroy(bbt_gather_plan* p) {
+    gather_release(p);
+    return 0;
+}
+
+int bbt_gather_plan_info(const bbt_gather_plan* p, int* route, int64_t* n_runs, int* tile_samples, int* lds_bytes) {
+    ARG_TRY(p, "bbt_gather_plan_info: null plan");
+    if (route) *route = p->route;
+    if (n_runs) *n_runs = p->n_runs;
+    if (tile_samples) *tile_samples = p->T;
+    if (lds_bytes) *lds_bytes = p->lds_bytes;
+    return 0;
+}
+
+int bbt_gather_execute(bbt_gather_plan* p, const void* const* src_dev, const int64_t* src_first_sample, void* out_dev,
+                       int64_t n_samples, bbt_stream stream) {
+    ARG_TRY(p && src_dev && out_dev, "bbt_gather_execute: null argument");
+    ARG_TRY(n_samples >= 0, "bbt_gather_execute: n_samples=%lld", (long long)n_samples);
+    if (n_samples == 0) return 0;
+    hipStream_t st = (hipStream_t)stream;
+    const int eb = p->eb;
+    const size_t nu = p->used.size();
+    const uintptr_t o0 = (uintptr_t)out_dev, o1 = o0 + (uintptr_t)(n_samples * p->R * eb);
+    ARG_TRY(o0 % (uintptr_t)eb == 0, "bbt_gather_execute: out_dev is not aligned to the element size %d", eb);
+    GatherPtrs ptrs = {};
+    bool al16 = o0 % 16 == 0;
+    for (size_t u = 0; u < nu; ++u) {
+        const int s = p->used[u];
+        ARG_TRY(src_dev[s], "bbt_gather_execute: null source %d", s);
+        const int64_t first = src_first_sample ? src_first_sample[s] : 0;
+        ARG_TRY(first >= 0, "bbt_gather_execute: src_first_sample[%d]=%lld is negative", s, (long long)first);
+        const int64_t row = p->src_row[(size_t)s] * eb;
+        const uintptr_t i0 = (uintptr_t)src_dev[s] + (uintptr_t)(first * row), i1 = i0 + (uintptr_t)(n_samples * row);
+        ARG_TRY(i0 % (uintptr_t)eb == 0, "bbt_gather_execute: source %d is not aligned to the element size %d", s, eb);
+        ARG_TRY(i1 <= o0 || o1 <= i0, "bbt_gather_execute: out_dev overlaps source %d", s);
+        ptrs.p[u] = (const char*)i0;
+        al16 = al16 && i0 % 16 == 0;
+    }
+    if (gather_upload_all(p)) return 1;
+    const long long total_rows = n_samples;
+    auto grid_for = [](long long units) {
+        return dim3((unsigned)std::max<long long>(1, std::min<long long>((units + BBT_GATHER_THREADS - 1) / BBT_GATHER_THREADS, 8192)));
+    };
+#define BBT_GATHER_MAP(E, TAB, ROW)                                                                              \
+    hipLaunchKernelGGL((k_gather_map<E>), grid_for(total_rows * (long long)(ROW)), dim3(BBT_GATHER_THREADS), 0, st, \
+                       ptrs, (const long long*)p->stride_dev, (int)nu, (const int2*)(TAB), (int)(ROW), (E*)out_dev, \
+                       total_rows)
+    if (p->route == BBT_GATHER_RUN_COPY && al16) {
+        BBT_GATHER_MAP(GatherB16, p->tab16, p->R * eb / 16);
+    } else if (p->route == BBT_GATHER_TILE) {
+        unsigned long long vec_mask = 0;
+        for (size_t u = 0; u < nu; ++u) {
+            ptrs.p[u] += p->tile_lo[u];
+            if (p->tile_vec[u] && (uintptr_t)ptrs.p[u] % 16 == 0) vec_mask |= 1ull << u;
+        }
+        const long long n_tiles = (n_samples + p->T - 1) / p->T;
+        const dim3 grid((unsigned)std::min<long long>(n_tiles, 1 << 16));
+        const int vec_out = (o0 % 16 == 0 && ((long long)p->T * p->R * eb) % 16 == 0) ? 1 : 0;
+#define BBT_GATHER_TILE_K(E)                                                                                       \
+    hipLaunchKernelGGL((k_gather_tile<E>), grid, dim3(BBT_GATHER_THREADS), (size_t)p->lds_bytes, st, ptrs, vec_mask, \
+                       (const GatherTileSrc*)p->tile_src_dev, (int)nu, (const int2*)p->tab_tile, (int)p->R,         \
+                       (E*)out_dev, total_rows, p->T, vec_out)
+        switch (eb) {
+            case 1: BBT_GATHER_TILE_K(unsigned char); break;
+            case 2: BBT_GATHER_TILE_K(unsigned short); break;
+            case 4: BBT_GATHER_TILE_K(unsigned); break;
+            case 8: BBT_GATHER_TILE_K(GatherB8); break;
+            default: BBT_GATHER_TILE_K(GatherB16); break;
+        }
+#undef BBT_GATHER_TILE_K
+    } else {
+        switch (eb) {
+            case 1: BBT_GATHER_MAP(unsigned char, p->tab_elem, p->R); break;
+            case 2: BBT_GATHER_MAP(unsigned short, p->tab_elem, p->R); break;
+            case 4: BBT_GATHER_MAP(unsigned, p->tab_elem, p->R); break;
+            case 8: BBT_GATHER_MAP(GatherB8, p->tab_elem, p->R); break;
+            default: BBT_GATHER_MAP(GatherB16, p->tab_elem, p->R); break;
+        }
+    }
+#undef BBT_GATHER_MAP
+    HIP_TRY(hipGetLastError());
     return 0;
 }
 

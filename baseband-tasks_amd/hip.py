@@ -106,6 +106,11 @@ SIGNATURES = {
     'bbt_r2c_plan_destroy': [_vp],
     'bbt_r2c_plan_info': [_vp, C.POINTER(_int), _pi64],
     'bbt_r2c_execute': [_vp, _vp, _vp, _i64, _vp],
+    'bbt_gather_plan_create': [_pvp, _int, _pi64, _i64, C.POINTER(C.c_int32), _pi64, _int],
+    'bbt_gather_plan_create_ex': [_pvp, _int, _pi64, _i64, C.POINTER(C.c_int32), _pi64, _int, _int],
+    'bbt_gather_plan_destroy': [_vp],
+    'bbt_gather_plan_info': [_vp, C.POINTER(_int), _pi64, C.POINTER(_int), C.POINTER(_int)],
+    'bbt_gather_execute': [_vp, C.POINTER(_vp), _pi64, _vp, _i64, _vp],
     'bbt_real_op': [_vp, _vp, _int, _i64, _int, _int, _vp],
     'bbt_chirp': [_vp, _i64, _int, C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_double),
                   C.c_double, C.c_double, C.c_double, _vp],
@@ -120,7 +125,7 @@ SIGNATURES = {
 }
 
 #: oldest libbbt_hip.so whose entry points and argument meanings this binding assumes
-MIN_LIB_VERSION = 154
+MIN_LIB_VERSION = 155
 
 _lib = None
 _lock = threading.Lock()
@@ -1021,6 +1026,45 @@ class R2CPlan(_Plan):
     def execute(self, in_dev, out_dev, n_frames):
         """in_dev: (n_frames * 2 n_out, n_stream) float32 -> out_dev: (n_frames * n_out, n_stream) complex64."""
         check(lib().bbt_r2c_execute(self._h, in_dev.ptr_to_read(), out_dev.ptr, int(n_frames), _stream))
+
+
+class GatherPlan(_Plan):
+    """An index map over the elements of a sample (bbt_gather_*): element j of an output sample is
+    element ``map_elem[j]`` of the sample at the same time offset of source ``map_src[j]``."""
+    _destroy = 'bbt_gather_plan_destroy'
+    ROUTES = {'auto': 0, 'run_copy': 1, 'tile': 2, 'direct': 3}
+
+    def __init__(self, src_row_elems, map_src, map_elem, elem_bytes, route='auto'):
+        super().__init__()
+        rows = np.ascontiguousarray(src_row_elems, dtype=np.int64).ravel()
+        self.map_src = np.ascontiguousarray(map_src, dtype=np.int32).ravel()
+        self.map_elem = np.ascontiguousarray(map_elem, dtype=np.int64).ravel()
+        if self.map_src.shape != self.map_elem.shape:
+            raise ValueError("map_src and map_elem must have the same length")
+        self.n_src, self.elem_bytes = len(rows), int(elem_bytes)
+        self.src_row_elems, self.out_row_elems = rows, len(self.map_src)
+        check(lib().bbt_gather_plan_create_ex(
+            C.byref(self._h), self.n_src, rows.ctypes.data_as(_pi64), self.out_row_elems,
+            self.map_src.ctypes.data_as(C.POINTER(C.c_int32)), self.map_elem.ctypes.data_as(_pi64),
+            self.elem_bytes, self.ROUTES[route]))
+
+    def info(self):
+        route, runs, tile, lds = _int(), _i64(), _int(), _int()
+        check(lib().bbt_gather_plan_info(self._h, C.byref(route), C.byref(runs), C.byref(tile), C.byref(lds)))
+        names = {v: k for k, v in self.ROUTES.items()}
+        return dict(route=names[route.value], n_runs=runs.value, tile_samples=tile.value, lds_bytes=lds.value)
+
+    def execute(self, sources, out_dev, n_samples, first_samples=None):
+        """sources: one DeviceArray per source (None for a source the map does not use), source k
+        holding rows of ``src_row_elems[k]`` elements from sample ``first_samples[k]`` (default 0)
+        on; out_dev: ``n_samples`` rows of ``out_row_elems`` elements."""
+        if len(sources) != self.n_src:
+            raise ValueError(f"the plan has {self.n_src} sources; got {len(sources)}")
+        ptrs = (_vp * self.n_src)(*[None if s is None else s.ptr_to_read() for s in sources])
+        first = np.zeros(self.n_src, np.int64) if first_samples is None else \
+            np.ascontiguousarray(first_samples, dtype=np.int64)
+        check(lib().bbt_gather_execute(self._h, ptrs, first.ctypes.data_as(_pi64), out_dev.ptr,
+                                       int(n_samples), _stream))
 
 
 class PfbPlan(_Plan):

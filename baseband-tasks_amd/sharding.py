@@ -177,7 +177,9 @@ def gather_subbands(local, torch, dist, comm=None, axis=1):
     """Concatenate equally shaped per-rank results along the sub-band axis, in
     rank order: ``(n, k, ...)`` -> ``(n, world * k, ...)`` on every rank
     (``axis`` = 1, a dedispersed stream), or along any later axis -- a
-    channelized stream ``(n, n_chan, k, ...)`` has its sub-bands on axis 2."""
+    channelized stream ``(n, n_chan, k, ...)`` has its sub-bands on axis 2.
+    (Streams on one GPU are joined by `~baseband_tasks_amd.combining.Concatenate`,
+    which now exists; this function stays the collective across ranks.)"""
     world = dist.get_world_size()
     flat = gather_frames(local, torch, dist, comm)                 # (world * n, ...)
     n = local.shape[0]

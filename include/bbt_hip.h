@@ -14,6 +14,8 @@
  *   bbt_pfb_*   PolyphaseFilterBankSamples.ppf + Channelize.task
  *               pfb.py:91-100 (definition), 145-154 (Fourier form)
  *   bbt_r2c_*   Real2Complex.task             conversion.py:77-101
+ *   bbt_gather_plan_* / bbt_gather_execute   the `task` methods of shaping.py and
+ *               CombineStreamsBase._read_frame, combining.py:120-125
  *
  * Conventions
  *   - every function returns 0 on success, non-zero on failure;
@@ -46,6 +48,7 @@ typedef struct bbt_pfb_plan bbt_pfb_plan;
 typedef struct bbt_shift_plan bbt_shift_plan;
 typedef struct bbt_fir_plan bbt_fir_plan;
 typedef struct bbt_r2c_plan bbt_r2c_plan;
+typedef struct bbt_gather_plan bbt_gather_plan;
 typedef struct bbt_comm bbt_comm;
 
 /* ---- library / device ------------------------------------------------- */
@@ -387,6 +390,54 @@ int bbt_r2c_plan_destroy(bbt_r2c_plan* plan);
 int bbt_r2c_plan_info(const bbt_r2c_plan* plan, int* one_pass, int64_t* workspace_bytes);
 int bbt_r2c_execute(bbt_r2c_plan* plan, const void* in_dev, void* out_dev, int64_t n_frames,
                     bbt_stream stream);
+
+/* ---- shaping and combining: index maps -----------------------------------------
+ * Replaces the `task` methods of shaping.py (Reshape, Transpose, ReshapeAndTranspose, GetItem,
+ * GetSlice, ChangeSampleShape) and CombineStreamsBase._read_frame (combining.py:120-125: Stack,
+ * Concatenate, CombineStreams).  None of them computes: element j of an output sample is a copy
+ * of element map_elem[j] of the sample at the same time offset of source map_src[j],
+ *   out[t][j] = src[map_src[j]][src_first_sample[map_src[j]] + t][map_elem[j]],  0 <= j < out_row_elems.
+ *   n_src          1 to 64 sources; src_row_elems[s]: elements per sample of source s
+ *   out_row_elems  elements per output sample (rows of less than 2 GiB)
+ *   elem_bytes     1, 2, 4, 8 or 16 (all sources and the output share it)
+ * The maps are copied; entries out of range are refused.  The plan compresses the map into runs
+ * (maximal stretches where source and element advance together) and picks a route:
+ *   BBT_GATHER_RUN_COPY  every run, and every row, is whole 16-byte units at 16-byte offsets:
+ *                        lanes move 16 bytes each, consecutive lanes consecutive addresses
+ *   BBT_GATHER_TILE      short runs: a workgroup stages tile_samples samples of the stretch of each
+ *                        source row that the map uses in LDS and writes the output rows
+ *                        coalesced, reading LDS through the map.  tile_samples is what fits 32 KiB
+ *                        if that is eight samples at least, else what fits 64 KiB (the budget of
+ *                        the other kernels); taken when a tile fits and the stretches are at most
+ *                        four times the bytes used
+ *   BBT_GATHER_DIRECT    everything else: one output element per lane, gathered reads
+ * bbt_gather_plan_create_ex forces a route (tests run each on one map); a route whose conditions
+ * the map does not meet is refused.  bbt_gather_plan_create is route = BBT_GATHER_AUTO.
+ * bbt_gather_execute: src_dev[s] is the device address of source s (entries of sources the map
+ * does not use are not read), src_first_sample[s] the sample of it that goes with output sample 0
+ * (null: all zero) -- how Stack aligns streams that start at different times; out_dev holds
+ * n_samples rows.  One launch serves all sources.  Pointers must be aligned to elem_bytes; where
+ * one is not 16-byte aligned the run-copy route runs on the direct kernel and the tile route
+ * stages element by element.  An output that overlaps a source is refused.  All index arithmetic
+ * over n_samples * row is 64-bit.  No atomics: results are bit-reproducible.  Asynchronous on
+ * `stream`.  Creating a plan and asking for its route need no device: the first execute call
+ * uploads the tables, to the device that is current then; after that the plan does not change, so
+ * calls on it may run concurrently. */
+#define BBT_GATHER_AUTO 0
+#define BBT_GATHER_RUN_COPY 1
+#define BBT_GATHER_TILE 2
+#define BBT_GATHER_DIRECT 3
+#define BBT_GATHER_LDS_BYTES 65536
+int bbt_gather_plan_create(bbt_gather_plan** plan, int n_src, const int64_t* src_row_elems, int64_t out_row_elems,
+                           const int32_t* map_src, const int64_t* map_elem, int elem_bytes);
+int bbt_gather_plan_create_ex(bbt_gather_plan** plan, int n_src, const int64_t* src_row_elems,
+                              int64_t out_row_elems, const int32_t* map_src, const int64_t* map_elem,
+                              int elem_bytes, int route);
+int bbt_gather_plan_destroy(bbt_gather_plan* plan);
+int bbt_gather_plan_info(const bbt_gather_plan* plan, int* route, int64_t* n_runs, int* tile_samples,
+                         int* lds_bytes);
+int bbt_gather_execute(bbt_gather_plan* plan, const void* const* src_dev, const int64_t* src_first_sample,
+                       void* out_dev, int64_t n_samples, bbt_stream stream);
 
 /* ---- integer sample shifts -------------------------------------------------
  * Replaces ShiftSamples.task (sampling.py:424-425, data[self._indices]), the
