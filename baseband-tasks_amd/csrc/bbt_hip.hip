@@ -22,6 +22,7 @@
 #include "gen_kernels.hpp"
 #include "big_kernels.hpp"
 #include "gen2_host.hpp"
+#include "gen_host.hpp"
 #include "rtc.hpp"
 #include "fold_kernels.hpp"
 #include "r2c_kernels.hpp"
@@ -155,51 +156,7 @@ static int get_wroot(cf** out) {
 static bool fft_len_ok(int64_t n) { return is_pow2(n) && n >= 256 && n <= 4096; }
 
 // ---- lengths 2^a 3^b 5^c 7^d (fft_generic.hpp) ------------------------------
-static bool factor_7smooth(int64_t n, GenGeo* g) {
-    // Stages of the LDS Stockham transform: radices from {2..10, 12, 14, 15, 16} (the composite
-    // ones are small Cooley-Tukey transforms on registers, fft_generic.hpp), as few as possible --
-    // every stage is a round trip of the whole tile through LDS with two barriers -- and among
-    // the shortest lists the one with the smallest largest radix (registers).
-    if (n < 1 || n > BBT_GEN_MAX_LEN) return false;
-    static const int all[] = {16, 15, 14, 12, 10, 9, 8, 7, 6, 5, 4, 3, 2};
-    const int* radices = all;
-    int nrad = 13;
-    while (nrad > 1 && radices[0] > BBT_GEN_MAXR) {   // (the list is in descending order)
-        ++radices;
-        --nrad;
-    }
-    g->n = (int)n;
-    g->nfac = 0;
-    if (n == 1) return true;
-    // dynamic programme over the divisors of n: best[d] = (stages, largest radix) to reach d
-    std::map<int64_t, std::pair<int, int>> best;
-    std::map<int64_t, int> step;
-    best[1] = {0, 0};
-    std::vector<int64_t> divisors;
-    for (int64_t d = 1; d <= n; ++d)
-        if (n % d == 0) divisors.push_back(d);
-    for (int64_t d : divisors) {
-        auto it = best.find(d);
-        if (it == best.end()) continue;
-        for (int i = 0; i < nrad; ++i) {
-            const int r = radices[i];
-            const int64_t e = d * r;
-            if (n % e) continue;
-            const std::pair<int, int> cand = {it->second.first + 1, std::max(it->second.second, r)};
-            auto jt = best.find(e);
-            if (jt == best.end() || cand < jt->second) {
-                best[e] = cand;
-                step[e] = r;
-            }
-        }
-    }
-    if (!best.count(n) || best[n].first > BBT_GEN_MAX_FACTORS) return false;
-    std::vector<int> fac;
-    for (int64_t d = n; d > 1; d /= step[d]) fac.push_back(step[d]);
-    std::sort(fac.begin(), fac.end(), std::greater<int>());      // (large radices first: fewer twiddles)
-    for (int r : fac) g->fac[g->nfac++] = r;
-    return true;
-}
+// (stage lists, workgroup size, split and tile rules: gen_host.hpp)
 static int rtc_mode() {                     // 0 off, 1 on, 2 required
     const char* e = getenv("BBT_RTC");
     if (!e || !*e) return 1;
@@ -213,8 +170,7 @@ static bool is_7smooth(int64_t n) {
         while (n % r == 0) n /= r;
     return n == 1;
 }
-// N = N1 * N2 with N1 <= N2 <= BBT_GEN_MAX_LEN: the largest N1 up to 512 (the column passes
-// then hold 8 columns of N1 points in their LDS tile: 128-byte runs), else as balanced as possible.
+// N = N1 * N2 for a two-level plan (gen_host.hpp: gen_split)
 static bool split_7smooth(int64_t n, int* n1, int* n2) {
     if (const char* env = getenv("BBT_GEN_N1")) {            // (dev: force the split)
         const int64_t d = atoll(env);
@@ -224,25 +180,7 @@ static bool split_7smooth(int64_t n, int* n1, int* n2) {
             return true;
         }
     }
-    // (plans on the run-time specialised kernels: the split rule measured for them; the column
-    // tile of the general kernels holds n1 * 8 <= 8192 elements, so n1 <= 1024 keeps the fall-back)
-    if (rtc_mode() && g2_choose_split(n, 8, 1024, BBT_GEN_MAX_LEN, n1, n2)) return true;
-    const int64_t prefer = 512;
-    int64_t best = 0, wide = 0;
-    for (int64_t d = 1; d * d <= n; ++d)
-        if (n % d == 0 && n / d <= BBT_GEN_MAX_LEN) {
-            best = d;
-            if (d <= prefer) wide = d;
-        }
-    if (wide) best = wide;
-    if (!best) return false;
-    *n1 = (int)best;
-    *n2 = (int)(n / best);
-    return true;
-}
-static int gen_threads(int elements) {          // elements <= BBT_GEN_EPT * threads, whole waves
-    int t = ((elements + BBT_GEN_EPT - 1) / BBT_GEN_EPT + 63) / 64 * 64;
-    return t < 64 ? 64 : (t > 1024 ? 1024 : t);
+    return gen_split(n, rtc_mode() != 0, n1, n2);
 }
 static std::map<std::pair<int, int>, cf*> g_gen_tables;    // (device, n) -> stage twiddles; -n: stages reversed
 static int get_gen_table(GenGeo* g, cf** out, bool reversed = false);
@@ -1154,6 +1092,10 @@ static int osm_run_chunk(bbt_osm_plan* p, const float2* in, float2* out, const O
             }
         } else {
             const int ct = p->gen_ct, tiles = (p->n2 + ct - 1) / ct;
+            // (what k_gen_col transforms: a tile beyond it would come back untransformed in part)
+            ARG_TRY(ct >= 1 && (ct & (ct - 1)) == 0 && (long long)p->n1 * ct <= BBT_GEN_MAX_LEN,
+                    "osm: a column tile of %d x %d elements is more than the general kernels' %d (or not a power of two of columns)",
+                    p->n1, ct, BBT_GEN_MAX_LEN);
             const size_t lds_c = (size_t)p->n1 * ct * sizeof(f4), lds_r = (size_t)p->n2 * sizeof(f4);
             if (ensure_dyn_lds((const void*)k_gen_col<true>, lds_c) ||
                 ensure_dyn_lds((const void*)k_gen_col<false>, lds_c) ||
@@ -1497,19 +1439,12 @@ int bbt_osm_plan_create(bbt_osm_plan** plan, int64_t n_fft, int n_stream, int n_
     }
     p->n2 = (int)(n_fft / p->n1 / p->outer);
     if (p->generic) {
-        if (!factor_7smooth(p->n2, &p->g2) || (p->n1 > 1 && !factor_7smooth(p->n1, &p->g1)))
+        if (!gen_factor_7smooth(p->n2, &p->g2) || (p->n1 > 1 && !gen_factor_7smooth(p->n1, &p->g1)))
             return bail(fail("bbt_osm_plan_create: cannot factor %d x %d", p->n1, p->n2));
         if (get_gen_table(&p->g2, &p->wn2) || get_reversed(p->g2, &p->g2r, &p->wn2r)) return bail(1);
-        // columns per tile: a power of two (gen_stage), as many as fit the LDS tile up to 8
-        // (128-byte runs of the stream and of the work buffer; measured: 8 columns 18.9, 16
-        // columns 18.1, 4 columns 17.3 Gsamples/s for the 1 666 980-sample block)
-        p->gen_ct = 1;
-        if (p->n1 > 1) {
-            // (short blocks on the compiled kernels: as many columns as fill a wave, gen2_host.hpp g2_col_ct)
-            const int ct_cap = getenv("BBT_GEN_CT") ? atoi(getenv("BBT_GEN_CT"))         // (dev)
-                               : (rtc_mode() && n_fft <= (1 << 17)) ? g2_col_ct(p->n1, g2_pmax(BBT_G2_KIND_COL)) : 8;
-            while (p->gen_ct < ct_cap && 2 * p->gen_ct * p->n1 <= 2 * BBT_GEN_MAX_LEN) p->gen_ct *= 2;
-        }
+        // columns per tile of the column passes (gen_host.hpp: gen_col_ct_wanted)
+        p->gen_ct = gen_col_ct_wanted(n_fft, p->n1, rtc_mode() != 0,
+                                      getenv("BBT_GEN_CT") ? std::max(1, atoi(getenv("BBT_GEN_CT"))) : 0);     // (dev)
         // The kernels specialised on this length (fft_gen2.hpp), compiled now; if that is not
         // possible the plan runs on the general ones.
         if (rtc_mode()) {
@@ -1519,12 +1454,7 @@ int bbt_osm_plan_create(bbt_osm_plan** plan, int64_t n_fft, int n_stream, int n_
             if (ok) p->q2r = g2_reversed(p->q2);
             if (ok && p->n1 > 1) {
                 // (a column tile is one workgroup: at most 1024 threads and 64 KiB of exchange area)
-                int ct = p->gen_ct;
-                while ((ok = g2_plan(p->n1, ct, &p->q1, g2_pmax(BBT_G2_KIND_COL))) && ct > 1 &&
-                       (p->q1.threads() > 1024 || p->q1.lds_elems * 8 > 64 * 1024))
-                    ct /= 2;
-                p->gen_ct = ct;
-                ok = ok && p->q1.threads() <= 1024 && p->q1.lds_elems * 8 <= 64 * 1024;
+                ok = g2_fit_col_plan(p->n1, &p->gen_ct, &p->q1);
             }
             ok = ok && p->q2.threads() <= 1024 && std::max(p->q2.lds_elems, p->q2r.lds_elems) * 8 <= 96 * 1024;
             if (!ok) fail("no stage list within a workgroup for %d x %d", p->n1, p->n2);
@@ -1900,7 +1830,7 @@ static int osm_channelized(bbt_osm_plan* p, const char* who, const void* in_dev,
     FftTables tabc;
     GenGeo gsmall = {};
     cf* wsmall = nullptr;
-    if (small ? (!factor_7smooth(n_chan, &gsmall) || get_gen_table(&gsmall, &wsmall))
+    if (small ? (!gen_factor_7smooth(n_chan, &gsmall) || get_gen_table(&gsmall, &wsmall))
               : get_tables(n_chan, &tabc))
         return 1;
     // seam slots and jobs.  The slots are filled by the lanes and read by the seam pass at the
@@ -2476,7 +2406,7 @@ int bbt_chan_plan_create(bbt_chan_plan** plan, int n_chan, int n_stream, int dir
         }
     } else if (!fast) {
         p->generic = true;
-        if (!factor_7smooth(n_chan, &p->g) || get_gen_table(&p->g, &p->wn)) {
+        if (!gen_factor_7smooth(n_chan, &p->g) || get_gen_table(&p->g, &p->wn)) {
             if (g_err.empty()) fail("bbt_chan_plan_create: cannot factor n_chan=%d", n_chan);
             delete p;
             return 1;
@@ -3134,7 +3064,7 @@ int bbt_r2c_plan_create_ex(bbt_r2c_plan** plan, int64_t n_out, int n_stream, int
         if (get_big_table((int)n_out, &p->big_tw)) return bail(1);
         if (upload(&p->resp, r2c_response(n_out, 1.0 / (double)n_out))) return bail(1);
     } else if (p->one_pass) {
-        if (!factor_7smooth(n_out, &p->g)) return bail(fail("bbt_r2c_plan_create: cannot factor %lld", (long long)n_out));
+        if (!gen_factor_7smooth(n_out, &p->g)) return bail(fail("bbt_r2c_plan_create: cannot factor %lld", (long long)n_out));
         if (get_gen_table(&p->g, &p->wn) || get_reversed(p->g, &p->gr, &p->wnr)) return bail(1);
         if (upload(&p->resp, r2c_response(n_out, 1.0 / (double)n_out))) return bail(1);
         if (rtc_mode()) {

@@ -36,15 +36,11 @@
 #include <hip/hip_runtime.h>
 #endif
 #include "fft_core.hpp"
+#include "gen_geo.hpp"
 
 namespace bbt {
 
-#define BBT_GEN_MAX_FACTORS 24
-#define BBT_GEN_MAX_LEN 8192          // elements of one LDS tile (n * ct)
-#ifndef BBT_GEN_EPT
-#define BBT_GEN_EPT 8                 // tile elements per thread
-#endif
-#define BBT_GEN_MAX_THREADS (BBT_GEN_MAX_LEN / BBT_GEN_EPT)
+// (BBT_GEN_MAX_LEN, BBT_GEN_EPT, BBT_GEN_MAXR and GenGeo: gen_geo.hpp, shared with the host rules)
 // Stage twiddles W^{r k}, r < R: 1 = one table value W^k per butterfly and its powers by products
 // (w[r] = w[ceil(r/2)] w[floor(r/2)], at most four roundings deep); 0 = R - 1 table loads.  The
 // loads were what the stages waited for (eight 8-byte loads per radix-9 butterfly against nine
@@ -54,15 +50,6 @@ namespace bbt {
 #ifndef BBT_GEN_TW_POWERS
 #define BBT_GEN_TW_POWERS 1
 #endif
-#ifndef BBT_GEN_MAXR
-#define BBT_GEN_MAXR 12               // largest radix of a stage (14 .. 16: spilled registers; measured 5 % slower)
-#endif
-struct GenGeo {
-    int n;                            // transform length
-    int nfac;                         // number of stages
-    int fac[BBT_GEN_MAX_FACTORS];     // radices in {2..10, 12, 14, 15, 16}, product n
-    int woff[BBT_GEN_MAX_FACTORS];    // where stage s finds its twiddles in the table (host: get_gen_table)
-};
 
 typedef float f4 __attribute__((ext_vector_type(4)));
 __device__ __forceinline__ c2 f4_to_c2(f4 x) { return c2{v2{x.x, x.y}, v2{x.z, x.w}}; }

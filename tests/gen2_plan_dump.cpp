@@ -1,9 +1,12 @@
 // Prints what the host planner of the generic-length engine (csrc/gen2_host.hpp) decides, as
 // JSON lines, for tests/test_gen2_planner.py:   gen2_plan_dump plan <pmax> <n> <ct> ... | split <N> ...
+// and, per block length, what bbt_osm_plan_create runs a two-level block of the general LDS
+// Stockham kernels with (csrc/gen_host.hpp):      gen2_plan_dump route off|on|failed <N> ...
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
 #include "gen2_host.hpp"
+#include "gen_host.hpp"
 using namespace bbt;
 
 static void dump(const G2Plan& g) {
@@ -44,6 +47,33 @@ int main(int argc, char** argv) {
             printf(", \"row\": ");
             dump(r);
             printf("}\n");
+        }
+    } else if (!strcmp(argv[1], "route")) {
+        // mode: plan-time compilation off (BBT_RTC=0), on, or on and failed (the general kernels
+        // then run with the split and the tile chosen for the compiled ones)
+        const int mode = !strcmp(argv[2], "off") ? BBT_GEN_RTC_OFF : !strcmp(argv[2], "on") ? BBT_GEN_RTC_ON : BBT_GEN_RTC_FAILED;
+        for (int i = 3; i < argc; ++i) {
+            const long long n = atoll(argv[i]);
+            int n1 = 0, n2 = 0;
+            bool measured = false;          // (the split is the one measured for the compiled kernels)
+            GenGeo f1, f2;
+            if (!gen_split(n, mode != BBT_GEN_RTC_OFF, &n1, &n2, &measured) || !gen_factor_7smooth(n1, &f1) || !gen_factor_7smooth(n2, &f2)) {
+                printf("null\n");
+                continue;
+            }
+            const int ct = gen_col_ct(n, n1, mode);
+            // (the columns the compiled kernels take on this split)
+            int g2_ct = gen_col_ct_wanted(n, n1, true);
+            G2Plan q1;
+            const bool fits = g2_fit_col_plan(n1, &g2_ct, &q1);
+            printf("{\"n\": %lld, \"n1\": %d, \"n2\": %d, \"ct\": %d, \"col_threads\": %d, \"col_lds\": %lld, "
+                   "\"row_threads\": %d, \"row_lds\": %lld, \"g2_split\": %s, \"g2_ct\": %d, \"g2_fits\": %s, \"fac1\": [",
+                   n, n1, n2, ct, gen_threads(n1 * ct), (long long)n1 * ct * 16, gen_threads(n2), (long long)n2 * 16,
+                   measured ? "true" : "false", g2_ct, fits ? "true" : "false");
+            for (int s = 0; s < f1.nfac; ++s) printf("%s%d", s ? ", " : "", f1.fac[s]);
+            printf("], \"fac2\": [");
+            for (int s = 0; s < f2.nfac; ++s) printf("%s%d", s ? ", " : "", f2.fac[s]);
+            printf("]}\n");
         }
     } else if (!strcmp(argv[1], "source")) {
         G2Plan g;

@@ -203,3 +203,103 @@ def test_two_level_source_of_short_blocks_compiles(dump, n):
         assert sorted(name for _, name, _ in found) == ['k_first', 'k_last', 'k_row']
         for lds, name, scratch in found:
             assert int(scratch) == 0 and int(lds) <= 64 * 1024, (n, name, lds, scratch)
+
+
+# --------------------------------------------------------------------------- the general kernels' routes
+GEN_MAX_LEN, GEN_EPT, LDS_CAP = 8192, 8, 160 * 1024      # (csrc/gen_geo.hpp; LDS of a CU of gfx950)
+MODES = ('off', 'on', 'failed')
+
+
+def smooth_lengths(lo, hi):
+    """Every 2^a 3^b 5^c 7^d in (lo, hi], ascending."""
+    out = []
+    p7 = 1
+    while p7 <= hi:
+        p5 = p7
+        while p5 <= hi:
+            p3 = p5
+            while p3 <= hi:
+                p2 = p3
+                while p2 <= hi:
+                    if p2 > lo:
+                        out.append(p2)
+                    p2 *= 2
+                p3 *= 3
+            p5 *= 5
+        p7 *= 7
+    return sorted(out)
+
+
+def _package_module(name):
+    """A module of the package without the package's own import (which loads the library)."""
+    import types
+    pkg = 'bbt_planner_pkg'
+    if pkg not in sys.modules:
+        stub = types.ModuleType(pkg)
+        stub.__path__ = [os.path.join(ROOT, 'baseband-tasks_amd')]
+        sys.modules[pkg] = stub
+    return importlib.import_module(f'{pkg}.{name}')
+
+
+def route_faults(g):
+    """What of the general kernels' contract (csrc/fft_generic.hpp: a tile of n * ct <= BBT_GEN_MAX_LEN
+    elements, every stage of radix R covering it with ceil(BBT_GEN_EPT / R) butterflies per thread)
+    the route `g` of one block length breaks: a list of words, empty if it is sound."""
+    bad = []
+    n, n1, n2, ct = g['n'], g['n1'], g['n2'], g['ct']
+    if n1 * n2 != n or int(np.prod(g['fac1'])) != n1 or int(np.prod(g['fac2'])) != n2:
+        bad.append('product')
+    if n2 > GEN_MAX_LEN:
+        bad.append('n2')
+    if ct < 1 or ct & (ct - 1) or g['col_threads'] % ct:
+        bad.append('ct')
+    if n1 * ct > GEN_MAX_LEN:
+        bad.append('tile')
+    if g['col_lds'] != n1 * ct * 16 or g['row_lds'] != n2 * 16 or max(g['col_lds'], g['row_lds']) > LDS_CAP:
+        bad.append('lds')
+    for fac, threads, elems in ((g['fac1'], g['col_threads'], n1 * ct), (g['fac2'], g['row_threads'], n2)):
+        if threads % 64 or not 64 <= threads <= 1024:
+            bad.append('threads')
+        if any(r * -(-GEN_EPT // r) * threads < elems for r in fac):
+            bad.append('stage')
+    return bad
+
+
+def test_every_block_length_gets_a_sound_route_on_the_general_kernels(dump):
+    """Every block length the Python side hands the library (fourier.py: HipFFTMaker._transformable,
+    2^a 3^b 5^c 7^d in (8192, 2^26] that are not powers of two), in every mode of plan-time compilation -- off
+    (BBT_RTC=0), on, and on but failed, when the general kernels run with the split and the tile chosen
+    for the compiled ones: N1 x N2 = N, N2 <= 8192, a tile of `ct` columns (a power of two that
+    divides the workgroup) within BBT_GEN_MAX_LEN elements and 160 KiB of LDS, and every stage
+    of both factors reaching the whole tile (`R * ceil(BBT_GEN_EPT / R) * threads >= elements`,
+    the caller's contract of fft_generic.hpp).  A tile beyond that is transformed in part, without
+    an error."""
+    fourier = _package_module('fourier')
+    lengths = [n for n in smooth_lengths(8192, 2**26) if n & (n - 1) and fourier.HipFFTMaker._transformable(n)]
+    assert len(lengths) == 2792
+    for mode in MODES:
+        routes = dump('route', mode, *lengths)
+        assert None not in routes, (mode, [n for n, g in zip(lengths, routes) if g is None][:10])
+        faults = [(g['n'], g['n1'], g['n2'], g['ct'], route_faults(g)) for g in routes if route_faults(g)]
+        assert not faults, (mode, len(faults), faults[:8])
+        assert [g['n'] for g in routes] == lengths
+
+
+def test_python_and_c_agree_on_the_lengths_that_split(dump):
+    """`HipFFTMaker._transformable` (fourier.py) and `_splits` (conversion.py) accept a block length
+    exactly when the library's split rule finds two factors for it: every 2^a 3^b 5^c 7^d in
+    (8192, 2^26], powers of two included, with plan-time compilation on and off."""
+    fourier, conversion = _package_module('fourier'), _package_module('conversion')
+    lengths = smooth_lengths(8192, 2**26)
+    assert len(lengths) + len(smooth_lengths(0, 8192)) == 3174          # (the count fourier.py states)
+    splits = [conversion._splits(n) for n in lengths]
+    transformable = [fourier.HipFFTMaker._transformable(n) for n in lengths]
+    for mode in ('off', 'on'):
+        routes = dump('route', mode, *lengths)
+        assert len(routes) == len(lengths)
+        for n, g, s, t in zip(lengths, routes, splits, transformable):
+            assert (g is not None) == s, (mode, n)
+            if n & (n - 1):              # (powers of two: their own plans, up to 2^24)
+                assert (g is not None) == t, (mode, n)
+    refused = [n for n, t in zip(lengths, transformable) if not t]
+    assert len(refused) == 52 and refused[0] == 20588575        # (5^2 7^7: fourier.py)
