@@ -26,6 +26,7 @@ from .shaping import (ChangeSampleShapeBase, ChangeSampleShape, Reshape, Transpo
                       GetItem, GetSlice)
 from .combining import CombineStreamsBase, CombineStreams, Concatenate, Stack
 from .ingest import RawFrameStream, open_vdif, open_dada
+from . import phases
 from . import hip
 from . import hdf5
 

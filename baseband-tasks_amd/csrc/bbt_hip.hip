@@ -25,12 +25,13 @@
 #include "gen_host.hpp"
 #include "rtc.hpp"
 #include "fold_kernels.hpp"
+#include "phase_kernels.hpp"
 #include "r2c_kernels.hpp"
 #include "gather_kernels.hpp"
 
 using namespace bbt;
 
-#define BBT_VERSION 155
+#define BBT_VERSION 156
 
 // ---------------------------------------------------------------------------
 // errors
@@ -2981,6 +2982,91 @@ extern "C" int bbt_fold_runs(const void* in_dev, void* out_dev, int64_t n_in, in
                            scale_dev, accumulate);
         HIP_TRY(hipGetLastError());
     }
+    return 0;
+}
+
+// ---------------------------------------------------------------------------
+// run tables from polynomial phases (phase_kernels.hpp)
+static int64_t phase_tiles(int64_t n) { return (n + BBT_PHASE_TILE - 1) / BBT_PHASE_TILE; }
+
+// work area: grid (int32 per cell, padded to 16 bytes) | sample tiles | cell tiles | n_run, status,
+// n_occupied, pad | begin, slot, slot by position (run_cap each)
+extern "C" int bbt_phase_runs_work(int64_t n_samples, int64_t n_cell, int64_t run_cap, int64_t* bytes) {
+    ARG_TRY(bytes, "bbt_phase_runs_work: null argument");
+    ARG_TRY(n_samples >= 0 && n_cell >= 0 && run_cap >= 0, "bbt_phase_runs_work: bad sizes");
+    ARG_TRY(n_cell < (1ll << 40) && n_samples < (1ll << 40) && run_cap <= n_samples,
+            "bbt_phase_runs_work: sizes out of range");
+    *bytes = ((n_cell * 4 + 15) / 16) * 16 + 8 * (phase_tiles(n_samples) + phase_tiles(n_cell) + 4 + 3 * run_cap);
+    return 0;
+}
+
+extern "C" int bbt_phase_runs(const void* pieces_dev, int64_t n_piece, int n_coeff, int64_t s_begin,
+                              int64_t s_end, int64_t n_phase, const int64_t* rows_dev, int64_t n_row,
+                              int64_t n_cell, int64_t slot0, int64_t n_slot, int64_t run_cap,
+                              int64_t* slot_ptr_dev, int64_t* run_begin_dev, int64_t* run_end_dev,
+                              int64_t* counts_dev, void* work_dev, int64_t work_bytes, int64_t* info,
+                              bbt_stream stream) {
+    ARG_TRY(pieces_dev && rows_dev && slot_ptr_dev && run_begin_dev && run_end_dev && counts_dev && work_dev && info,
+            "bbt_phase_runs: null argument");
+    ARG_TRY(n_piece >= 1 && n_piece < (1ll << 31) && n_coeff >= 1 && n_coeff <= 64 && n_phase >= 1 && n_row >= 1,
+            "bbt_phase_runs: bad sizes");
+    ARG_TRY(s_begin >= 0 && s_end > s_begin, "bbt_phase_runs: the pieces cover no samples");
+    ARG_TRY(slot0 >= 0 && n_row * n_phase <= n_slot - slot0, "bbt_phase_runs: the rows do not fit the slots");
+    ARG_TRY(n_cell >= 1 && run_cap >= 1 && run_cap <= s_end - s_begin && run_cap < (1ll << 31),
+            "bbt_phase_runs: bad grid or run capacity");
+    ARG_TRY(((uintptr_t)work_dev & 15) == 0, "bbt_phase_runs: the work area must be 16-byte aligned");
+    const int64_t n = s_end - s_begin;
+    int64_t need = 0;
+    if (bbt_phase_runs_work(n, n_cell, run_cap, &need) != 0) return 1;
+    ARG_TRY(work_bytes >= need, "bbt_phase_runs: work area of %lld bytes, %lld needed", (long long)work_bytes,
+            (long long)need);
+    const int64_t nt_s = phase_tiles(n), nt_c = phase_tiles(n_cell);
+    ARG_TRY(nt_s < (1ll << 31) && nt_c < (1ll << 31) && n_slot < (1ll << 38), "bbt_phase_runs: too large for one call");
+    hipStream_t st = (hipStream_t)stream;
+    int* grid = (int*)work_dev;
+    long long* w = (long long*)((char*)work_dev + ((n_cell * 4 + 15) / 16) * 16);
+    long long* tile_s = w;
+    long long* tile_c = tile_s + nt_s;
+    long long* scalars = tile_c + nt_c;                      // n_run, status, n_occupied
+    long long* begin_t = scalars + 4;
+    long long* slot_t = begin_t + run_cap;
+    long long* slot_sorted = slot_t + run_cap;
+    const long long* q = (const long long*)pieces_dev;
+    PhasePieces P;
+    P.lo = q;
+    P.m0 = q + (n_piece + 1);
+    P.row = P.m0 + n_piece;
+    P.dt0 = (const double*)(P.row + n_piece);
+    P.step = P.dt0 + n_piece;
+    P.ref_int = P.step + n_piece;
+    P.ref_frac = P.ref_int + n_piece;
+    P.coeff = P.ref_frac + n_piece;
+    P.n_piece = (int)n_piece;
+    P.n_coeff = n_coeff;
+    const long long* rows = (const long long*)rows_dev;      // k0 | n_cycle | cell0
+    HIP_TRY(hipMemsetAsync(grid, 0, (size_t)n_cell * 4, st));
+    HIP_TRY(hipMemsetAsync(scalars, 0, 32, st));
+    HIP_TRY(hipMemsetAsync(counts_dev, 0, (size_t)(n_row * n_phase) * 8, st));
+    hipLaunchKernelGGL(k_phase_count, dim3((unsigned)nt_s), dim3(256), 0, st, P, (long long)n_phase, tile_s);
+    hipLaunchKernelGGL(k_scan_tiles, dim3(1), dim3(256), 0, st, tile_s, (long long)nt_s, scalars, (long long)run_cap,
+                       scalars + 1);
+    hipLaunchKernelGGL(k_phase_scatter, dim3((unsigned)nt_s), dim3(256), 0, st, P, (long long)n_phase,
+                       (const long long*)tile_s, rows, rows + n_row, rows + 2 * n_row, (long long)n_row,
+                       (long long)n_cell, (long long)slot0, (long long)run_cap, begin_t, slot_t, grid, scalars + 1);
+    hipLaunchKernelGGL(k_grid_count, dim3((unsigned)nt_c), dim3(256), 0, st, (const int*)grid, (long long)n_cell, tile_c);
+    hipLaunchKernelGGL(k_scan_tiles, dim3(1), dim3(256), 0, st, tile_c, (long long)nt_c, scalars + 2,
+                       (long long)run_cap, scalars + 1);
+    hipLaunchKernelGGL(k_grid_compact, dim3((unsigned)nt_c), dim3(256), 0, st, (const int*)grid, (long long)n_cell,
+                       (const long long*)tile_c, (const long long*)begin_t, (const long long*)slot_t,
+                       (const long long*)scalars, (long long)run_cap, (const long long*)(scalars + 1),
+                       (long long)s_end, (long long)slot0, (long long)(n_row * n_phase), (long long*)run_begin_dev,
+                       (long long*)run_end_dev, slot_sorted, (unsigned long long*)counts_dev);
+    hipLaunchKernelGGL(k_slot_ptr, dim3((unsigned)((n_slot + 1 + 255) / 256)), dim3(256), 0, st,
+                       (const long long*)slot_sorted, (const long long*)scalars, (long long)run_cap,
+                       (const long long*)(scalars + 1), (long long)n_slot, (long long*)slot_ptr_dev);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipMemcpyAsync(info, scalars, 16, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
     return 0;
 }
 

@@ -20,7 +20,7 @@ sample's ``k`` comes from the same time expression, only fewer of them are asked
 import numpy as np
 
 __all__ = ['phase_parts', 'phase_difference', 'sample_times', 'bin_runs', 'fold_table',
-           'contiguous_table']
+           'contiguous_table', 'polynomial_bins', 'piece_table', 'plan_pieces']
 
 #: samples handled in one piece by `bin_runs` (bounds host memory)
 PIECE = 1 << 22
@@ -57,6 +57,30 @@ def unwrapped_bin(value, n_phase):
     """``floor(phase) * n_phase + int((phase % 1) * n_phase)``, int64."""
     whole, frac = phase_parts(value)
     b = np.minimum((frac * n_phase).astype(np.int64), n_phase - 1)
+    return whole * n_phase + b
+
+
+def polynomial_bins(coeff, dt0, step, ref_int, ref_frac, m, n_phase):
+    """Unwrapped bin of the samples ``m`` (int64 offsets from the row start) of a piece whose
+    phase is a polynomial: ``x = dt0 + m * step``, ``phase = ref_int + ref_frac +
+    sum_j coeff[j] x**j`` (``ref_int`` a whole number, ``ref_frac`` in [-0.5, 0.5]).
+
+    This function is the definition of the bins of a phase that offers pieces (see
+    `~baseband_tasks_amd.phases.PolycoPhase.fold_pieces`): the table kernel
+    (csrc/phase_kernels.hpp) carries out the same float64 operations in the same order, none
+    of them fused, so host and device agree bit for bit.
+    """
+    x = dt0 + np.asarray(m, dtype=np.int64).astype(np.float64) * step
+    p = np.full(x.shape, coeff[-1], dtype=np.float64)
+    for c in coeff[-2::-1]:
+        p = p * x
+        p = p + c
+    whole = np.floor(p)
+    frac = (p - whole) + ref_frac                   # in [-0.5, 1.5)
+    carry = np.floor(frac)
+    frac = frac - carry
+    whole = whole.astype(np.int64) + carry.astype(np.int64) + np.int64(ref_int)
+    b = np.minimum((frac * float(n_phase)).astype(np.int64), n_phase - 1)
     return whole * n_phase + b
 
 
@@ -214,6 +238,99 @@ def fold_table(row_edges, row_phase, n_phase, c0, c1):
         return r0, n_row, np.zeros(n_row * n_phase + 1, np.int64), z, z, np.zeros(n_row * n_phase, np.int64)
     return (r0, n_row) + _csr(np.concatenate(slots), np.concatenate(begins), np.concatenate(ends),
                               n_row * n_phase, c0)
+
+
+def piece_rows(row_edges, c0, c1):
+    """(first row, one past the last row) of the rows that meet the chunk [c0, c1)."""
+    r0 = max(int(np.searchsorted(row_edges, c0, side='right')) - 1, 0)
+    r1 = min(int(np.searchsorted(row_edges, c1, side='left')), len(row_edges) - 1)
+    return r0, max(r1, r0)
+
+
+def piece_table(row_edges, row_pieces, n_phase, c0, c1):
+    """`fold_table` for a phase given in polynomial pieces, on the host: the bin of every
+    sample from `polynomial_bins`, runs where (row, bin) changes.
+
+    ``row_pieces(r, lo, hi)``: the pieces of row ``r`` for its samples [lo, hi) (absolute
+    indices), as (m_begin, m_end, coeff, dt0, step, ref_int, ref_frac) with ``m`` counted from
+    ``row_edges[r]``.
+    """
+    row_edges = np.asarray(row_edges, dtype=np.int64)
+    r0, r1 = piece_rows(row_edges, c0, c1)
+    slots, begins, ends = [], [], []
+    for r in range(r0, r1):
+        lo, hi = max(c0, int(row_edges[r])), min(c1, int(row_edges[r + 1]))
+        if hi <= lo:
+            continue
+        n_ref = int(row_edges[r])
+        starts, ks, prev = [], [], None
+        for (m0, m1, coeff, dt0, step, ref_int, ref_frac) in row_pieces(r, lo, hi):   # (they tile [lo, hi))
+            for a in range(m0, m1, PIECE):
+                m = np.arange(a, min(m1, a + PIECE), dtype=np.int64)
+                k = polynomial_bins(coeff, dt0, step, ref_int, ref_frac, m, n_phase)
+                first = np.ones(1, bool) if prev is None else k[:1] != prev
+                new = np.concatenate((first, k[1:] != k[:-1]))
+                starts.append(m[new] + n_ref)
+                ks.append(k[new])
+                prev = k[-1]
+        b = np.concatenate(starts)
+        slots.append((r - r0) * n_phase + np.concatenate(ks) % n_phase)
+        begins.append(b)
+        ends.append(np.concatenate((b[1:], [hi])).astype(np.int64))
+    n_row = r1 - r0
+    if not slots:
+        z = np.zeros(0, np.int64)
+        return r0, n_row, np.zeros(n_row * n_phase + 1, np.int64), z, z, np.zeros(n_row * n_phase, np.int64)
+    return (r0, n_row) + _csr(np.concatenate(slots), np.concatenate(begins), np.concatenate(ends),
+                              n_row * n_phase, c0)
+
+
+def plan_pieces(row_edges, row_pieces, n_phase, c0, c1):
+    """What the table kernel (`~baseband_tasks_amd.hip.phase_runs`) needs for the chunk [c0, c1):
+    the pieces of its rows with sample indices relative to c0, and per row the grid of cycles its
+    bins span, from `polynomial_bins` at the first and last sample of each row in the chunk.
+
+    Returns (first row, number of rows, plan); plan is None if no row meets the chunk.
+    """
+    row_edges = np.asarray(row_edges, dtype=np.int64)
+    r0, r1 = piece_rows(row_edges, c0, c1)
+    lo, m0, row, dt0, step, ref_int, ref_frac, coeff = [], [], [], [], [], [], [], []
+    k0, n_cycle, run_cap = [], [], 0
+    for r in range(r0, r1):
+        a, b = max(c0, int(row_edges[r])), min(c1, int(row_edges[r + 1]))
+        if b <= a:
+            k0.append(0)
+            n_cycle.append(0)
+            continue
+        n_ref = int(row_edges[r])
+        pieces = row_pieces(r, a, b)
+        for (pa, pb, c, d0, st, ri, rf) in pieces:
+            lo.append(pa + n_ref - c0)
+            m0.append(pa)
+            row.append(r - r0)
+            dt0.append(d0)
+            step.append(st)
+            ref_int.append(ri)
+            ref_frac.append(rf)
+            coeff.append(np.asarray(c, dtype=float))
+        first, last = pieces[0], pieces[-1]
+        k_first = int(polynomial_bins(first[2], first[3], first[4], first[5], first[6], np.array([first[0]]), n_phase)[0])
+        k_last = int(polynomial_bins(last[2], last[3], last[4], last[5], last[6], np.array([last[1] - 1]), n_phase)[0])
+        if k_last < k_first:
+            raise ValueError("phase must increase with time")
+        base = (k_first // n_phase) * n_phase
+        k0.append(base)
+        n_cycle.append((k_last - base) // n_phase + 1)
+        run_cap += min(b - a, k_last - k_first + 1)
+    if not lo:
+        return r0, r1 - r0, None
+    width = max(len(c) for c in coeff)
+    plan = dict(lo=np.array(lo + [min(c1, int(row_edges[r1])) - c0], np.int64), m0=np.array(m0, np.int64),
+                row=np.array(row, np.int64), dt0=np.array(dt0, float), step=np.array(step, float),
+                ref_int=np.array(ref_int, float), ref_frac=np.array(ref_frac, float),
+                coeff=np.array([np.concatenate((c, np.zeros(width - len(c)))) for c in coeff], float),
+                k0=np.array(k0, np.int64), n_cycle=np.array(n_cycle, np.int64), run_cap=run_cap)
+    return r0, r1 - r0, plan
 
 
 def contiguous_table(edges, c0, c1):

@@ -95,6 +95,9 @@ SIGNATURES = {
     'bbt_pfb_execute': [_vp, _vp, _vp, _i64, _vp],
     'bbt_detect_integrate': [_vp, _vp, _i64, _i64, _i64, _int, _int, _vp],
     'bbt_fold_runs': [_vp, _vp, _i64, _i64, _int, _vp, _vp, _vp, _i64, _vp, _int, _vp, _i64, _vp],
+    'bbt_phase_runs_work': [_i64, _i64, _i64, _pi64],
+    'bbt_phase_runs': [_vp, _i64, _int, _i64, _i64, _i64, _vp, _i64, _i64, _i64, _i64, _i64, _vp, _vp, _vp, _vp,
+                       _vp, _i64, _pi64, _vp],
     'bbt_shift_plan_create': [_pvp, _int, _int, _pi32],
     'bbt_shift_plan_destroy': [_vp],
     'bbt_shift_execute': [_vp, _vp, _vp, _i64, _vp],
@@ -125,7 +128,7 @@ SIGNATURES = {
 }
 
 #: oldest libbbt_hip.so whose entry points and argument meanings this binding assumes
-MIN_LIB_VERSION = 155
+MIN_LIB_VERSION = 156
 
 _lib = None
 _lock = threading.Lock()
@@ -746,15 +749,73 @@ def fold_runs(in_dev, out_dev, n_elem, mode, slot_ptr, run_begin, run_end, scale
     n_runs = len(run_begin)
     table = DeviceArray.from_host(np.concatenate([slot_ptr, run_begin, run_end]))
     tptr = table.ptr
+    return _fold_launch(in_dev, out_dev, n_in, n_elem, mode, tptr, tptr + 8 * (n_slot + 1),
+                        tptr + 8 * (n_slot + 1 + n_runs), n_slot, n_out_f, scale, accumulate)
+
+
+def _fold_launch(in_dev, out_dev, n_in, n_elem, mode, sp_ptr, rb_ptr, re_ptr, n_slot, n_out_f, scale, accumulate):
     sc = DeviceArray.from_host(np.ascontiguousarray(scale, dtype=np.float32)) if scale is not None else None
     work_floats = min(FOLD_MAX_SPLIT * n_slot * n_out_f, 1 << 24)
     work = DeviceArray((work_floats,), np.float32) if work_floats >= 2 * n_slot * n_out_f else None
     check(lib().bbt_fold_runs(in_dev.ptr_to_read(), out_dev.ptr, int(n_in), int(n_elem), int(mode),
-                              tptr, tptr + 8 * (n_slot + 1), tptr + 8 * (n_slot + 1 + n_runs),
+                              sp_ptr, rb_ptr, re_ptr,
                               int(n_slot), sc.ptr if sc is not None else None, int(bool(accumulate)),
                               work.ptr if work is not None else None,
                               int(work_floats) if work is not None else 0, _stream))
     return out_dev
+
+
+def fold_runs_device(in_dev, out_dev, n_elem, mode, slot_ptr, run_begin, run_end, scale=None,
+                     accumulate=False):
+    """`fold_runs` with the table already in HBM (int64 `DeviceArray`s, as `phase_runs` makes
+    them; the kernel clips runs to the input)."""
+    n_slot = slot_ptr.shape[0] - 1
+    if n_slot <= 0:
+        return out_dev
+    n_in = in_dev.shape[0] if in_dev.shape else 0
+    n_out_f = 2 * int(n_elem) if mode == 1 else int(n_elem)
+    if out_dev.size * (2 if out_dev.dtype.kind == 'c' else 1) != n_slot * n_out_f:
+        raise ValueError("fold_runs: output is not n_slot rows of the mode's width")
+    if in_dev.size * (2 if in_dev.dtype.kind == 'c' else 1) != n_in * int(n_elem) * (1 if mode == 2 else 2):
+        raise ValueError("fold_runs: input is not n_in samples of n_elem elements")
+    return _fold_launch(in_dev, out_dev, n_in, n_elem, mode, slot_ptr.ptr_to_read(), run_begin.ptr_to_read(),
+                        run_end.ptr_to_read(), n_slot, n_out_f, scale, accumulate)
+
+
+def phase_runs(plan, n_phase, slot0=0, n_slot=None):
+    """Run table of a chunk from polynomial phases, made on the GPU (bbt_phase_runs).
+
+    ``plan``: what `~baseband_tasks_amd.fold_table.plan_pieces` returns.  Returns (slot_ptr,
+    run_begin, run_end) as int64 `DeviceArray`s -- slot_ptr has ``n_slot + 1`` entries, the
+    chunk's rows starting at slot ``slot0``; run_begin / run_end hold ``n_run`` runs -- then
+    ``n_run`` and the samples per slot of the chunk's rows (host int64)."""
+    n_piece, n_row = len(plan['row']), len(plan['k0'])
+    n_chunk_slot = n_row * int(n_phase)
+    n_slot = n_chunk_slot + slot0 if n_slot is None else int(n_slot)
+    n_coeff = plan['coeff'].shape[1]
+    words = np.concatenate([plan['lo'].astype(np.int64).view(np.float64), plan['m0'].astype(np.int64).view(np.float64),
+                            plan['row'].astype(np.int64).view(np.float64), plan['dt0'], plan['step'], plan['ref_int'],
+                            plan['ref_frac'], plan['coeff'].ravel()]).astype(np.float64, copy=False)
+    pieces = DeviceArray.from_host(words)
+    cell0 = np.concatenate(([0], np.cumsum(plan['n_cycle'] * int(n_phase))))
+    n_cell = int(cell0[-1])
+    rows = DeviceArray.from_host(np.concatenate([plan['k0'], plan['n_cycle'], cell0[:-1]]).astype(np.int64))
+    s_begin, s_end, run_cap = int(plan['lo'][0]), int(plan['lo'][-1]), int(plan['run_cap'])
+    need = C.c_int64()
+    check(lib().bbt_phase_runs_work(s_end - s_begin, n_cell, run_cap, C.byref(need)))
+    work = DeviceArray((need.value // 8 + 2,), np.int64)
+    slot_ptr = DeviceArray((n_slot + 1,), np.int64)
+    runs = DeviceArray((2, run_cap), np.int64)
+    counts = DeviceArray((n_chunk_slot,), np.int64)
+    info = (C.c_int64 * 2)()
+    check(lib().bbt_phase_runs(pieces.ptr, n_piece, n_coeff, s_begin, s_end, int(n_phase), rows.ptr, n_row, n_cell,
+                               int(slot0), n_slot, run_cap, slot_ptr.ptr, runs.ptr, runs.ptr + 8 * run_cap,
+                               counts.ptr, work.ptr, work.nbytes, info, _stream))
+    if info[1] != 0:
+        raise ValueError("phase_runs: the phase does not increase with time (or the plan does not "
+                         f"describe it): status {info[1]}, {info[0]} runs for a capacity of {run_cap}")
+    n_run = int(info[0])
+    return slot_ptr, runs[0:1].reshape(run_cap)[:n_run], runs[1:2].reshape(run_cap)[:n_run], n_run, counts.to_host()
 
 
 def detect_power_axis(in_dev, out_dev, n_out, step, outer, inner, average=True):

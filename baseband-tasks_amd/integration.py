@@ -2,6 +2,7 @@
 baseband_tasks/integration.py: `Integrate` 52-303, `Fold` 306-395, `PulseStack`
 398-478)."""
 import operator
+import os
 import warnings
 
 import numpy as np
@@ -10,7 +11,8 @@ from . import hip
 from . import units as u
 from .base import BaseTaskBase, _stream_rate, _stream_start
 from .device_task import DeviceTaskMixin, fetch_device
-from .fold_table import contiguous_table, fold_table, phase_difference, sample_times
+from .fold_table import (contiguous_table, fold_table, phase_difference, piece_table, plan_pieces,
+                         sample_times)
 from .functions import _DetectTask
 from .units import Time
 
@@ -220,10 +222,12 @@ class _RunTableTask(DeviceTaskMixin, BaseTaskBase):
         while True:
             c1 = min(in1, c0 + per)
             s0, sp, rb, re, cnt = table(c0, c1)
-            full = np.empty(n_slot + 1, np.int64)
-            full[:s0 + 1] = 0
-            full[s0:s0 + len(sp)] = sp
-            full[s0 + len(sp):] = sp[-1]
+            on_device = isinstance(sp, hip.DeviceArray)        # (made there; slot_ptr is complete)
+            if not on_device:
+                full = np.empty(n_slot + 1, np.int64)
+                full[:s0 + 1] = 0
+                full[s0:s0 + len(sp)] = sp
+                full[s0 + len(sp):] = sp[-1]
             counts[s0:s0 + len(cnt)] += cnt
             last = c1 >= in1
             scale = None
@@ -232,7 +236,10 @@ class _RunTableTask(DeviceTaskMixin, BaseTaskBase):
                     scale = np.where(counts > 0, 1. / np.maximum(counts, 1), np.nan).astype(np.float32)
             if len(rb) or scale is not None:
                 x = fetch_device(src, c0, c1 - c0) if c1 > c0 else hip.DeviceArray((1,) + tuple(src.shape[1:]), src.dtype)
-                hip.fold_runs(x, rows, n_elem, mode, full, rb, re, scale=scale, accumulate=True)
+                if on_device:
+                    hip.fold_runs_device(x, rows, n_elem, mode, sp, rb, re, scale=scale, accumulate=True)
+                else:
+                    hip.fold_runs(x, rows, n_elem, mode, full, rb, re, scale=scale, accumulate=True)
             if last:
                 return counts
             c0 = c1
@@ -270,6 +277,9 @@ class Fold(_RunTableTask):
         array-valued `~baseband_tasks_amd.units.Time`, returns cycles (a float array,
         anything with ``to_value('cycle')``, or a two-part phase with ``.int`` and
         ``.frac``).  ``lambda t: F0 * (t - t0)`` works.  Must increase with time.
+        A phase that offers polynomial pieces (``fold_pieces``, as
+        `~baseband_tasks_amd.phases.PolycoPhase` does) has its run tables made on the
+        GPU; see `table_route`.
     step : int or float, optional
         Input samples (int) or seconds (float) per profile; default: everything.
     start : int or `~baseband_tasks_amd.units.Time`
@@ -343,11 +353,47 @@ class Fold(_RunTableTask):
             return lambda n: phase(times(n))
         return row
 
+    #: where the run tables of a phase that offers polynomial pieces (``fold_pieces``, see
+    #: INTEGRATION.md) are made: 'device' (the table kernel), 'host' (NumPy, every sample), or
+    #: None: the environment's BBT_FOLD_TABLE, else 'device'.  Both give the same table.
+    table_route = None
+
+    def _route(self):
+        route = self.table_route or os.environ.get('BBT_FOLD_TABLE', '') or 'device'
+        if route not in ('device', 'host'):
+            raise ValueError(f"table route {route!r}: must be 'device' or 'host'")
+        return route
+
+    def _row_pieces(self, edges):
+        ih, rate = self.ih, _stream_rate(self.ih)
+        fold_pieces = self.phase.fold_pieces
+
+        def pieces(r, lo, hi):
+            n_ref = int(edges[r])
+            t_ref = ih._tell_time(n_ref) if hasattr(ih, '_tell_time') else _stream_start(ih) + n_ref / rate
+            return fold_pieces(t_ref, rate, lo - n_ref, hi - n_ref)
+        return pieces
+
     def _tables(self, a, b):
         """Row edges and the chunk table function for rows [a, b)."""
         edges = self._get_offsets(np.arange(a, b + 1))
-        row_phase = self._row_phase(edges)
         n_phase = self.n_phase
+        if hasattr(self.phase, 'fold_pieces'):
+            row_pieces = self._row_pieces(edges)
+            n_slot = (b - a) * n_phase
+
+            def host_table(c0, c1):
+                r0, n_row, sp, rb, re, cnt = piece_table(edges, row_pieces, n_phase, c0, c1)
+                return r0 * n_phase, sp, rb, re, cnt
+
+            def device_table(c0, c1):
+                r0, n_row, plan = plan_pieces(edges, row_pieces, n_phase, c0, c1)
+                if plan is None:
+                    return host_table(c0, c1)              # (no samples: an empty table)
+                sp, rb, re, n_run, cnt = hip.phase_runs(plan, n_phase, r0 * n_phase, n_slot)
+                return r0 * n_phase, sp, rb, re, cnt
+            return edges, (device_table if self._route() == 'device' else host_table)
+        row_phase = self._row_phase(edges)
 
         def table(c0, c1):
             r0, n_row, sp, rb, re, cnt = fold_table(edges, row_phase, n_phase, c0, c1)
@@ -361,7 +407,7 @@ class Fold(_RunTableTask):
 
     def _counts(self, a, b):
         edges, table = self._tables(a, b)
-        _, sp, rb, re, cnt = table(int(edges[0]), int(edges[-1]))
+        _, sp, rb, re, cnt = table(int(edges[0]), int(edges[-1]))      # (on either route, counts on the host)
         out = np.zeros((b - a) * self.n_phase, np.int64)
         out[:len(cnt)] = cnt
         return out.reshape(b - a, self.n_phase)

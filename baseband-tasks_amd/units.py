@@ -23,6 +23,8 @@ s = 1.0
 ms = 1.0e-3
 us = 1.0e-6
 ns = 1.0e-9
+minute = 60.0
+day = 86400.0
 one = 1.0
 cycle = 1.0
 

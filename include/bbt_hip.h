@@ -359,6 +359,36 @@ int bbt_fold_runs(const void* in_dev, void* out_dev, int64_t n_in, int64_t n_ele
                   const int64_t* run_end_dev, int64_t n_slot, const float* scale_dev, int accumulate,
                   void* work_dev, int64_t work_floats, bbt_stream stream);
 
+/* Run table for bbt_fold_runs made on the device, for samples whose pulse phase is given in
+ * polynomial pieces (the host twin, and the definition of the bins, is
+ * baseband_tasks_amd.fold_table.polynomial_bins / piece_table).
+ *   pieces_dev  8-byte words: lo[n_piece + 1] (int64, the samples [lo[p], lo[p+1]) of the chunk
+ *               belong to piece p; lo[0] = s_begin, lo[n_piece] = s_end), m0[n_piece] (int64,
+ *               offset of sample lo[p] from the start of its row), row[n_piece] (int64, output
+ *               row counted from the first row of the chunk), dt0, step, ref_int, ref_frac
+ *               [n_piece each, float64], coeff[n_piece][n_coeff] (float64): sample i of piece p has
+ *               x = dt0 + (m0 + i - lo) * step, phase = ref_int + ref_frac + sum_j coeff[j] x^j and
+ *               the unwrapped bin k = floor(phase) * n_phase + int(frac(phase) * n_phase), in
+ *               float64 without fused multiply-adds.
+ *   rows_dev    int64: k0[n_row] (a multiple of n_phase not above the row's first k),
+ *               n_cycle[n_row] (how many times n_phase bins the row spans from k0),
+ *               cell0[n_row] (running sum of n_phase * n_cycle); n_cell their total.
+ *   outputs     slot_ptr[n_slot + 1] with row r, bin b at slot slot0 + r * n_phase + b;
+ *               run_begin / run_end [run_cap] (the first info[0] are the runs, slot by slot, in
+ *               time order within a slot); counts[n_row * n_phase] samples per slot of the chunk.
+ *   info        host int64[2]: the number of runs, and a status: 0, or nonzero if the runs
+ *               exceed run_cap or a bin falls outside its row's cycles (a phase that decreases);
+ *               the table is then empty.  The call waits for the stream.
+ *   work        device scratch of bbt_phase_runs_work(s_end - s_begin, n_cell, run_cap) bytes.
+ * The table depends on the arguments only (scans, one cell per run); the counts are integer
+ * sums. */
+int bbt_phase_runs_work(int64_t n_samples, int64_t n_cell, int64_t run_cap, int64_t* bytes);
+int bbt_phase_runs(const void* pieces_dev, int64_t n_piece, int n_coeff, int64_t s_begin, int64_t s_end,
+                   int64_t n_phase, const int64_t* rows_dev, int64_t n_row, int64_t n_cell, int64_t slot0,
+                   int64_t n_slot, int64_t run_cap, int64_t* slot_ptr_dev, int64_t* run_begin_dev,
+                   int64_t* run_end_dev, int64_t* counts_dev, void* work_dev, int64_t work_bytes,
+                   int64_t* info, bbt_stream stream);
+
 /* ---- real streams to complex baseband: Real2Complex ---------------------------
  * Replaces Real2Complex.task (conversion.py:77-101): every frame of 2 M real samples of each of
  * the S streams (fft, one-sided spectrum, ifft, times exp(-i pi n / 2), every second sample) gives
