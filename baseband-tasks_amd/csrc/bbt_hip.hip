@@ -28,10 +28,11 @@
 #include "phase_kernels.hpp"
 #include "r2c_kernels.hpp"
 #include "gather_kernels.hpp"
+#include "pack_kernels.hpp"
 
 using namespace bbt;
 
-#define BBT_VERSION 156
+#define BBT_VERSION 157
 
 // ---------------------------------------------------------------------------
 // errors
@@ -3931,6 +3932,84 @@ extern "C" int bbt_unpack_masked(const void* raw_dev, void* out_dev, int64_t n_f
 #undef BBT_UNPACK
     HIP_TRY(hipGetLastError());
     return 0;
+}
+
+// ---------------------------------------------------------------------------
+// float32 / complex64 -> coded words and binary16 (pack_kernels.hpp): the encoders of the compact
+// HDF5 payloads.  Decoding coded words is bbt_unpack with header_bytes = 0.
+#define BBT_PACK_MAX (1ll << 40)
+static bool aligned16(const void* a, const void* b) {
+    return (((uintptr_t)a | (uintptr_t)b) & 15u) == 0;
+}
+extern "C" int bbt_pack(const void* in_dev, void* out_dev, int64_t n_comp, int bits, int code,
+                        bbt_stream stream) {
+    ARG_TRY(in_dev && out_dev, "bbt_pack: null argument");
+    ARG_TRY(code == 0, "bbt_pack: code must be 0 (VDIF levels)");
+    ARG_TRY(bits == 1 || bits == 2 || bits == 4 || bits == 8 || bits == 16,
+            "bbt_pack: %d bits per component are not supported", bits);
+    ARG_TRY(n_comp >= 0 && n_comp <= BBT_PACK_MAX, "bbt_pack: %lld components (0 .. 2^40)", (long long)n_comp);
+    ARG_TRY((((uintptr_t)in_dev | (uintptr_t)out_dev) & 3u) == 0, "bbt_pack: pointers must be 4-byte aligned");
+    if (n_comp == 0) return 0;
+    const long long per = 32 / bits, n_words = (n_comp + per - 1) / per;
+    const bool vec = aligned16(in_dev, out_dev);
+#define BBT_PACK_V(B_, W_, V_)                                                                          \
+    hipLaunchKernelGGL((k_pack<B_, W_, V_>),                                                            \
+                       dim3((unsigned)((n_words + (long long)BBT_PACK_THREADS * W_ - 1) /              \
+                                       ((long long)BBT_PACK_THREADS * W_))),                            \
+                       dim3(BBT_PACK_THREADS), 0, (hipStream_t)stream, (const float*)in_dev,            \
+                       (unsigned*)out_dev, (long long)n_comp, n_words)
+#define BBT_PACK(B_, W_)                        \
+    do {                                        \
+        if (vec) BBT_PACK_V(B_, W_, true);      \
+        else BBT_PACK_V(B_, W_, false);         \
+    } while (0)
+    switch (bits) {                 // (words per thread: see pack_kernels.hpp)
+        case 1: BBT_PACK(1, 1); break;
+        case 2: BBT_PACK(2, 1); break;
+        case 4: BBT_PACK(4, 2); break;
+        case 8: BBT_PACK(8, 4); break;
+        default: BBT_PACK(16, 4); break;
+    }
+#undef BBT_PACK
+#undef BBT_PACK_V
+    HIP_TRY(hipGetLastError());
+    return 0;
+}
+
+static int half_launch(const void* in_dev, void* out_dev, int64_t n, bool to_half, bbt_stream stream,
+                       const char* who) {
+    ARG_TRY(in_dev && out_dev, "%s: null argument", who);
+    ARG_TRY(n >= 0 && n <= BBT_PACK_MAX, "%s: %lld values (0 .. 2^40)", who, (long long)n);
+    const uintptr_t f = (uintptr_t)(to_half ? in_dev : (const void*)out_dev);
+    const uintptr_t h = (uintptr_t)(to_half ? (const void*)out_dev : in_dev);
+    ARG_TRY((f & 3u) == 0 && (h & 1u) == 0, "%s: pointers must be aligned to their elements", who);
+    if (n == 0) return 0;
+    const long long per_block = (long long)BBT_PACK_THREADS * BBT_HALF_PER;
+    const dim3 grid((unsigned)((n + per_block - 1) / per_block));
+    const bool vec = aligned16(in_dev, out_dev);
+    if (to_half) {
+        if (vec)
+            hipLaunchKernelGGL((k_to_half<true>), grid, dim3(BBT_PACK_THREADS), 0, (hipStream_t)stream,
+                               (const float*)in_dev, (unsigned short*)out_dev, (long long)n);
+        else
+            hipLaunchKernelGGL((k_to_half<false>), grid, dim3(BBT_PACK_THREADS), 0, (hipStream_t)stream,
+                               (const float*)in_dev, (unsigned short*)out_dev, (long long)n);
+    } else {
+        if (vec)
+            hipLaunchKernelGGL((k_from_half<true>), grid, dim3(BBT_PACK_THREADS), 0, (hipStream_t)stream,
+                               (const unsigned short*)in_dev, (float*)out_dev, (long long)n);
+        else
+            hipLaunchKernelGGL((k_from_half<false>), grid, dim3(BBT_PACK_THREADS), 0, (hipStream_t)stream,
+                               (const unsigned short*)in_dev, (float*)out_dev, (long long)n);
+    }
+    HIP_TRY(hipGetLastError());
+    return 0;
+}
+extern "C" int bbt_to_half(const void* in_dev, void* out_dev, int64_t n, bbt_stream stream) {
+    return half_launch(in_dev, out_dev, n, true, stream, "bbt_to_half");
+}
+extern "C" int bbt_from_half(const void* in_dev, void* out_dev, int64_t n, bbt_stream stream) {
+    return half_launch(in_dev, out_dev, n, false, stream, "bbt_from_half");
 }
 
 // ---------------------------------------------------------------------------

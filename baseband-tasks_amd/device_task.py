@@ -339,6 +339,10 @@ class DeviceTaskMixin:
             target = out[done:done + n] if isinstance(out, np.ndarray) else None
             if target is not None and target.flags.c_contiguous and target.dtype == self._device_dtype:
                 piece.to_host(target)
+            elif getattr(out, 'accepts_device', False):
+                # (an ``out`` that says so -- the HDF5 writer -- gets the device piece itself, a view
+                # of this task's cache it consumes at once: it encodes in HBM and copies down less)
+                out[done:done + n] = piece
             else:
                 out[done:done + n] = piece.to_host()
             done += n

@@ -13,7 +13,7 @@ import numpy as np
 
 __all__ = ['HipError', 'HipLibraryMissing', 'lib', 'available', 'DeviceArray',
            'OsmPlan', 'ChanPlan', 'PfbPlan', 'set_stream', 'get_stream',
-           'synchronize', 'Event', 'device_count', 'set_device']
+           'synchronize', 'Event', 'device_count', 'set_device', 'pack', 'to_half', 'from_half']
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 # BBT_HIP_LIB points at another build of the same library (the sanitizer build
@@ -120,6 +120,9 @@ SIGNATURES = {
     'bbt_scale_streams': [_vp, _vp, _i64, _int, _vp, _vp],
     'bbt_unpack': [_vp, _vp, _i64, _int, _int, _int, _int, _int, _int, _int, _vp],
     'bbt_unpack_masked': [_vp, _vp, _i64, _int, _int, _int, _int, _int, _int, _int, _vp, _vp],
+    'bbt_pack': [_vp, _vp, _i64, _int, _int, _vp],
+    'bbt_to_half': [_vp, _vp, _i64, _vp],
+    'bbt_from_half': [_vp, _vp, _i64, _vp],
     'bbt_comm_unique_id': [_vp, _sz],
     'bbt_comm_init': [_pvp, _int, _int, _vp, _sz],
     'bbt_comm_destroy': [_vp],
@@ -128,7 +131,7 @@ SIGNATURES = {
 }
 
 #: oldest libbbt_hip.so whose entry points and argument meanings this binding assumes
-MIN_LIB_VERSION = 156
+MIN_LIB_VERSION = 157
 
 _lib = None
 _lock = threading.Lock()
@@ -881,6 +884,89 @@ def square_real(x, out):
 def scale_streams(x, out, n_samples, n_elem, factor_dev):
     """out[i, e] = x[i, e] * factor[e] (complex64)."""
     check(lib().bbt_scale_streams(x.ptr_to_read(), out.ptr, int(n_samples), int(n_elem), factor_dev.ptr, _stream))
+
+
+#: widths `pack` encodes (and `bbt_unpack` code 0 decodes)
+PACK_BITS = (1, 2, 4, 8, 16)
+
+
+def _components(x, who):
+    """Number of float32 components of a float32 / complex64 `DeviceArray`."""
+    if not isinstance(x, DeviceArray):
+        raise TypeError(f"{who}: the input must be a DeviceArray, not {type(x).__name__}")
+    if x.dtype not in (np.dtype(np.float32), np.dtype(np.complex64)):
+        raise TypeError(f"{who}: the input must be float32 or complex64, not {x.dtype}")
+    return x.size * (2 if x.dtype.kind == 'c' else 1)
+
+
+def pack(x, bits, out=None):
+    """Encode a float32 / complex64 `DeviceArray` (complex: re, im adjacent) into VDIF-coded
+    little-endian 32-bit words, the first component in the least significant bits (bbt_pack in
+    include/bbt_hip.h; the codes of `ingest.encode_vdif_frames`).  Returns a uint32 `DeviceArray`
+    of ``ceil(components * bits / 32)`` words (``out`` if given)."""
+    n_comp = _components(x, 'pack')
+    if isinstance(bits, bool) or not isinstance(bits, (int, np.integer)) or int(bits) not in PACK_BITS:
+        raise ValueError(f"pack: bits must be one of {PACK_BITS}, not {bits!r}")
+    bits = int(bits)
+    n_words = -(-n_comp * bits // 32)
+    if out is None:
+        out = DeviceArray((n_words,), np.uint32)
+    elif not isinstance(out, DeviceArray):
+        raise TypeError(f"pack: out must be a DeviceArray, not {type(out).__name__}")
+    elif out.dtype != np.dtype(np.uint32):
+        raise TypeError(f"pack: out must be uint32, not {out.dtype}")
+    elif out.size != n_words:
+        raise ValueError(f"pack: out holds {out.size} words; {n_comp} components at {bits} bits make {n_words}")
+    if n_comp:
+        check(lib().bbt_pack(x.ptr_to_read(), out.ptr, n_comp, bits, 0, _stream))
+    return out
+
+
+def to_half(x, out=None):
+    """float32 / complex64 `DeviceArray` -> IEEE binary16 components (bbt_to_half): a float16
+    `DeviceArray` of ``x``'s shape, with a last axis of 2 (re, im) added for complex input."""
+    n = _components(x, 'to_half')
+    shape = x.shape + ((2,) if x.dtype.kind == 'c' else ())
+    if out is None:
+        out = DeviceArray(shape, np.float16)
+    elif not isinstance(out, DeviceArray):
+        raise TypeError(f"to_half: out must be a DeviceArray, not {type(out).__name__}")
+    elif out.dtype != np.dtype(np.float16):
+        raise TypeError(f"to_half: out must be float16, not {out.dtype}")
+    elif out.size != n:
+        raise ValueError(f"to_half: out holds {out.size} values for {n} components")
+    if n:
+        check(lib().bbt_to_half(x.ptr_to_read(), out.ptr, n, _stream))
+    return out
+
+
+def from_half(h, dtype=np.float32, out=None):
+    """float16 `DeviceArray` -> float32, or complex64 from (re, im) pairs along the last axis
+    (bbt_from_half; exact)."""
+    if not isinstance(h, DeviceArray):
+        raise TypeError(f"from_half: the input must be a DeviceArray, not {type(h).__name__}")
+    if h.dtype != np.dtype(np.float16):
+        raise TypeError(f"from_half: the input must be float16, not {h.dtype}")
+    dtype = np.dtype(dtype)
+    if dtype not in (np.dtype(np.float32), np.dtype(np.complex64)):
+        raise TypeError(f"from_half: dtype must be float32 or complex64, not {dtype}")
+    if dtype.kind == 'c':
+        if not h.shape or h.shape[-1] != 2:
+            raise ValueError(f"from_half: complex64 needs a last axis of 2 (re, im), not shape {h.shape}")
+        shape = h.shape[:-1]
+    else:
+        shape = h.shape
+    if out is None:
+        out = DeviceArray(shape, dtype)
+    elif not isinstance(out, DeviceArray):
+        raise TypeError(f"from_half: out must be a DeviceArray, not {type(out).__name__}")
+    elif out.dtype != dtype:
+        raise TypeError(f"from_half: out must be {dtype}, not {out.dtype}")
+    elif out.size * (2 if dtype.kind == 'c' else 1) != h.size:
+        raise ValueError(f"from_half: out holds {out.size} {dtype} for {h.size} halves")
+    if h.size:
+        check(lib().bbt_from_half(h.ptr_to_read(), out.ptr, h.size, _stream))
+    return out
 
 
 class _Plan:

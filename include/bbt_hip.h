@@ -559,6 +559,31 @@ int bbt_unpack_masked(const void* raw_dev, void* out_dev, int64_t n_frames, int 
                       int header_bytes, int bits, int samples_per_frame, int n_thread, int n_elem,
                       int code, const void* valid_dev, bbt_stream stream);
 
+/* ---- compact payloads of the HDF5 intermediate format ---------------------
+ * The encoders behind `hdf5.HDF5StreamWriter` (reference io/hdf5/payload.py:
+ * 121-178): a stream is encoded in HBM and leaves the device at its stored
+ * width.  Decoding coded words is bbt_unpack with header_bytes = 0.
+ *   bbt_pack       n_comp float32 components (complex: re, im adjacent) ->
+ *                  ceil(n_comp * bits / 32) little-endian 32-bit words, the
+ *                  first component in the least significant bits, a last
+ *                  partial word zero in its unused bits: the inverse of
+ *                  bbt_unpack code 0.  bits 1, 2, 4, 8, 16; code 0 only.
+ *                  1 bit x > 0; 2 bits the number of thresholds -2, 0, 2
+ *                  strictly below x; 4 bits clip(rint(x * 2.95 + 8), 0, 15);
+ *                  8 bits clip(rint(x * 35.5 + 127.5), 0, 255); 16 bits
+ *                  clip(rint(x + 32768), 0, 65535) -- product and sum rounded
+ *                  to float32 separately, rint half to even, +-inf to the end
+ *                  codes, NaN to code 0.
+ *   bbt_to_half    n float32 -> IEEE binary16 (round to nearest even,
+ *                  subnormals kept, overflow to +-inf, NaN stays NaN)
+ *   bbt_from_half  n binary16 -> float32 (exact)
+ * n_comp, n <= 2^40.  Pointers aligned to their elements; 16-byte aligned
+ * pointers take the vector kernels. */
+int bbt_pack(const void* in_dev, void* out_dev, int64_t n_comp, int bits, int code,
+             bbt_stream stream);
+int bbt_to_half(const void* in_dev, void* out_dev, int64_t n, bbt_stream stream);
+int bbt_from_half(const void* in_dev, void* out_dev, int64_t n, bbt_stream stream);
+
 /* ---- multi-GPU: one process per GPU, RCCL over xGMI ----------------------
  * The reference has no distributed code; these are what SURVEY 8(b)/(e) ask a
  * replacement to export for the way this path shards (independent overlap-save
