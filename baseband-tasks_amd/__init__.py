@@ -29,5 +29,6 @@ from .ingest import RawFrameStream, open_vdif, open_dada
 from . import phases
 from . import hip
 from . import hdf5
+from . import psrfits
 
 __version__ = '0.1.0'

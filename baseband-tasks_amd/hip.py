@@ -13,7 +13,8 @@ import numpy as np
 
 __all__ = ['HipError', 'HipLibraryMissing', 'lib', 'available', 'DeviceArray',
            'OsmPlan', 'ChanPlan', 'PfbPlan', 'set_stream', 'get_stream',
-           'synchronize', 'Event', 'device_count', 'set_device', 'pack', 'to_half', 'from_half']
+           'synchronize', 'Event', 'device_count', 'set_device', 'pack', 'to_half', 'from_half',
+           'psrfits_encode', 'psrfits_decode']
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 # BBT_HIP_LIB points at another build of the same library (the sanitizer build
@@ -123,6 +124,8 @@ SIGNATURES = {
     'bbt_pack': [_vp, _vp, _i64, _int, _int, _vp],
     'bbt_to_half': [_vp, _vp, _i64, _vp],
     'bbt_from_half': [_vp, _vp, _i64, _vp],
+    'bbt_psrfits_encode': [_vp, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _i64, _vp],
+    'bbt_psrfits_decode': [_vp, _vp, _vp, _vp, C.c_float, _vp, _i64, _i64, _i64, _i64, _vp],
     'bbt_comm_unique_id': [_vp, _sz],
     'bbt_comm_init': [_pvp, _int, _int, _vp, _sz],
     'bbt_comm_destroy': [_vp],
@@ -131,7 +134,7 @@ SIGNATURES = {
 }
 
 #: oldest libbbt_hip.so whose entry points and argument meanings this binding assumes
-MIN_LIB_VERSION = 157
+MIN_LIB_VERSION = 158
 
 _lib = None
 _lock = threading.Lock()
@@ -966,6 +969,79 @@ def from_half(h, dtype=np.float32, out=None):
         raise ValueError(f"from_half: out holds {out.size} {dtype} for {h.size} halves")
     if h.size:
         check(lib().bbt_from_half(h.ptr_to_read(), out.ptr, h.size, _stream))
+    return out
+
+
+#: the stored type of a fold-mode profile: int16, big-endian
+PSRFITS_CODE = np.dtype('>i2')
+
+
+def _rows_shape(shape, who):
+    """(n_row, n_bin, n_chan, n_pol) of profiles of shape (n_row, n_bin[, n_chan[, n_pol]])."""
+    if not 2 <= len(shape) <= 4:
+        raise ValueError(f"{who}: profiles have shape (row, bin[, chan[, pol]]), not {tuple(shape)}")
+    shape = tuple(shape) + (1,) * (4 - len(shape))
+    if min(shape[1:]) < 1:
+        raise ValueError(f"{who}: an empty axis in {shape}")
+    return shape
+
+
+def psrfits_encode(x):
+    """Code float32 profiles ``(n_row, n_bin[, n_chan[, n_pol]])`` in HBM as the rows of a PSRFITS
+    fold-mode table (bbt_psrfits_encode in include/bbt_hip.h; `psrfits.encode_rows` is the NumPy
+    restatement).  Returns `DeviceArray`s ``(codes, scl, offs, n_finite)``: big-endian int16
+    ``(n_row, n_pol, n_chan, n_bin)``, and float32, float32, int32 ``(n_row, n_pol, n_chan)``."""
+    if not isinstance(x, DeviceArray):
+        raise TypeError(f"psrfits_encode: the input must be a DeviceArray, not {type(x).__name__}")
+    if x.dtype != np.dtype(np.float32):
+        raise TypeError(f"psrfits_encode: the input must be float32, not {x.dtype}")
+    n_row, n_bin, n_chan, n_pol = _rows_shape(x.shape, 'psrfits_encode')
+    codes = DeviceArray((n_row, n_pol, n_chan, n_bin), PSRFITS_CODE)
+    scl = DeviceArray((n_row, n_pol, n_chan), np.float32)
+    offs = DeviceArray((n_row, n_pol, n_chan), np.float32)
+    n_finite = DeviceArray((n_row, n_pol, n_chan), np.int32)
+    if n_row:
+        check(lib().bbt_psrfits_encode(x.ptr_to_read(), codes.ptr, scl.ptr, offs.ptr, n_finite.ptr,
+                                       n_row, n_bin, n_chan, n_pol, _stream))
+    return codes, scl, offs, n_finite
+
+
+def psrfits_decode(codes, scl, offs, wts=None, zero_off=0., out=None):
+    """Decode rows of a PSRFITS fold-mode table in HBM (bbt_psrfits_decode): big-endian int16
+    ``codes (n_row, n_pol, n_chan, n_bin)``, float32 ``scl`` and ``offs (n_row, n_pol, n_chan)``
+    and optional float32 weights ``wts (n_row, n_chan)`` -> float32 ``(n_row, n_bin, n_chan,
+    n_pol)``: ``((float)code - zero_off) * scl + offs``, times the weight (``out`` if given)."""
+    for name, a, dtype in (('codes', codes, PSRFITS_CODE), ('scl', scl, np.float32), ('offs', offs, np.float32),
+                           ('wts', wts, np.float32)):
+        if a is None and name == 'wts':
+            continue
+        if not isinstance(a, DeviceArray):
+            raise TypeError(f"psrfits_decode: {name} must be a DeviceArray, not {type(a).__name__}")
+        if a.dtype != np.dtype(dtype):
+            raise TypeError(f"psrfits_decode: {name} must be {np.dtype(dtype).str}, not {a.dtype.str}")
+    if len(codes.shape) != 4 or min(codes.shape[1:]) < 1:
+        raise ValueError(f"psrfits_decode: codes have shape (row, pol, chan, bin), not {codes.shape}")
+    n_row, n_pol, n_chan, n_bin = codes.shape
+    if scl.size != n_row * n_pol * n_chan or offs.size != scl.size:
+        raise ValueError(f"psrfits_decode: scl and offs hold {scl.size} and {offs.size} values for "
+                         f"{n_row * n_pol * n_chan} profiles")
+    if wts is not None and wts.size != n_row * n_chan:
+        raise ValueError(f"psrfits_decode: wts holds {wts.size} values for {n_row} rows of {n_chan} channels")
+    zero_off = float(zero_off)
+    if zero_off != zero_off:
+        raise ValueError("psrfits_decode: zero_off is not a number")
+    if out is None:
+        out = DeviceArray((n_row, n_bin, n_chan, n_pol), np.float32)
+    elif not isinstance(out, DeviceArray):
+        raise TypeError(f"psrfits_decode: out must be a DeviceArray, not {type(out).__name__}")
+    elif out.dtype != np.dtype(np.float32):
+        raise TypeError(f"psrfits_decode: out must be float32, not {out.dtype}")
+    elif out.size != codes.size:
+        raise ValueError(f"psrfits_decode: out holds {out.size} values for {codes.size} codes")
+    if n_row:
+        check(lib().bbt_psrfits_decode(codes.ptr_to_read(), scl.ptr_to_read(), offs.ptr_to_read(),
+                                       wts.ptr_to_read() if wts is not None else None, zero_off, out.ptr,
+                                       n_row, n_bin, n_chan, n_pol, _stream))
     return out
 
 

@@ -584,6 +584,33 @@ int bbt_pack(const void* in_dev, void* out_dev, int64_t n_comp, int bits, int co
 int bbt_to_half(const void* in_dev, void* out_dev, int64_t n, bbt_stream stream);
 int bbt_from_half(const void* in_dev, void* out_dev, int64_t n, bbt_stream stream);
 
+/* ---- PSRFITS fold-mode rows -------------------------------------------------
+ * The coding behind `psrfits.PSRFITSWriter` / `PSRFITSReader`: the DATA, DAT_SCL
+ * and DAT_OFFS columns of a SUBINT table in PSR mode (the reference reads them
+ * in io/psrfits/hdu.py:457-474; its writer does not scale).
+ *   bbt_psrfits_encode   x[n_row][n_bin][n_chan][n_pol] float32 ->
+ *       codes[n_row][n_pol][n_chan][n_bin] int16 stored big-endian, and per
+ *       (row, pol, chan) scl, offs (float32) and n_finite (int32).  In float32,
+ *       every operation rounded on its own: mn, mx over the finite bins (NaN and
+ *       +-inf are left out; n_finite counts the rest); offs = 0.5 mn + 0.5 mx;
+ *       scl = (0.5 mx - 0.5 mn) / 32767, 1 where that is not > 0;
+ *       code = clip(rint((x - offs) / scl), -32767, 32767) with the IEEE divide,
+ *       rint half to even; 0 for a bin that is not finite.  No finite bin:
+ *       offs = 0, scl = 1, codes 0.  No atomics: the same bytes every time.
+ *   bbt_psrfits_decode   the inverse layout change,
+ *       out[row][bin][chan][pol] = ((float)code - zero_off) * scl + offs
+ *       (three roundings), then times wts[row][chan] if wts_dev is not NULL.
+ * n_bin, n_chan, n_pol >= 1 (any, odd included); at most 2^40 samples a call.
+ * Pointers aligned to their elements; 16-byte aligned floats, 4-byte aligned
+ * codes, n_chan * n_pol a multiple of 4 and an even n_bin take the vector
+ * kernels. */
+int bbt_psrfits_encode(const void* x_dev, void* codes_dev, void* scl_dev, void* offs_dev,
+                       void* n_finite_dev, int64_t n_row, int64_t n_bin, int64_t n_chan,
+                       int64_t n_pol, bbt_stream stream);
+int bbt_psrfits_decode(const void* codes_dev, const void* scl_dev, const void* offs_dev,
+                       const void* wts_dev, float zero_off, void* out_dev, int64_t n_row,
+                       int64_t n_bin, int64_t n_chan, int64_t n_pol, bbt_stream stream);
+
 /* ---- multi-GPU: one process per GPU, RCCL over xGMI ----------------------
  * The reference has no distributed code; these are what SURVEY 8(b)/(e) ask a
  * replacement to export for the way this path shards (independent overlap-save
