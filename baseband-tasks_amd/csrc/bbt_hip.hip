@@ -30,10 +30,11 @@
 #include "gather_kernels.hpp"
 #include "pack_kernels.hpp"
 #include "psrfits_kernels.hpp"
+#include "noise_kernels.hpp"
 
 using namespace bbt;
 
-#define BBT_VERSION 158
+#define BBT_VERSION 159
 
 // ---------------------------------------------------------------------------
 // errors
@@ -3068,6 +3069,73 @@ extern "C" int bbt_phase_runs(const void* pieces_dev, int64_t n_piece, int n_coe
                        (const long long*)(scalars + 1), (long long)n_slot, (long long*)slot_ptr_dev);
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipMemcpyAsync(info, scalars, 16, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    return 0;
+}
+
+// ---------------------------------------------------------------------------
+// NumPy's normal stream (noise_kernels.hpp)
+static int64_t noise_tiles(int64_t n_words) { return (n_words + BBT_NOISE_TILE - 1) / BBT_NOISE_TILE; }
+
+// work area: counters (4 per frame) | totals | flags | tile offsets (int64 each) | tile counts
+// (6 uint32 per tile) | tile maps | tile entry states (uint32 / int32 per tile)
+extern "C" int bbt_philox_normal_work(int64_t n_frame, int64_t n_words, int64_t* bytes) {
+    ARG_TRY(bytes, "bbt_philox_normal_work: null argument");
+    ARG_TRY(n_frame >= 1 && n_frame <= 65535 && n_words >= 4 && n_words % 4 == 0 && n_words < (1ll << 40),
+            "bbt_philox_normal_work: bad sizes");
+    const int64_t tiles = n_frame * noise_tiles(n_words);
+    *bytes = 8 * (6 * n_frame + tiles) + 4 * 8 * tiles;
+    return 0;
+}
+
+extern "C" int bbt_philox_normal(const uint64_t* key, const uint64_t* counters, int64_t n_frame, int64_t n,
+                                 int64_t n_words, double guard, float* out_dev, int64_t out_stride,
+                                 void* work_dev, int64_t work_bytes, int64_t* totals, int64_t* flags,
+                                 bbt_stream stream) {
+    ARG_TRY(key && counters && out_dev && work_dev && totals && flags, "bbt_philox_normal: null argument");
+    int64_t need = 0;
+    if (bbt_philox_normal_work(n_frame, n_words, &need) != 0) return 1;
+    ARG_TRY(n >= 1 && n <= out_stride && n < (1ll << 40), "bbt_philox_normal: bad frame length or stride");
+    ARG_TRY(guard >= 0, "bbt_philox_normal: the guard must not be negative");
+    ARG_TRY(work_bytes >= need, "bbt_philox_normal: work area of %lld bytes, %lld needed", (long long)work_bytes,
+            (long long)need);
+    ARG_TRY(((uintptr_t)work_dev & 15) == 0 && ((uintptr_t)out_dev & 3) == 0,
+            "bbt_philox_normal: the work area must be 16-byte aligned, the output 4-byte aligned");
+    const int64_t n_tile = noise_tiles(n_words);
+    ARG_TRY(n_tile < (1ll << 31), "bbt_philox_normal: too many words for one call");
+    hipStream_t st = (hipStream_t)stream;
+    // the first block of a frame comes from the state's counter plus one
+    std::vector<uint64_t> first((size_t)n_frame * 4);
+    for (int64_t f = 0; f < n_frame; ++f) {
+        bool carry = true;
+        for (int i = 0; i < 4; ++i) {
+            const uint64_t c = counters[f * 4 + i] + (carry ? 1 : 0);
+            carry = carry && c == 0;
+            first[f * 4 + i] = c;
+        }
+    }
+    const int64_t tiles = n_frame * n_tile;
+    nu64* ctr = (nu64*)work_dev;
+    long long* total_d = (long long*)(ctr + 4 * n_frame);
+    long long* flag_d = total_d + n_frame;
+    long long* tile_off = flag_d + n_frame;
+    unsigned* tile_cnt = (unsigned*)(tile_off + tiles);
+    unsigned* tile_map = tile_cnt + 6 * tiles;
+    int* tile_entry = (int*)(tile_map + tiles);
+    HIP_TRY(hipMemcpyAsync(ctr, first.data(), (size_t)n_frame * 32, hipMemcpyHostToDevice, st));
+    HIP_TRY(hipStreamSynchronize(st));                     // (pageable source: `first` may go)
+    HIP_TRY(hipMemsetAsync(total_d, 0, (size_t)n_frame * 16, st));
+    const dim3 grid((unsigned)n_tile, (unsigned)n_frame), block(256);
+    hipLaunchKernelGGL(k_noise_count, grid, block, 0, st, (const nu64*)ctr, (nu64)key[0], (nu64)key[1],
+                       (long long)n_words, (long long)n_tile, tile_map, tile_cnt);
+    hipLaunchKernelGGL(k_noise_scan, dim3((unsigned)n_frame), block, 0, st, (const unsigned*)tile_map,
+                       (const unsigned*)tile_cnt, (long long)n_tile, tile_entry, tile_off, total_d);
+    hipLaunchKernelGGL(k_noise_emit, grid, block, 0, st, (const nu64*)ctr, (nu64)key[0], (nu64)key[1],
+                       (long long)n_words, (long long)n_tile, (const int*)tile_entry, (const long long*)tile_off,
+                       (long long)n, guard, out_dev, (long long)out_stride, flag_d);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipMemcpyAsync(totals, total_d, (size_t)n_frame * 8, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipMemcpyAsync(flags, flag_d, (size_t)n_frame * 8, hipMemcpyDeviceToHost, st));
     HIP_TRY(hipStreamSynchronize(st));
     return 0;
 }

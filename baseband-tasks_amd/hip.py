@@ -14,7 +14,7 @@ import numpy as np
 __all__ = ['HipError', 'HipLibraryMissing', 'lib', 'available', 'DeviceArray',
            'OsmPlan', 'ChanPlan', 'PfbPlan', 'set_stream', 'get_stream',
            'synchronize', 'Event', 'device_count', 'set_device', 'pack', 'to_half', 'from_half',
-           'psrfits_encode', 'psrfits_decode']
+           'psrfits_encode', 'psrfits_decode', 'philox_normal']
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 # BBT_HIP_LIB points at another build of the same library (the sanitizer build
@@ -99,6 +99,8 @@ SIGNATURES = {
     'bbt_phase_runs_work': [_i64, _i64, _i64, _pi64],
     'bbt_phase_runs': [_vp, _i64, _int, _i64, _i64, _i64, _vp, _i64, _i64, _i64, _i64, _i64, _vp, _vp, _vp, _vp,
                        _vp, _i64, _pi64, _vp],
+    'bbt_philox_normal_work': [_i64, _i64, _pi64],
+    'bbt_philox_normal': [_vp, _vp, _i64, _i64, _i64, C.c_double, _vp, _i64, _vp, _i64, _pi64, _pi64, _vp],
     'bbt_shift_plan_create': [_pvp, _int, _int, _pi32],
     'bbt_shift_plan_destroy': [_vp],
     'bbt_shift_execute': [_vp, _vp, _vp, _i64, _vp],
@@ -134,7 +136,7 @@ SIGNATURES = {
 }
 
 #: oldest libbbt_hip.so whose entry points and argument meanings this binding assumes
-MIN_LIB_VERSION = 158
+MIN_LIB_VERSION = 159
 
 _lib = None
 _lock = threading.Lock()
@@ -822,6 +824,68 @@ def phase_runs(plan, n_phase, slot0=0, n_slot=None):
                          f"describe it): status {info[1]}, {info[0]} runs for a capacity of {run_cap}")
     n_run = int(info[0])
     return slot_ptr, runs[0:1].reshape(run_cap)[:n_run], runs[1:2].reshape(run_cap)[:n_run], n_run, counts.to_host()
+
+
+#: relative margin inside which a comparison of the normal sampler that goes through exp / log1p is
+#: left to NumPy (see bbt_philox_normal in include/bbt_hip.h)
+NOISE_GUARD = 2.0 ** -46
+
+
+def noise_word_count(n):
+    """Words of the Philox stream examined first for n normals: 4 * ceil((1.03 n + 256) / 4)
+    (the sampler takes 1.022 words per normal on average)."""
+    return 4 * (-(-(103 * int(n) + 25600) // 400))
+
+
+def philox_normal(out, key, counters, n=None, n_words=None, guard=NOISE_GUARD):
+    """NumPy's normals on the GPU (bbt_philox_normal): row f of ``out`` (a float32 `DeviceArray`
+    of shape (n_frame, stride)) gets the first ``n`` (default: stride) values, rounded to float32,
+    that ``Generator(Philox).normal`` gives for a state with this ``key`` (two uint64), counter
+    ``counters[f]`` (four uint64) and an empty buffer.
+
+    ``n_words`` words of the stream are examined per frame (default `noise_word_count`); frames
+    whose words hold fewer than n normals are run again with the number doubled, until they do.
+    Returns (flags, reruns): flags[f] is True if a decision of frame f was too close to call
+    between this device's and the host's math library -- its row is then to be made with NumPy --
+    and reruns counts the runs of a frame that had to be repeated with more words."""
+    if out.dtype != np.float32 or len(out.shape) != 2:
+        raise TypeError("philox_normal: out must be a float32 DeviceArray of shape (n_frame, stride)")
+    n_frame, stride = out.shape
+    n = stride if n is None else int(n)
+    key = np.ascontiguousarray(key, dtype=np.uint64)
+    counters = np.ascontiguousarray(counters, dtype=np.uint64)
+    if key.shape != (2,) or counters.shape != (n_frame, 4):
+        raise ValueError("philox_normal: key must hold 2 and counters (n_frame, 4) uint64")
+    if not 1 <= n <= stride:
+        raise ValueError("philox_normal: n must be between 1 and the row length of out")
+    n_words = noise_word_count(n) if n_words is None else int(n_words)
+    flags = np.zeros(n_frame, bool)
+    todo = np.arange(n_frame)
+    reruns = 0
+    while len(todo):
+        # (runs of consecutive frames share a call; after a shortfall usually one frame is left)
+        first = int(todo[0])
+        count = 1
+        while count < len(todo) and todo[count] == first + count and count < 65535:
+            count += 1
+        need = C.c_int64()
+        check(lib().bbt_philox_normal_work(count, n_words, C.byref(need)))
+        work = DeviceArray((need.value // 8 + 2,), np.int64)
+        totals = np.zeros(count, np.int64)
+        flagged = np.zeros(count, np.int64)
+        piece = out[first:first + count]
+        ctr = counters[first:first + count]
+        check(lib().bbt_philox_normal(key.ctypes.data, ctr.ctypes.data, count, n, n_words, float(guard),
+                                      piece.ptr, stride, work.ptr, work.nbytes,
+                                      totals.ctypes.data_as(_pi64), flagged.ctypes.data_as(_pi64), _stream))
+        flags[first:first + count] = flagged != 0
+        short = first + np.nonzero((totals < n) & (flagged == 0))[0]
+        todo = todo[count:]
+        for f in short:
+            sub_flags, again = philox_normal(out[int(f):int(f) + 1], key, counters[f:f + 1], n, 2 * n_words, guard)
+            flags[f] = sub_flags[0]
+            reruns += 1 + again
+    return flags, reruns
 
 
 def detect_power_axis(in_dev, out_dev, n_out, step, outer, inner, average=True):

@@ -611,6 +611,31 @@ int bbt_psrfits_decode(const void* codes_dev, const void* scl_dev, const void* o
                        const void* wts_dev, float zero_off, void* out_dev, int64_t n_row,
                        int64_t n_bin, int64_t n_chan, int64_t n_pol, bbt_stream stream);
 
+/* ---- NumPy's normal stream, made on the device (csrc/noise_kernels.hpp) -----
+ * Frame f is the first n values of `Generator(Philox).normal` for a bit generator
+ * whose state has this key, counter counters[f] and an empty buffer (buffer_pos 4),
+ * each rounded to float32, written to out_dev + f * out_stride: Philox-4x64-10 and
+ * NumPy's 256-step ziggurat, bit for bit.
+ *   key, counters   host: uint64[2], uint64[n_frame][4]
+ *   n               normals per frame (>= 1, <= out_stride); n_frame in [1, 65535]
+ *   n_words         words of the stream examined per frame: a positive multiple of 4.
+ *                   totals[f] is the number of normals they hold; if it is below n the
+ *                   caller asks again with more words (the values written are then the
+ *                   first totals[f] of the frame).
+ *   guard           a comparison of the sampler that goes through exp or log1p, or a
+ *                   tail value's rounding to float32, that a relative perturbation of
+ *                   this size could turn sets flags[f] = 1: the caller makes that frame
+ *                   with NumPy.  2^-46 assumes both math libraries good to about 2 ulp.
+ *   totals, flags   host int64[n_frame].  The call waits for the stream.
+ *   work            device scratch of bbt_philox_normal_work(n_frame, n_words) bytes,
+ *                   16-byte aligned.
+ * No atomics; the output depends on the arguments only. */
+int bbt_philox_normal_work(int64_t n_frame, int64_t n_words, int64_t* bytes);
+int bbt_philox_normal(const uint64_t* key, const uint64_t* counters, int64_t n_frame, int64_t n,
+                      int64_t n_words, double guard, float* out_dev, int64_t out_stride,
+                      void* work_dev, int64_t work_bytes, int64_t* totals, int64_t* flags,
+                      bbt_stream stream);
+
 /* ---- multi-GPU: one process per GPU, RCCL over xGMI ----------------------
  * The reference has no distributed code; these are what SURVEY 8(b)/(e) ask a
  * replacement to export for the way this path shards (independent overlap-save
