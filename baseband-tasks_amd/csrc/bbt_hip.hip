@@ -30,11 +30,12 @@
 #include "gather_kernels.hpp"
 #include "pack_kernels.hpp"
 #include "psrfits_kernels.hpp"
+#include "psrsearch_kernels.hpp"
 #include "noise_kernels.hpp"
 
 using namespace bbt;
 
-#define BBT_VERSION 159
+#define BBT_VERSION 160
 
 // ---------------------------------------------------------------------------
 // errors
@@ -4157,6 +4158,69 @@ extern "C" int bbt_psrfits_decode(const void* codes_dev, const void* scl_dev, co
     HIP_TRY(hipGetLastError());
     return 0;
 }
+
+// ---------------------------------------------------------------------------
+// PSRFITS search-mode rows (psrsearch_kernels.hpp): float32 samples (row, sample, chan, pol) <->
+// unsigned codes of 1, 2, 4 or 8 bits (row, sample, pol, chan), packed along the channels, with a
+// scale and an offset per (row, pol, chan).  The tiling is psrsearch_geo.hpp's.
+static int psrsearch_shape(const char* who, int64_t n_row, int64_t nsblk, int64_t n_chan, int64_t n_pol, int nbits,
+                           const void* codes_dev, PsrSearchGeo* g) {
+    ARG_TRY(n_row >= 0, "%s: %lld rows", who, (long long)n_row);
+    const char* bad = psrsearch_geo(nsblk, n_chan, n_pol, nbits, ((uintptr_t)codes_dev & 3u) == 0, g);
+    ARG_TRY(!bad, "%s: %s (%lld samples a row, %lld channels, %lld polarizations, %d bits)", who, bad ? bad : "",
+            (long long)nsblk, (long long)n_chan, (long long)n_pol, nbits);
+    ARG_TRY((double)n_row * (double)nsblk * (double)(n_chan * n_pol) <= (double)BBT_PACK_MAX,
+            "%s: more than 2^40 samples", who);
+    ARG_TRY(n_row * g->n_tile < (1ll << 31), "%s: too many tiles for one call", who);
+    return 0;
+}
+#define BBT_PSRSEARCH_LAUNCH(K_, ...)                                                                       \
+    do {                                                                                                    \
+        const dim3 grid((unsigned)(n_row * g.n_tile)), block(BBT_PSRSEARCH_THREADS);                        \
+        switch (nbits * 2 + g.vec) {                                                                        \
+            case 2: hipLaunchKernelGGL((K_<1, false>), grid, block, 0, (hipStream_t)stream, __VA_ARGS__); break;  \
+            case 3: hipLaunchKernelGGL((K_<1, true>), grid, block, 0, (hipStream_t)stream, __VA_ARGS__); break;   \
+            case 4: hipLaunchKernelGGL((K_<2, false>), grid, block, 0, (hipStream_t)stream, __VA_ARGS__); break;  \
+            case 5: hipLaunchKernelGGL((K_<2, true>), grid, block, 0, (hipStream_t)stream, __VA_ARGS__); break;   \
+            case 8: hipLaunchKernelGGL((K_<4, false>), grid, block, 0, (hipStream_t)stream, __VA_ARGS__); break;  \
+            case 9: hipLaunchKernelGGL((K_<4, true>), grid, block, 0, (hipStream_t)stream, __VA_ARGS__); break;   \
+            case 16: hipLaunchKernelGGL((K_<8, false>), grid, block, 0, (hipStream_t)stream, __VA_ARGS__); break; \
+            default: hipLaunchKernelGGL((K_<8, true>), grid, block, 0, (hipStream_t)stream, __VA_ARGS__); break;  \
+        }                                                                                                   \
+    } while (0)
+extern "C" int bbt_psrsearch_encode(const void* x_dev, void* codes_dev, void* scl_dev, void* offs_dev,
+                                    void* n_finite_dev, int64_t n_row, int64_t nsblk, int64_t n_chan,
+                                    int64_t n_pol, int nbits, double nsigma, bbt_stream stream) {
+    ARG_TRY(x_dev && codes_dev && scl_dev && offs_dev && n_finite_dev, "bbt_psrsearch_encode: null argument");
+    PsrSearchGeo g;
+    if (psrsearch_shape("bbt_psrsearch_encode", n_row, nsblk, n_chan, n_pol, nbits, codes_dev, &g)) return 1;
+    ARG_TRY((((uintptr_t)x_dev | (uintptr_t)scl_dev | (uintptr_t)offs_dev | (uintptr_t)n_finite_dev) & 3u) == 0,
+            "bbt_psrsearch_encode: pointers must be aligned to their elements");
+    ARG_TRY(nsigma > 0. && nsigma < HUGE_VAL, "bbt_psrsearch_encode: nsigma must be positive and finite");
+    if (n_row == 0) return 0;
+    BBT_PSRSEARCH_LAUNCH(k_psrsearch_encode, (const float*)x_dev, (unsigned char*)codes_dev, (float*)scl_dev,
+                         (float*)offs_dev, (int*)n_finite_dev, (long long)nsblk, (long long)n_chan,
+                         (long long)n_pol, nsigma, g);
+    HIP_TRY(hipGetLastError());
+    return 0;
+}
+extern "C" int bbt_psrsearch_decode(const void* codes_dev, const void* scl_dev, const void* offs_dev,
+                                    const void* wts_dev, float zero_off, void* out_dev, int64_t n_row,
+                                    int64_t nsblk, int64_t n_chan, int64_t n_pol, int nbits, bbt_stream stream) {
+    ARG_TRY(codes_dev && scl_dev && offs_dev && out_dev, "bbt_psrsearch_decode: null argument");
+    PsrSearchGeo g;
+    if (psrsearch_shape("bbt_psrsearch_decode", n_row, nsblk, n_chan, n_pol, nbits, codes_dev, &g)) return 1;
+    ARG_TRY((((uintptr_t)out_dev | (uintptr_t)scl_dev | (uintptr_t)offs_dev | (uintptr_t)wts_dev) & 3u) == 0,
+            "bbt_psrsearch_decode: pointers must be aligned to their elements");
+    ARG_TRY(zero_off == zero_off, "bbt_psrsearch_decode: zero_off is not a number");
+    if (n_row == 0) return 0;
+    BBT_PSRSEARCH_LAUNCH(k_psrsearch_decode, (const unsigned char*)codes_dev, (const float*)scl_dev,
+                         (const float*)offs_dev, (const float*)wts_dev, zero_off, (float*)out_dev,
+                         (long long)nsblk, (long long)n_chan, (long long)n_pol, g);
+    HIP_TRY(hipGetLastError());
+    return 0;
+}
+#undef BBT_PSRSEARCH_LAUNCH
 
 // ---------------------------------------------------------------------------
 // multi-GPU: one process per GPU, RCCL over xGMI.  The path

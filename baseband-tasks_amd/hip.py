@@ -14,7 +14,7 @@ import numpy as np
 __all__ = ['HipError', 'HipLibraryMissing', 'lib', 'available', 'DeviceArray',
            'OsmPlan', 'ChanPlan', 'PfbPlan', 'set_stream', 'get_stream',
            'synchronize', 'Event', 'device_count', 'set_device', 'pack', 'to_half', 'from_half',
-           'psrfits_encode', 'psrfits_decode', 'philox_normal']
+           'psrfits_encode', 'psrfits_decode', 'psrsearch_encode', 'psrsearch_decode', 'philox_normal']
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 # BBT_HIP_LIB points at another build of the same library (the sanitizer build
@@ -128,6 +128,8 @@ SIGNATURES = {
     'bbt_from_half': [_vp, _vp, _i64, _vp],
     'bbt_psrfits_encode': [_vp, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _i64, _vp],
     'bbt_psrfits_decode': [_vp, _vp, _vp, _vp, C.c_float, _vp, _i64, _i64, _i64, _i64, _vp],
+    'bbt_psrsearch_encode': [_vp, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _i64, _int, C.c_double, _vp],
+    'bbt_psrsearch_decode': [_vp, _vp, _vp, _vp, C.c_float, _vp, _i64, _i64, _i64, _i64, _int, _vp],
     'bbt_comm_unique_id': [_vp, _sz],
     'bbt_comm_init': [_pvp, _int, _int, _vp, _sz],
     'bbt_comm_destroy': [_vp],
@@ -136,7 +138,7 @@ SIGNATURES = {
 }
 
 #: oldest libbbt_hip.so whose entry points and argument meanings this binding assumes
-MIN_LIB_VERSION = 159
+MIN_LIB_VERSION = 160
 
 _lib = None
 _lock = threading.Lock()
@@ -1106,6 +1108,101 @@ def psrfits_decode(codes, scl, offs, wts=None, zero_off=0., out=None):
         check(lib().bbt_psrfits_decode(codes.ptr_to_read(), scl.ptr_to_read(), offs.ptr_to_read(),
                                        wts.ptr_to_read() if wts is not None else None, zero_off, out.ptr,
                                        n_row, n_bin, n_chan, n_pol, _stream))
+    return out
+
+
+#: widths of a search-mode code
+PSRSEARCH_BITS = (1, 2, 4, 8)
+#: columns (channels x polarizations) of a row from which bbt_psrsearch_encode adds a column's
+#: samples in order (BBT_PSRSEARCH_MANY in csrc/psrsearch_geo.hpp)
+PSRSEARCH_MANY_COLUMNS = 64
+
+
+def _search_dims(nsblk, n_chan, n_pol, nbits, who):
+    if isinstance(nbits, bool) or nbits not in PSRSEARCH_BITS:
+        raise ValueError(f"{who}: nbits must be one of {PSRSEARCH_BITS}, not {nbits!r}")
+    nsblk, n_chan, n_pol = int(nsblk), int(n_chan), int(n_pol)
+    if min(nsblk, n_chan, n_pol) < 1:
+        raise ValueError(f"{who}: an empty axis in (nsblk, nchan, npol) = {(nsblk, n_chan, n_pol)}")
+    if n_pol > 32:
+        raise ValueError(f"{who}: {n_pol} polarizations; at most 32 are coded")
+    if n_chan * nbits % 8:
+        raise ValueError(f"{who}: {n_chan} channels of {nbits} bits do not fill whole bytes "
+                         "(nchan * nbits must be a multiple of 8)")
+    return nsblk, n_chan, n_pol, int(nbits)
+
+
+def psrsearch_encode(x, nsblk, nbits, nsigma):
+    """Code float32 samples ``(n, n_chan[, n_pol])``, ``n`` a whole number of rows of ``nsblk``
+    samples, in HBM as the rows of a PSRFITS search-mode table (bbt_psrsearch_encode in
+    include/bbt_hip.h; `psrfits.encode_search_rows` is the NumPy restatement).  Returns
+    `DeviceArray`s ``(codes, scl, offs, n_finite)``: uint8 ``(n_row, nsblk, n_pol, n_chan * nbits
+    / 8)``, and float32, float32, int32 ``(n_row, n_pol, n_chan)``."""
+    if not isinstance(x, DeviceArray):
+        raise TypeError(f"psrsearch_encode: the input must be a DeviceArray, not {type(x).__name__}")
+    if x.dtype != np.dtype(np.float32):
+        raise TypeError(f"psrsearch_encode: the input must be float32, not {x.dtype}")
+    if not 2 <= len(x.shape) <= 3:
+        raise ValueError(f"psrsearch_encode: samples have shape (n, chan[, pol]), not {tuple(x.shape)}")
+    n, n_chan, n_pol = tuple(x.shape) + (1,) * (3 - len(x.shape))
+    nsblk, n_chan, n_pol, nbits = _search_dims(nsblk, n_chan, n_pol, nbits, 'psrsearch_encode')
+    if n % nsblk:
+        raise ValueError(f"psrsearch_encode: {n} samples are not a whole number of rows of {nsblk}")
+    nsigma = float(nsigma)
+    if not 0. < nsigma < np.inf:
+        raise ValueError(f"psrsearch_encode: nsigma must be positive and finite, not {nsigma}")
+    n_row = n // nsblk
+    codes = DeviceArray((n_row, nsblk, n_pol, n_chan * nbits // 8), np.uint8)
+    scl = DeviceArray((n_row, n_pol, n_chan), np.float32)
+    offs = DeviceArray((n_row, n_pol, n_chan), np.float32)
+    n_finite = DeviceArray((n_row, n_pol, n_chan), np.int32)
+    if n_row:
+        check(lib().bbt_psrsearch_encode(x.ptr_to_read(), codes.ptr, scl.ptr, offs.ptr, n_finite.ptr,
+                                         n_row, nsblk, n_chan, n_pol, nbits, nsigma, _stream))
+    return codes, scl, offs, n_finite
+
+
+def psrsearch_decode(codes, scl, offs, wts, zero_off, nbits, dims, out=None):
+    """Decode rows of a PSRFITS search-mode table in HBM (bbt_psrsearch_decode): uint8 ``codes``
+    holding ``(n_row, nsblk, n_pol, n_chan * nbits / 8)`` bytes, float32 ``scl`` and ``offs (n_row,
+    n_pol, n_chan)`` and float32 weights ``wts (n_row, n_chan)`` or None, with ``dims = (nsblk,
+    n_chan, n_pol)`` -> float32 ``(n_row * nsblk, n_chan, n_pol)``: ``((float)code - zero_off) *
+    scl + offs``, times the weight (``out`` if given)."""
+    for name, a, dtype in (('codes', codes, np.uint8), ('scl', scl, np.float32), ('offs', offs, np.float32),
+                           ('wts', wts, np.float32)):
+        if a is None and name == 'wts':
+            continue
+        if not isinstance(a, DeviceArray):
+            raise TypeError(f"psrsearch_decode: {name} must be a DeviceArray, not {type(a).__name__}")
+        if a.dtype != np.dtype(dtype):
+            raise TypeError(f"psrsearch_decode: {name} must be {np.dtype(dtype).str}, not {a.dtype.str}")
+    if len(tuple(dims)) != 3:
+        raise ValueError(f"psrsearch_decode: dims are (nsblk, nchan, npol), not {dims!r}")
+    nsblk, n_chan, n_pol, nbits = _search_dims(*dims, nbits, 'psrsearch_decode')
+    if offs.size != scl.size or scl.size % (n_chan * n_pol):
+        raise ValueError(f"psrsearch_decode: scl and offs hold {scl.size} and {offs.size} values for rows of "
+                         f"{n_chan} channels and {n_pol} polarizations")
+    n_row = scl.size // (n_chan * n_pol)
+    row_bytes = nsblk * n_pol * n_chan * nbits // 8
+    if codes.size != n_row * row_bytes:
+        raise ValueError(f"psrsearch_decode: codes hold {codes.size} bytes for {n_row} rows of {row_bytes}")
+    if wts is not None and wts.size != n_row * n_chan:
+        raise ValueError(f"psrsearch_decode: wts holds {wts.size} values for {n_row} rows of {n_chan} channels")
+    zero_off = float(zero_off)
+    if zero_off != zero_off:
+        raise ValueError("psrsearch_decode: zero_off is not a number")
+    if out is None:
+        out = DeviceArray((n_row * nsblk, n_chan, n_pol), np.float32)
+    elif not isinstance(out, DeviceArray):
+        raise TypeError(f"psrsearch_decode: out must be a DeviceArray, not {type(out).__name__}")
+    elif out.dtype != np.dtype(np.float32):
+        raise TypeError(f"psrsearch_decode: out must be float32, not {out.dtype}")
+    elif out.size != n_row * nsblk * n_chan * n_pol:
+        raise ValueError(f"psrsearch_decode: out holds {out.size} values for {n_row * nsblk * n_chan * n_pol} codes")
+    if n_row:
+        check(lib().bbt_psrsearch_decode(codes.ptr_to_read(), scl.ptr_to_read(), offs.ptr_to_read(),
+                                         wts.ptr_to_read() if wts is not None else None, zero_off, out.ptr,
+                                         n_row, nsblk, n_chan, n_pol, nbits, _stream))
     return out
 
 

@@ -611,6 +611,40 @@ int bbt_psrfits_decode(const void* codes_dev, const void* scl_dev, const void* o
                        const void* wts_dev, float zero_off, void* out_dev, int64_t n_row,
                        int64_t n_bin, int64_t n_chan, int64_t n_pol, bbt_stream stream);
 
+/* ---- PSRFITS search-mode rows ------------------------------------------------
+ * The coding behind `psrfits.PSRFITSSearchWriter` / `PSRFITSSearchReader`: the
+ * DATA, DAT_SCL and DAT_OFFS columns of a SUBINT table with OBS_MODE = 'SEARCH'
+ * (the reference has fold mode only; `psrfits.encode_search_rows` /
+ * `decode_search_rows` restate the rule in NumPy).
+ *   bbt_psrsearch_encode   x[n_row][nsblk][n_chan][n_pol] float32 ->
+ *       codes: bytes [n_row][nsblk][n_pol][n_chan * nbits / 8], unsigned codes of
+ *       nbits = 1, 2, 4 or 8 bits, the first channel of a byte in its most
+ *       significant bits; and per (row, pol, chan) scl, offs (float32) and
+ *       n_finite (int32).  Over the finite samples of a column, in float64 with
+ *       every operation rounded on its own: n, S1 = sum x, S2 = sum x * x;
+ *       mean = S1 / n; std = sqrt(max(S2 / n - mean * mean, 0));
+ *       offs = float(mean - nsigma * std);
+ *       scl = float((2 * nsigma) * std / (2^nbits - 1)); where n = 0 or scl is
+ *       not > 0: scl = 1, offs = float(mean) (0 when n = 0).  In float32:
+ *       code = clip(rint((x - offs) / scl), 0, 2^nbits - 1), IEEE divide, rint
+ *       half to even, a NaN quotient 0; a sample that is not finite takes the
+ *       code of float(mean).  No atomics: the same bytes every time.  With
+ *       n_chan * n_pol >= 64 a column's samples are added in order; below, in
+ *       256 / (n_chan * n_pol) interleaved partial sums that meet in a tree.
+ *   bbt_psrsearch_decode   the inverse layout change,
+ *       out[row][sample][chan][pol] = ((float)code - zero_off) * scl + offs
+ *       (three roundings), then times wts[row][chan] if wts_dev is not NULL.
+ * n_chan * nbits a multiple of 8; n_pol <= 32; at most 2^40 samples a call.
+ * Floats aligned to 4 bytes; 4-byte aligned codes with n_chan * nbits a multiple
+ * of 32 are stored and loaded as dwords, others as bytes. */
+int bbt_psrsearch_encode(const void* x_dev, void* codes_dev, void* scl_dev, void* offs_dev,
+                         void* n_finite_dev, int64_t n_row, int64_t nsblk, int64_t n_chan,
+                         int64_t n_pol, int nbits, double nsigma, bbt_stream stream);
+int bbt_psrsearch_decode(const void* codes_dev, const void* scl_dev, const void* offs_dev,
+                         const void* wts_dev, float zero_off, void* out_dev, int64_t n_row,
+                         int64_t nsblk, int64_t n_chan, int64_t n_pol, int nbits,
+                         bbt_stream stream);
+
 /* ---- NumPy's normal stream, made on the device (csrc/noise_kernels.hpp) -----
  * Frame f is the first n values of `Generator(Philox).normal` for a bit generator
  * whose state has this key, counter counters[f] and an empty buffer (buffer_pos 4),

@@ -1,0 +1,253 @@
+"""PSRFITS search-mode coding on the GPU: `hip.psrsearch_encode` / `hip.psrsearch_decode` against the
+NumPy restatement `psrfits.encode_search_rows` / `decode_search_rows`, and a dynamic spectrum
+streamed into a file through ``read(out=writer)`` and read back.
+
+What is held to what: ``n_finite`` equals the twin's; ``scl`` and ``offs`` equal the twin's where a
+thread adds a column's samples in the twin's order (64 columns a row or more) and are within 2
+float32 ulp where the float64 sums are made in interleaved parts (fewer columns); the codes are, byte
+for byte, what the twin makes from the device's own ``scl`` and ``offs`` (float32, contraction off:
+no freedom); decoding is bit-identical."""
+import numpy as np
+import pytest
+
+import baseband_tasks_amd as bt
+from baseband_tasks_amd import hip, psrfits
+from baseband_tasks_amd import units as u
+from test_psrfits_search_host import flat, noise
+
+pytestmark = pytest.mark.gpu
+
+#: ((nrow, nsblk, nchan, npol), nbits): one tile of 64 columns at every width (the 1-bit rows leave as
+#: bytes, the others as dwords); a byte a spectrum; 48 columns, not a power of two, nsblk neither;
+#: one sample a row; few columns, time across the lanes, more samples than a coding tile; 16 tiles
+CASES = [((3, 64, 16, 4), 8), ((3, 64, 16, 4), 4), ((3, 64, 16, 4), 2), ((3, 64, 16, 4), 1),
+         ((2, 32, 8, 1), 1), ((2, 48, 24, 2), 4), ((2, 48, 24, 2), 8), ((1, 1, 16, 2), 8),
+         ((2, 8192, 8, 2), 8), ((2, 64, 1024, 4), 8)]
+SHIFTED = ((2, 64, 16, 4), 8)         # input 4 bytes, codes 1 byte into their allocations: byte accesses
+IDS = [f'{s[0]}x{s[1]}x{s[2]}x{s[3]}-{b}bit' for s, b in CASES + [SHIFTED]]
+
+
+@pytest.fixture(scope='module', autouse=True)
+def _need_gpu():
+    if not hip.available():
+        pytest.fail("no GPU / libbbt_hip.so: the -m gpu suite must run on an MI355X")
+
+
+@pytest.fixture(scope='module')
+def cases():
+    """(shape, nbits) -> (samples, what `encode_search_rows` makes of them), made once."""
+    out = {}
+    for shape, nbits in CASES + [SHIFTED]:
+        x = noise(shape, seed=sum(shape) + nbits)
+        out[shape, nbits] = x, psrfits.encode_search_rows(flat(x), shape[1], nbits)
+    return out
+
+
+def shifted(a, by):
+    """``a`` in HBM as a view that starts ``by`` bytes into its allocation."""
+    flat_a = np.ascontiguousarray(a).ravel()
+    per = by // flat_a.dtype.itemsize
+    room = hip.DeviceArray((flat_a.size + per,), flat_a.dtype)
+    view = room[per:]
+    view.copy_from_host(flat_a)
+    assert view.ptr % 16 == by
+    return view.reshape(a.shape)
+
+
+def same_bytes(got, want):
+    assert got.dtype == want.dtype and got.shape == want.shape
+    bad = np.nonzero((np.ascontiguousarray(got).view(np.uint8) != np.ascontiguousarray(want).view(np.uint8)).ravel())[0]
+    assert bad.size == 0, (bad.size, bad[:8])
+
+
+def ulps(a, b):
+    """Distance of two float32 arrays in units in the last place (finite values)."""
+    def key(v):
+        i = np.ascontiguousarray(v, np.float32).view(np.int32).astype(np.int64)
+        return np.where(i < 0, -(i & 0x7fffffff), i)
+    return np.abs(key(a) - key(b))
+
+
+def check_encode(x, want, got, nsblk, nbits):
+    codes, scl, offs, n_finite = got
+    n_row, _, n_chan, n_pol = x.shape
+    assert codes.dtype == np.uint8 and codes.shape == (n_row, nsblk, n_pol, n_chan * nbits // 8)
+    same_bytes(n_finite, want[3])
+    d_scl, d_offs = ulps(scl, want[1]).max(), ulps(offs, want[2]).max()
+    print(f'{x.shape} {nbits} bit: scl within {d_scl} ulp, offs within {d_offs} ulp of the twin')
+    if n_chan * n_pol >= hip.PSRSEARCH_MANY_COLUMNS:        # (the twin's order of summation)
+        same_bytes(scl, want[1])
+        same_bytes(offs, want[2])
+    else:
+        assert d_scl <= 2 and d_offs <= 2
+    same_bytes(codes, psrfits.encode_search_rows(flat(x), nsblk, nbits, scl=scl, offs=offs)[0])
+
+
+# -- 1. encode ---------------------------------------------------------------------------------------
+@pytest.mark.parametrize('shape, nbits', CASES, ids=IDS[:-1])
+def test_encode(cases, shape, nbits):
+    x, want = cases[shape, nbits]
+    got = hip.psrsearch_encode(hip.DeviceArray.from_host(flat(x)), shape[1], nbits, psrfits.SEARCH_NSIGMA[nbits])
+    check_encode(x, want, [a.to_host() for a in got], shape[1], nbits)
+
+
+def test_encode_of_unaligned_views(cases):
+    """The input a view 4 bytes into its allocation; then, through the C ABI, codes that start 1
+    byte into theirs: stored byte by byte."""
+    shape, nbits = SHIFTED
+    x, want = cases[SHIFTED]
+    n_row, nsblk, n_chan, n_pol = shape
+    dev = shifted(flat(x), 4)
+    check_encode(x, want, [a.to_host() for a in hip.psrsearch_encode(dev, nsblk, nbits, 6.0)], nsblk, nbits)
+    room = hip.DeviceArray((want[0].size + 1,), np.uint8)
+    room.copy_from_host(np.full(room.size, 0xa5, np.uint8))
+    scl, offs = hip.DeviceArray(want[1].shape, np.float32), hip.DeviceArray(want[2].shape, np.float32)
+    n_finite = hip.DeviceArray(want[3].shape, np.int32)
+    hip.check(hip.lib().bbt_psrsearch_encode(dev.ptr, room.ptr + 1, scl.ptr, offs.ptr, n_finite.ptr, n_row, nsblk,
+                                             n_chan, n_pol, nbits, 6.0, None))
+    back = room.to_host()
+    assert back[0] == 0xa5                                        # (nothing before the first code)
+    check_encode(x, want, [back[1:].reshape(want[0].shape), scl.to_host(), offs.to_host(), n_finite.to_host()],
+                 nsblk, nbits)
+
+
+# -- 2. decode ---------------------------------------------------------------------------------------
+@pytest.mark.parametrize('shape, nbits', CASES + [SHIFTED], ids=IDS)
+def test_decode_is_exact(cases, shape, nbits):
+    _, (codes, scl, offs, _) = cases[shape, nbits]
+    n_row, nsblk, n_chan, n_pol = shape
+    dims = (nsblk, n_chan, n_pol)
+    d_codes = shifted(codes, 1) if (shape, nbits) == SHIFTED else hip.DeviceArray.from_host(codes)
+    d_scl, d_offs = hip.DeviceArray.from_host(scl), hip.DeviceArray.from_host(offs)
+    got = hip.psrsearch_decode(d_codes, d_scl, d_offs, None, 0., nbits, dims)
+    assert got.shape == (n_row * nsblk, n_chan, n_pol)
+    same_bytes(got.to_host(), psrfits.decode_search_rows(codes, scl, offs, nbits=nbits))
+    wts = np.random.default_rng(3).integers(0, 3, (n_row, n_chan)).astype(np.float32) * np.float32(0.7)
+    out = hip.DeviceArray((n_row * nsblk * n_chan * n_pol + 1,), np.float32)
+    view = out[1:] if (shape, nbits) == SHIFTED else out[:out.size - 1]
+    res = hip.psrsearch_decode(d_codes, d_scl, d_offs, hip.DeviceArray.from_host(wts), 0.5, nbits, dims, out=view)
+    assert res.ptr == view.ptr
+    same_bytes(res.to_host().reshape(got.shape), psrfits.decode_search_rows(codes, scl, offs, wts, 0.5, nbits))
+
+
+# -- 3. a dynamic spectrum into a file and back ----------------------------------------------------------
+T0 = bt.Time('2020-01-01T00:00:00') + 0.25
+NSBLK = 64
+
+
+@pytest.fixture(scope='module')
+def waterfall():
+    noise_in = bt.DeviceNoiseGenerator((1 << 16, 2), T0, 1. * u.MHz, 1 << 12, seed=11, frequency=400. * u.MHz,
+                                       sideband=1, polarization=['X', 'Y'])
+    stream = bt.Integrate(bt.Power(bt.Channelize(noise_in, 16)), 4)
+    assert stream.shape == (1024, 16, 4)
+    return stream, stream.read()
+
+
+def table(name):
+    raw = np.fromfile(name, np.uint8)
+    sub = psrfits.read_hdus(raw)[1]
+    return np.ndarray((int(sub.header['NAXIS2']),), psrfits.table_dtype(sub.header), buffer=raw, offset=sub.data_offset)
+
+
+@pytest.mark.parametrize('nbits', [8, 2])
+def test_waterfall_streams_into_a_file(waterfall, tmp_path, nbits):
+    stream, spectrum = waterfall
+    name, host_name = str(tmp_path / 'device.fits'), str(tmp_path / 'host.fits')
+    keys = dict(template=stream, nbits=nbits, nsblk=NSBLK, primary={'TELESCOP': 'nowhere'})
+    stream.seek(0)
+    with psrfits.open_search(name, 'w', **keys) as fw:
+        stream.read(out=fw)
+        assert fw.tell() == 1024
+    with psrfits.open_search(host_name, 'w', **keys) as fw:
+        fw.write(spectrum[:3 * NSBLK])
+        fw.write(spectrum[3 * NSBLK:])
+    with open(name, 'rb') as a, open(host_name, 'rb') as b:
+        same = a.read() == b.read()
+    rows = table(name)
+    if not same:                    # (scl or offs in the last place: then the rule of test_encode, row by row)
+        print('the two files differ: held to the twin row by row')
+        for k, (dev, host) in enumerate(zip(rows, table(host_name))):
+            x = spectrum[None, k * NSBLK:(k + 1) * NSBLK]
+            got = [np.array(dev['DATA']).reshape(1, NSBLK, 4, -1), dev['DAT_SCL'].astype(np.float32).reshape(1, 4, 16),
+                   dev['DAT_OFFS'].astype(np.float32).reshape(1, 4, 16)]
+            want = psrfits.encode_search_rows(x[0], NSBLK, nbits)
+            check_encode(x, want, got + [want[3]], NSBLK, nbits)
+            for column in ('TSUBINT', 'OFFS_SUB', 'DAT_FREQ', 'DAT_WTS'):
+                assert np.array_equal(dev[column], host[column])
+    with psrfits.open_search(name) as fh:
+        assert fh.shape == stream.shape and fh.dtype == stream.dtype and fh.samples_per_frame == NSBLK
+        assert fh.sample_rate == stream.sample_rate and abs(fh.start_time - stream.start_time) < 1e-9
+        assert np.allclose(np.broadcast_to(fh.frequency, fh.sample_shape),
+                           np.broadcast_to(stream.frequency, stream.sample_shape), rtol=1e-15, atol=0)
+        assert np.all(np.broadcast_to(fh.sideband, fh.sample_shape)
+                      == np.broadcast_to(stream.sideband, stream.sample_shape))
+        assert np.all(np.broadcast_to(fh.polarization, fh.sample_shape)
+                      == np.broadcast_to(stream.polarization, stream.sample_shape))
+        assert fh.primary['TELESCOP'] == 'nowhere'
+        summed = bt.Integrate(fh, 2).read_device()
+        assert isinstance(summed, hip.DeviceArray) and summed.shape == (512, 16, 4)
+        got = summed.to_host()
+    decoded = psrfits.decode_search_rows(np.array(rows['DATA']).reshape(16, NSBLK, 4, -1), rows['DAT_SCL'],
+                                         rows['DAT_OFFS'], rows['DAT_WTS'], nbits=nbits)
+    want = decoded.reshape(512, 2, 16, 4).sum(axis=1) * np.float32(0.5)
+    assert np.allclose(got, want, rtol=1e-6, atol=0)
+    # and the file holds the spectrum: inside the coded range to half a step, and 2^-12 of a step for the
+    # float32 roundings of coder and decoder (each below 2^-23 of a magnitude of at most 2^8 steps)
+    scl = rows['DAT_SCL'].astype(np.float64).reshape(16, 1, 4, 16).transpose(0, 1, 3, 2)
+    offs = rows['DAT_OFFS'].astype(np.float64).reshape(16, 1, 4, 16).transpose(0, 1, 3, 2)
+    x = spectrum.reshape(16, NSBLK, 16, 4).astype(np.float64)
+    inside = (x >= offs) & (x <= offs + (2 ** nbits - 1) * scl)
+    err = np.abs(decoded.reshape(x.shape) - x)
+    assert np.all(np.isfinite(spectrum)) and np.all(err[inside] <= ((0.5 + 2. ** -12) * scl * np.ones_like(x))[inside])
+
+
+# -- 4. argument checks ----------------------------------------------------------------------------------
+def test_argument_checks():
+    x = hip.DeviceArray((8, 16), np.float32)
+    x.copy_from_host(np.arange(128, dtype=np.float32).reshape(8, 16))
+    got = hip.psrsearch_encode(x, 4, 2, 1.5)
+    assert [a.shape for a in got] == [(2, 4, 1, 4), (2, 1, 16), (2, 1, 16), (2, 1, 16)]
+    assert hip.psrsearch_encode(hip.DeviceArray((0, 8, 2), np.float32), 4, 8, 6.)[0].shape == (0, 4, 2, 8)
+    with pytest.raises(TypeError):
+        hip.psrsearch_encode(np.zeros((8, 16), np.float32), 4, 8, 6.)
+    with pytest.raises(TypeError):
+        hip.psrsearch_encode(hip.DeviceArray((8, 16), np.complex64), 4, 8, 6.)
+    with pytest.raises(ValueError):
+        hip.psrsearch_encode(hip.DeviceArray((8,), np.float32), 4, 8, 6.)
+    with pytest.raises(ValueError):
+        hip.psrsearch_encode(x, 3, 8, 6.)                          # (8 samples are not rows of 3)
+    with pytest.raises(ValueError):
+        hip.psrsearch_encode(x, 4, 3, 6.)                          # (nbits)
+    with pytest.raises(ValueError):
+        hip.psrsearch_encode(hip.DeviceArray((8, 12), np.float32), 4, 1, 1.)       # (12 bits a spectrum)
+    with pytest.raises(ValueError):
+        hip.psrsearch_encode(x, 4, 8, 0.)                          # (nsigma)
+    codes, scl, offs, _ = got
+    with pytest.raises(TypeError):
+        hip.psrsearch_decode(scl, scl, offs, None, 0., 2, (4, 16, 1))
+    with pytest.raises(TypeError):
+        hip.psrsearch_decode(codes, scl, offs, None, 0., 2, (4, 16, 1), out=np.zeros((8, 16, 1), np.float32))
+    with pytest.raises(ValueError):
+        hip.psrsearch_decode(codes, scl, offs, None, 0., 2, (4, 16, 1), out=hip.DeviceArray((5,), np.float32))
+    with pytest.raises(ValueError):
+        hip.psrsearch_decode(codes, scl, offs, None, 0., 2, (8, 16, 1))            # (codes for rows of 4)
+    with pytest.raises(ValueError):
+        hip.psrsearch_decode(codes, scl, offs, None, 0., 2, (4, 16))
+    with pytest.raises(ValueError):
+        hip.psrsearch_decode(codes, scl, offs, None, 0., 1, (4, 12, 1))
+    with pytest.raises(ValueError):
+        hip.psrsearch_decode(codes, scl, offs, hip.DeviceArray((2, 8), np.float32), 0., 2, (4, 16, 1))   # (weights)
+    with pytest.raises(ValueError):
+        hip.psrsearch_decode(codes, scl, offs, None, float('nan'), 2, (4, 16, 1))
+    lib = hip.lib()
+    assert lib.bbt_psrsearch_encode(None, None, None, None, None, 1, 1, 8, 1, 8, 6., None) != 0
+    assert b'null' in lib.bbt_last_error()
+    assert lib.bbt_psrsearch_encode(x.ptr, codes.ptr, scl.ptr, offs.ptr, offs.ptr, 1, 4, 12, 1, 1, 1., None) != 0
+    assert b'multiple of 8' in lib.bbt_last_error()
+    assert lib.bbt_psrsearch_encode(x.ptr, codes.ptr, scl.ptr, offs.ptr, offs.ptr, 1, 4, 16, 1, 3, 1., None) != 0
+    assert b'nbits' in lib.bbt_last_error()
+    assert lib.bbt_psrsearch_encode(x.ptr, codes.ptr, scl.ptr, offs.ptr, offs.ptr, 1, 0, 16, 1, 8, 6., None) != 0
+    assert b'empty' in lib.bbt_last_error()
+    assert lib.bbt_psrsearch_decode(codes.ptr, scl.ptr + 1, offs.ptr, None, 0., x.ptr, 1, 4, 16, 1, 2, None) != 0
+    assert b'aligned' in lib.bbt_last_error()

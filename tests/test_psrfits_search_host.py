@@ -1,0 +1,371 @@
+"""PSRFITS search mode without a GPU: the bit order of packed codes pinned from the PSRFITS
+definition, the NumPy coding `encode_search_rows` / `decode_search_rows` that the kernels are held
+to, the bytes of a file written from host pieces (found with the card walker of
+test_psrfits_host.py), the writer's refusals, and the tiling of the kernels
+(csrc/psrsearch_geo.hpp) walked on the host by a stand-alone program under sanitizers."""
+import json
+import os
+import subprocess
+
+import numpy as np
+import pytest
+
+import baseband_tasks_amd as bt
+from baseband_tasks_amd import psrfits
+from baseband_tasks_amd import units as u
+from test_psrfits_host import WIDTHS, walk
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+CSRC = os.path.join(ROOT, 'baseband-tasks_amd', 'csrc')
+F32 = np.float32
+
+
+def noise(shape, seed=5):
+    """Seeded chi-square noise of 8 degrees of freedom, ``(nrow, nsblk, nchan, npol)``, with --
+    where there is room -- a NaN and an inf in column (chan 0, pol 0) of row 0, a constant column
+    (chan 1, last pol) in the last row and a channel (2) that is all NaN in row 0."""
+    rng = np.random.default_rng(seed)
+    x = (rng.standard_normal(shape + (8,)) ** 2).sum(-1).astype(F32)
+    n_row, nsblk, n_chan, n_pol = shape
+    if nsblk > 2:
+        x[0, 1, 0, 0] = np.nan
+        x[0, nsblk - 1, 0, 0] = np.inf
+    if n_chan > 1:
+        x[-1, :, 1, n_pol - 1] = 2.5
+    if n_chan > 2:
+        x[0, :, 2, :] = np.nan
+    return x
+
+
+def flat(x):
+    """(nrow, nsblk, nchan, npol) as the stream it is a piece of: (nrow * nsblk, nchan, npol)."""
+    return x.reshape((-1,) + x.shape[2:])
+
+
+# -- the bit order, from the definition: the first channel in the most significant bits ------------
+@pytest.mark.parametrize('nbits, codes, want', [
+    (4, [1, 2, 3, 4], b'\x12\x34'),
+    (1, [1, 0, 0, 0, 0, 0, 0, 1], b'\x81'),
+    (1, [0, 1, 1, 0, 1, 0, 0, 0, 1, 1, 1, 1, 0, 0, 0, 0], b'\x68\xf0'),
+    (2, [3, 0, 1, 2], b'\xc6'),
+    (2, [0, 0, 0, 1, 2, 2, 2, 2], b'\x01\xaa'),
+    (4, [15, 0, 0, 15], b'\xf0\x0f'),
+    (8, [0, 1, 254, 255], b'\x00\x01\xfe\xff'),
+])
+def test_bit_order(nbits, codes, want):
+    packed = psrfits.pack_codes(codes, nbits)
+    assert packed.dtype == np.uint8 and packed.tobytes() == want
+    assert list(psrfits.unpack_codes(np.frombuffer(want, np.uint8), nbits)) == codes
+
+
+def test_rows_are_sample_pol_chan_with_the_channel_fastest():
+    """A row whose samples are their own codes (scl 1, offs 0): x[s, c, p] = (s + 3 c + p) % 16 at
+    4 bits leaves as [s][p][c / 2] bytes, the even channel in the high nibble."""
+    s, c, p = np.meshgrid(np.arange(4), np.arange(6), np.arange(2), indexing='ij')
+    x = ((s + 3 * c + p) % 16).astype(F32)
+    ones, zeros = np.ones((1, 2, 6), F32), np.zeros((1, 2, 6), F32)
+    data = psrfits.encode_search_rows(x, 4, 4, scl=ones, offs=zeros)[0]
+    assert data.shape == (1, 4, 2, 3)
+    for si in range(4):
+        for pi in range(2):
+            for b in range(3):
+                hi, lo = int(x[si, 2 * b, pi]), int(x[si, 2 * b + 1, pi])
+                assert data[0, si, pi, b] == (hi << 4) | lo
+    back = psrfits.decode_search_rows(data, ones, zeros, nbits=4)
+    assert back.shape == (4, 6, 2) and np.array_equal(back, x)
+
+
+# -- the coding ----------------------------------------------------------------------------------------
+@pytest.mark.parametrize('nbits', [8, 4, 2, 1])
+def test_twin_round_trip(nbits):
+    shape = (2, 256, 8, 2)
+    rng = np.random.default_rng(3)
+    x = (rng.standard_normal(shape + (8,)) ** 2).sum(-1).astype(F32)
+    x[0, 7, 3, 1], x[1, 9, 2, 0] = 200., -200.            # (one far outlier each way: beyond 6 std of 256 samples)
+    k = psrfits.SEARCH_NSIGMA[nbits]
+    data, scl, offs, n_finite = psrfits.encode_search_rows(flat(x), 256, nbits)
+    assert data.dtype == np.uint8 and data.shape == (2, 256, 2, 8 * nbits // 8)
+    assert scl.dtype == offs.dtype == F32 and n_finite.dtype == np.int32 and np.all(n_finite == 256)
+    back = psrfits.decode_search_rows(data, scl, offs, nbits=nbits).reshape(shape)
+    mean = x.astype(np.float64).mean(axis=1, keepdims=True)
+    std = x.astype(np.float64).std(axis=1, keepdims=True)
+    scl_c = scl.transpose(0, 2, 1)[:, None].astype(np.float64)          # (row, 1, chan, pol)
+    offs_c = offs.transpose(0, 2, 1)[:, None].astype(np.float64)
+    # (the rule's own numbers: the two-pass mean and std above agree with them to rounding)
+    assert np.allclose(offs_c, mean - k * std, rtol=1e-5) and np.allclose(scl_c, 2 * k * std / (2 ** nbits - 1), rtol=1e-5)
+    inside = np.abs(x - mean) <= k * std * (1 - 1e-6)
+    err = np.abs(back.astype(np.float64) - x)
+    print(f'nbits {nbits}: largest error inside the range, in steps: {(err / scl_c)[inside].max():.7f}; '
+          f'clipped {np.count_nonzero(~inside)} of {x.size}')
+    assert np.all(err[inside] <= (scl_c / 2 * np.ones_like(err))[inside])
+    # clipped samples decode to the end levels
+    codes = psrfits.unpack_codes(data, nbits).transpose(0, 1, 3, 2)
+    low, high = x < mean - k * std * (1 + 1e-6), x > mean + k * std * (1 + 1e-6)
+    assert high.any() and np.all(codes[high] == 2 ** nbits - 1) and np.all(codes[low] == 0)
+    top = (F32(2 ** nbits - 1) * scl.transpose(0, 2, 1) + offs.transpose(0, 2, 1))[:, None]
+    assert np.array_equal(back[high], np.broadcast_to(top, shape)[high])
+    assert np.array_equal(back[low], np.broadcast_to(offs.transpose(0, 2, 1)[:, None], shape)[low])
+
+
+def test_statistics_are_the_rules():
+    """One column by hand, in float64 in sample order, as the rule states it."""
+    x = noise((1, 37, 8, 1), seed=2)
+    col = x[0, :, 0, 0]
+    s1 = s2 = 0.
+    n = 0
+    for v in col:
+        if np.isfinite(v):
+            s1, s2, n = s1 + float(v), s2 + float(v) * float(v), n + 1
+    mean = s1 / n
+    std = np.sqrt(max(s2 / n - mean * mean, 0.))
+    for nbits, k in psrfits.SEARCH_NSIGMA.items():
+        _, scl, offs, n_finite = psrfits.encode_search_rows(flat(x), 37, nbits)
+        assert n_finite[0, 0, 0] == n == 35
+        assert offs[0, 0, 0] == F32(mean - k * std) and scl[0, 0, 0] == F32(2. * k * std / (2 ** nbits - 1))
+        _, scl2, offs2, _ = psrfits.encode_search_rows(flat(x), 37, nbits, nsigma=2.25)
+        assert offs2[0, 0, 0] == F32(mean - 2.25 * std) and scl2[0, 0, 0] == F32(4.5 * std / (2 ** nbits - 1))
+    assert psrfits.SEARCH_NSIGMA == {8: 6.0, 4: 3.0, 2: 1.5, 1: 1.0}
+
+
+def test_edge_columns():
+    x = noise((2, 33, 8, 2))
+    data, scl, offs, n_finite = psrfits.encode_search_rows(flat(x), 33, 8)
+    codes = psrfits.unpack_codes(data, 8).transpose(0, 1, 3, 2)          # (row, sample, chan, pol)
+    # a constant column: std = 0, so scl = 1 and offs = float32(mean); codes 0; exact on the way back
+    assert scl[1, 1, 1] == 1. and offs[1, 1, 1] == 2.5 and np.all(codes[1, :, 1, 1] == 0)
+    assert np.all(psrfits.decode_search_rows(data, scl, offs).reshape(x.shape)[1, :, 1, 1] == 2.5)
+    # a column of NaN: n = 0, scl = 1, offs = 0, codes 0
+    assert np.all(n_finite[0, :, 2] == 0) and np.all(scl[0, :, 2] == 1.) and np.all(offs[0, :, 2] == 0.)
+    assert np.all(codes[0, :, 2, :] == 0)
+    # a NaN and an inf in a column: left out of the statistics, coded as float32(mean)
+    clean = x.copy()
+    finite = np.isfinite(x[0, :, 0, 0])
+    assert finite.sum() == 31 and n_finite[0, 0, 0] == 31
+    mean = F32(x[0, finite, 0, 0].astype(np.float64).sum() / 31)
+    clean[0, ~finite, 0, 0] = mean
+    d2, s2, o2, n2 = psrfits.encode_search_rows(flat(clean), 33, 8, scl=scl, offs=offs)
+    assert np.array_equal(d2, data) and n2[0, 0, 0] == 33
+    want = np.clip(np.rint((mean - offs[0, 0, 0]) / scl[0, 0, 0]), 0, 255)
+    assert np.all(codes[0, ~finite, 0, 0] == want) and 100 < want < 155         # (mid-range: the mean)
+    # DAT_WTS: 0 for a channel without a finite sample in any polarization
+    wts = n_finite.sum(axis=1) > 0
+    assert wts.shape == (2, 8) and not wts[0, 2] and wts.sum() == 15
+    # nsblk = 1: every column is constant
+    one = noise((3, 1, 8, 2), seed=4)
+    d1, s1, o1, n1 = psrfits.encode_search_rows(flat(one), 1, 8)
+    assert np.all(s1 == 1.) and np.all(d1 == 0) and np.array_equal(o1, np.nan_to_num(one[:, 0].transpose(0, 2, 1)))
+    assert np.array_equal(n1, np.isfinite(one[:, 0]).transpose(0, 2, 1).astype(np.int32))
+    # weights and ZERO_OFF in the decoder
+    w = np.array([[1., 0., 2., 1., 1., 1., 1., .5]] * 2, F32)
+    plain = psrfits.decode_search_rows(data, scl, offs).reshape(x.shape)
+    got = psrfits.decode_search_rows(data, scl, offs, w).reshape(x.shape)
+    assert np.array_equal(got, plain * w[:, None, :, None])
+    shifted = psrfits.decode_search_rows(data, scl, offs, zero_off=0.5).reshape(x.shape)
+    want = (codes.astype(F32) - F32(0.5)) * scl.transpose(0, 2, 1)[:, None] + offs.transpose(0, 2, 1)[:, None]
+    assert np.array_equal(shifted, want)
+
+
+# -- a written file ------------------------------------------------------------------------------------
+class Template:
+    """What a writer needs of a stream."""
+    shape = (3 * 16, 8, 2)
+    dtype = np.dtype(np.float32)
+    start_time = bt.Time('2021-03-04T05:06:07') + 0.123456789012
+    sample_rate = 1. / 7.5e-4
+    frequency = (400. + 1.5 * np.arange(8))[:, None] * u.MHz
+    sideband = np.int8(-1)
+    polarization = np.array(['LL', 'RR'])
+
+
+@pytest.fixture(scope='module', params=[8, 4, 2, 1])
+def written(request, tmp_path_factory):
+    nbits = request.param
+    name = str(tmp_path_factory.mktemp('psrfits_search') / f'host{nbits}.fits')
+    x = noise((3, 16, 8, 2), seed=9)
+    with psrfits.open_search(name, 'w', template=Template, nbits=nbits, nsblk=16,
+                             primary={'TELESCOP': 'GBT', 'SRC_NAME': ('B0000+00', 'Source')}) as fw:
+        assert isinstance(fw, psrfits.PSRFITSSearchWriter)
+        assert fw.accepts_device and fw.granule == 16 and fw.shape == Template.shape and fw.tell() == 0
+        fw.write(flat(x)[:16])
+        with pytest.raises(ValueError, match='granule'):
+            fw.write(flat(x)[16:20])
+        fw[16:48] = flat(x)[16:]
+        assert fw.tell() == 48
+        with pytest.raises(EOFError):
+            fw.write(flat(x)[:16])
+    return name, x, nbits
+
+
+def test_written_file_layout(written):
+    name, x, nbits = written
+    raw = np.fromfile(name, np.uint8).tobytes()
+    assert len(raw) % 2880 == 0
+    (primary, _), (sub, at) = walk(raw)
+    assert primary['SIMPLE'] == 'T' and primary['BITPIX'] == '8' and primary['NAXIS'] == '0' and primary['EXTEND'] == 'T'
+    assert primary['FITSTYPE'] == 'PSRFITS' and primary['OBS_MODE'] == 'SEARCH' and 'HDRVER' in primary
+    assert primary['TELESCOP'] == 'GBT' and primary['SRC_NAME'] == 'B0000+00'
+    assert float(primary['OBSFREQ']) == 404.5 and float(primary['OBSBW']) == -12. and primary['OBSNCHAN'] == '8'
+    assert sub['XTENSION'] == 'BINTABLE' and sub['EXTNAME'] == 'SUBINT' and sub['NAXIS'] == '2'
+    assert sub['INT_TYPE'] == 'TIME' and sub['INT_UNIT'] == 'SEC' and sub['POL_TYPE'] == 'LLRR'
+    assert (sub['NPOL'], sub['NBIN'], sub['NCHAN'], sub['NBITS'], sub['NSBLK']) == ('2', '1', '8', str(nbits), '16')
+    assert float(sub['ZERO_OFF']) == 0. and float(sub['CHAN_BW']) == -1.5 and float(sub['TBIN']) == 7.5e-4
+    assert sub['SIGNINT'] == '0' and sub['NSTOT'] == '48'
+    n_field = int(sub['TFIELDS'])
+    names = [sub[f'TTYPE{k}'] for k in range(1, n_field + 1)]
+    assert names == ['TSUBINT', 'OFFS_SUB', 'DAT_FREQ', 'DAT_WTS', 'DAT_OFFS', 'DAT_SCL', 'DATA']
+    forms = [sub[f'TFORM{k}'] for k in range(1, n_field + 1)]
+    assert forms == ['1D', '1D', '8D', '8E', '16E', '16E', f'{16 * 2 * 8 * nbits // 8}B']
+    widths = [int(f[:-1]) * WIDTHS[f[-1]] for f in forms]
+    assert int(sub['NAXIS1']) == sum(widths) and int(sub['NAXIS2']) == 3
+    assert sub['TDIM7'] == f'(8,2,{16 * nbits // 8})'
+    assert len(raw) == at + 2880 * -(-3 * sum(widths) // 2880)
+    data, scl, offs, n_finite = psrfits.encode_search_rows(flat(x), 16, nbits)
+    starts = np.concatenate([[0], np.cumsum(widths)])
+    stt = (int(primary['STT_IMJD']) - 40587) * 86400 + int(primary['STT_SMJD'])
+    for k in range(3):
+        row = raw[at + k * sum(widths):at + (k + 1) * sum(widths)]
+        field = lambda i, dtype: np.frombuffer(row[starts[i]:starts[i + 1]], dtype)
+        assert field(6, 'u1').tobytes() == data[k].tobytes()                      # (sample, pol, chan)
+        assert np.array_equal(field(5, '>f4'), scl[k].ravel()) and np.array_equal(field(4, '>f4'), offs[k].ravel())
+        assert np.array_equal(field(2, '>f8'), 400. + 1.5 * np.arange(8))
+        assert np.array_equal(field(3, '>f4'), (n_finite[k].sum(0) > 0).astype(F32))
+        tsubint, offs_sub = field(0, '>f8')[0], field(1, '>f8')[0]
+        assert tsubint == 16 * 7.5e-4
+        start = bt.Time(stt, float(primary['STT_OFFS'])) + (offs_sub - (k + 0.5) * tsubint)
+        assert abs(start - Template.start_time) < 1e-9
+    assert np.all(np.frombuffer(raw[at + 3 * sum(widths):], np.uint8) == 0)
+    wts = np.frombuffer(raw[at + starts[3]:at + starts[4]], '>f4')
+    assert list(wts) == [1., 1., 0., 1., 1., 1., 1., 1.]
+
+
+def test_written_file_reopens(written):
+    name, x, nbits = written
+    raw = np.fromfile(name, np.uint8)
+    hdus = psrfits.read_hdus(raw)
+    assert [h.name for h in hdus] == ['PRIMARY', 'SUBINT']
+    dtype = psrfits.table_dtype(hdus[1].header)
+    assert dtype.itemsize == hdus[1].header['NAXIS1'] and dtype['DATA'].shape == (16 * 2 * 8 * nbits // 8,)
+    with psrfits.open_search(name) as fh:
+        assert isinstance(fh, psrfits.PSRFITSSearchReader)
+        assert fh.shape == Template.shape and fh.dtype == np.float32 and fh.samples_per_frame == 16
+        assert fh.sample_rate == Template.sample_rate and fh.nbits == nbits and fh.weighted
+        assert abs(fh.start_time - Template.start_time) < 1e-9
+        assert fh.frequency.shape == (8, 1) and np.array_equal(fh.frequency, Template.frequency)
+        assert np.all(fh.sideband == -1) and list(fh.polarization.ravel()) == ['LL', 'RR']
+        assert fh.primary['TELESCOP'] == 'GBT' and fh.header['TDIM7'] == f'(8,2,{16 * nbits // 8})'
+        assert fh.zero_off == 0.
+    assert fh.closed
+    # fold mode's entry still refuses the file, and search mode's refuses a fold-mode archive
+    with pytest.raises(ValueError, match='SEARCH'):
+        psrfits.open(name)
+
+
+def test_open_search_refuses_fold_mode(tmp_path):
+    name = str(tmp_path / 'fold.fits')
+    with psrfits.open(name, 'w', shape=(2, 8, 2), start_time='2020-01-01T00:00:00', sample_rate=1.) as fw:
+        fw.write(np.zeros((2, 8, 2), F32))
+    with pytest.raises(ValueError, match='PSR'):
+        psrfits.open_search(name)
+    with pytest.raises(ValueError, match='mode'):
+        psrfits.open_search(name, 'a')
+    with pytest.raises(TypeError):
+        psrfits.open_search(name, 'r', verify=True)
+
+
+def test_single_polarization_and_default_nsblk(tmp_path):
+    name = str(tmp_path / 'one.fits')
+    x = noise((1, 4096, 8, 1), seed=6)[..., 0]
+    with psrfits.open_search(name, 'w', nbits=2, shape=(4096, 8), start_time='2020-01-01T00:00:00',
+                             sample_rate=1. * u.kHz) as fw:
+        assert fw.nsblk == 4096 and fw.nsigma == 1.5
+        fw.write(x[0])
+    raw = np.fromfile(name, np.uint8).tobytes()
+    (_, _), (sub, at) = walk(raw)
+    assert sub['TDIM7'] == '(8,1,1024)' and sub['POL_TYPE'] == 'INTEN' and sub['CHAN_BW'] == '*' and sub['NAXIS2'] == '1'
+    with psrfits.open_search(name) as fh:
+        assert fh.shape == (4096, 8, 1) and fh.sample_rate == 1000.
+        with pytest.raises(AttributeError):
+            fh.frequency
+
+
+# -- errors ----------------------------------------------------------------------------------------------
+def test_writer_refuses_what_it_cannot_store(tmp_path):
+    name = str(tmp_path / 'no.fits')
+    keys = dict(start_time='2020-01-01T00:00:00', sample_rate=1.)
+    with pytest.raises(TypeError, match='complex'):
+        psrfits.open_search(name, 'w', shape=(64, 8, 2), nsblk=32, dtype=np.complex64, **keys)
+    counted = np.dtype([('data', np.float32), ('count', int)])          # (what average=False makes)
+    with pytest.raises(TypeError, match='average'):
+        psrfits.open_search(name, 'w', shape=(64, 8, 2), nsblk=32, dtype=counted, **keys)
+    with pytest.raises(TypeError, match='float32'):
+        psrfits.open_search(name, 'w', shape=(64, 8, 2), nsblk=32, dtype=np.float64, **keys)
+
+    class Stacked:
+        shape, dtype, _time_from_offsets = (64, 8, 2), np.dtype(np.float32), True
+        start_time, sample_rate = bt.Time('2020-01-01T00:00:00'), 1.
+
+    with pytest.raises(TypeError, match='uniform'):
+        psrfits.open_search(name, 'w', template=Stacked, nsblk=32)
+    with pytest.raises(ValueError, match='shape'):
+        psrfits.open_search(name, 'w', shape=(64,), nsblk=32, **keys)
+    with pytest.raises(ValueError, match='shape'):
+        psrfits.open_search(name, 'w', shape=(64, 4, 8, 2), nsblk=32, **keys)
+    for nbits in (0, 3, 16, True):
+        with pytest.raises(ValueError, match='nbits'):
+            psrfits.open_search(name, 'w', shape=(64, 8, 2), nsblk=32, nbits=nbits, **keys)
+    # channels that do not fill bytes
+    with pytest.raises(ValueError, match='multiple of 8'):
+        psrfits.open_search(name, 'w', shape=(64, 5, 2), nsblk=32, nbits=4, **keys)
+    with pytest.raises(ValueError, match='multiple of 8'):
+        psrfits.open_search(name, 'w', shape=(64, 4, 2), nsblk=32, nbits=1, **keys)
+    # a length that is not whole rows: the message names the nearest that is
+    with pytest.raises(ValueError, match='nearest length that is, is 96'):
+        psrfits.open_search(name, 'w', shape=(100, 8, 2), nsblk=32, **keys)
+    with pytest.raises(ValueError, match='nearest length that is, is 128'):
+        psrfits.open_search(name, 'w', shape=(120, 8, 2), nsblk=32, **keys)
+    with pytest.raises(ValueError, match='nearest length that is, is 32'):
+        psrfits.open_search(name, 'w', shape=(5, 8, 2), nsblk=32, **keys)
+    with pytest.raises(ValueError, match='nsigma'):
+        psrfits.open_search(name, 'w', shape=(64, 8, 2), nsblk=32, nsigma=0., **keys)
+    with pytest.raises(ValueError, match='chan_bw'):
+        psrfits.open_search(name, 'w', shape=(64, 1), nsblk=32, nbits=8, frequency=400 * u.MHz, sideband=1, **keys)
+    with pytest.raises(ValueError, match='own'):
+        psrfits.open_search(name, 'w', shape=(64, 8), nsblk=32, primary={'OBS_MODE': 'PSR'}, **keys)
+    assert not os.path.exists(name)
+
+
+# -- the kernels' tiling, on the host ----------------------------------------------------------------------
+#: (nsblk, nchan, npol, nbits, codes 4-byte aligned): the shapes of tests/test_psrfits_search_gpu.py,
+#: the usual 1024 x 4 at every width, ragged last tiles, three and 32 polarizations
+GEO_SHAPES = [(64, 16, 4, 8, 1), (64, 16, 4, 4, 1), (64, 16, 4, 2, 1), (64, 16, 4, 1, 1), (64, 16, 4, 8, 0),
+              (32, 8, 1, 1, 1), (48, 24, 2, 4, 1), (48, 24, 2, 8, 1), (1, 16, 2, 8, 1), (8192, 8, 2, 8, 1),
+              (64, 1024, 4, 8, 1), (64, 1024, 4, 4, 1), (64, 1024, 4, 2, 1), (64, 1024, 4, 1, 1), (64, 1024, 4, 2, 0),
+              (10, 21, 3, 8, 1), (10, 96, 3, 4, 1), (10, 8, 32, 1, 1), (10, 40, 5, 2, 1), (7, 4096, 1, 1, 1),
+              (7, 100, 1, 8, 1), (7, 72, 4, 1, 1), (5, 1000, 2, 4, 0)]
+
+
+def test_kernel_tiling_on_the_host(tmp_path):
+    """Every LDS index inside the tile, every column and every stored byte owned once: the
+    program exits non-zero otherwise, and the sanitizers abort it on a wild index of its own."""
+    exe = str(tmp_path / 'psrsearch_geo_check')
+    subprocess.check_call(['g++', '-O1', '-g', '-std=c++17', '-fsanitize=address,undefined',
+                           '-fno-sanitize-recover=undefined', '-I', CSRC,
+                           os.path.join(ROOT, 'tests', 'psrsearch_geo_check.cpp'), '-o', exe])
+    args = [str(v) for shape in GEO_SHAPES for v in shape]
+    out = subprocess.run([exe] + args, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True)
+    assert out.returncode == 0, out.stdout + out.stderr
+    plans = [json.loads(line) for line in out.stdout.splitlines()]
+    assert len(plans) == len(GEO_SHAPES)
+    for (nsblk, nchan, npol, nbits, aligned), g in zip(GEO_SHAPES, plans):
+        assert g['walk'] == 0, (nsblk, nchan, npol, nbits, g)
+        assert g['ct'] * npol <= 256 and g['ts'] * npol * g['pol_pitch'] <= 8192
+        assert (g['ny'] == 1) == (nchan * npol >= 64)
+        assert g['vec'] == int(aligned and nchan * nbits % 32 == 0 and npol * 32 // nbits <= 256)
+        assert g['unit'] == (32 if g['vec'] else 8) // nbits
+    assert plans[10] == {'ct': 64, 'unit': 4, 'vec': 1, 'ny': 1, 'pol_pitch': 72, 'ts': 28, 'n_tile': 16, 'walk': 0}
+    # what the library refuses
+    bad = subprocess.run([exe, '8', '16', '4', '3', '1', '8', '4', '2', '1', '1', '8', '8', '33', '8', '1'],
+                         stdout=subprocess.PIPE, text=True)
+    assert bad.returncode == 0
+    errors = [json.loads(line)['error'] for line in bad.stdout.splitlines()]
+    assert 'nbits' in errors[0] and 'multiple of 8' in errors[1] and 'polarizations' in errors[2]
