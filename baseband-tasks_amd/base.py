@@ -105,6 +105,9 @@ class Base:
     closed = False
     _frame_index = None
     _frame = None
+    #: the stream below, for a wrapper whose ``read_device`` hands on that stream's result as it
+    #: is (the view then lives as long as that stream lets it: `device_task.cache_producer`)
+    _view_source = None
 
     def __init__(self, shape, start_time, sample_rate, *, samples_per_frame=1,
                  dtype=np.complex64, **kwargs):
@@ -595,7 +598,13 @@ class SetAttribute(TaskBase):
         # (a pass-through: on the device if the stream below is)
         return self._passthrough and bool(getattr(self.ih, '_produces_on_device', False))
 
+    @property
+    def _view_source(self):
+        return self.ih if self._passthrough else None
+
     def read_device(self, count=None):
+        """The samples of the stream below, as that stream hands them over: a view of a device
+        task's frame cache lives until the next read of the task it came from."""
         if not self._passthrough or not hasattr(self.ih, 'read_device'):
             return super().read_device(count)
         count = self._prepare_read(count, None)
@@ -644,7 +653,13 @@ class _TimeSlice(Base):
     def _produces_on_device(self):
         return bool(getattr(self.ih, '_produces_on_device', False))
 
+    @property
+    def _view_source(self):
+        return self.ih
+
     def read_device(self, count=None):
+        """The window's samples as the stream below hands them over: a view of a device task's
+        frame cache lives until the next read of the task it came from."""
         count = self._prepare_read(count, None)
         self.ih.seek(self._first + self.offset)
         result = self.ih.read_device(count)

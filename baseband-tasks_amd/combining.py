@@ -17,7 +17,8 @@ import numpy as np
 from . import hip
 from . import units as u
 from .base import Task, TaskBase, META_ATTRIBUTES, _stream_rate
-from .device_task import DeviceTaskMixin, fetch_device
+from .device_task import DeviceTaskMixin, cache_producer, fetch_device, views_to_keep
+from .hip import DeviceArray
 from .shaping import index_map, _prod
 
 __all__ = ['CombineStreamsBase', 'CombineStreams', 'Concatenate', 'Stack']
@@ -38,6 +39,11 @@ class CombineStreamsBase(DeviceTaskMixin, TaskBase):
         Input data streams: same ``sample_rate`` and ``dtype``; the output
         covers the time from the latest start to the earliest stop.  Streams
         that are not on the device are uploaded as for every other task.
+        Streams that reach the same device task (the same task twice, windows
+        or relabelled copies of one task) are read one after the other, and the
+        view each read hands over lives until the next read of that task: all
+        but the last are copied (one device-to-device copy each); streams with
+        distinct producers are gathered from where they are.
     atol : float (seconds) or time quantity, optional
         Tolerance within which streams should be considered aligned.  By
         default, the lesser of 1 ns and 0.01 sample.
@@ -47,6 +53,7 @@ class CombineStreamsBase(DeviceTaskMixin, TaskBase):
         Additional arguments to be passed on to the base class.
     """
     _plan = None
+    _keep = None
     #: Route of the gather plan: 'auto', or 'run_copy', 'tile', 'direct' to force one (tests).
     ROUTE = 'auto'
 
@@ -137,8 +144,17 @@ class CombineStreamsBase(DeviceTaskMixin, TaskBase):
     def _compute_frames(self, first, last, out):
         start, stop = self._frame_span(first, last)
         used = set(np.unique(self._map_src).tolist())
-        xs = [fetch_device(ih, f + start, stop - start) if k in used else None
-              for k, (ih, f) in enumerate(zip(self.ihs, self._firsts))]
+        if self._keep is None:
+            # (inputs that share a producer: the next fetch from it may refill the frame cache
+            # that the view of this one lies in)
+            self._keep = views_to_keep([cache_producer(ih) if k in used else None
+                                        for k, ih in enumerate(self.ihs)])
+        xs = []
+        for k, (ih, f) in enumerate(zip(self.ihs, self._firsts)):
+            x = fetch_device(ih, f + start, stop - start) if k in used else None
+            if self._keep[k]:
+                x = DeviceArray(x.shape, x.dtype).copy_from_device(x)
+            xs.append(x)
         self._get_plan().execute(xs, out, stop - start)
 
     def close(self):

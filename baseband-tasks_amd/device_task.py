@@ -4,7 +4,10 @@ A GPU task computes whole output frames in HBM, many per C-ABI call, and
 keeps the last computed run of frames as its frame cache (the reference keeps
 one host frame: baseband_tasks/base.py:459-465).  ``read`` copies to the host
 only what the caller asked for; ``read_device`` returns a zero-copy view of
-the cache (valid until the next read on the same task).
+the cache.  Such a view lives until the next read of the task it came from
+-- through whatever time slices, reshapes and relabellings it was handed on --
+and the combining tasks copy the views of inputs that share a producer
+(`cache_producer`, `views_to_keep`).
 """
 import numpy as np
 
@@ -12,7 +15,7 @@ from . import hip
 from . import host_pipeline
 from .hip import DeviceArray
 
-__all__ = ['DeviceTaskMixin', 'fetch_device']
+__all__ = ['DeviceTaskMixin', 'fetch_device', 'cache_producer', 'views_to_keep']
 
 
 def fetch_device(ih, start, count):
@@ -38,6 +41,35 @@ def produces_on_device(ih):
     `DeviceStream`, an unpacking reader -- rather than upload what ``ih.read`` returns (the
     fallback every `Base` stream has)?"""
     return bool(getattr(ih, '_produces_on_device', False))
+
+
+def cache_producer(ih):
+    """The object whose next read may overwrite what ``ih.read_device`` hands out: the device
+    task whose frame cache the result is a view of, found by walking down through the wrappers
+    that pass the view of the stream below straight on (``_view_source``: a time slice, a
+    `SetAttribute` that only relabels, a shaping task that keeps every element in place).  None
+    if the result is the caller's to keep: an upload of a host stream, a slice of a stream that
+    is resident in HBM (`DeviceStream`), or a view of a block that is never written again
+    (`DeviceNoiseGenerator`).  A device source of another kind counts as its own producer."""
+    for _ in range(64):
+        if not produces_on_device(ih):
+            return None
+        below = getattr(ih, '_view_source', None)
+        if below is None:
+            if getattr(ih, '_resident', False) or getattr(ih, '_views_keep_their_block', False):
+                return None
+            return ih
+        ih = below
+    return ih
+
+
+def views_to_keep(producers):
+    """For the inputs of one run, fetched in order: must the view of input ``k`` be copied before
+    the next fetch, because a later input reads from the same producer (`cache_producer`) again?
+    Never for an input without a producer, for producers that differ, or for the last fetch from
+    a producer."""
+    return [p is not None and any(q is p for q in producers[k + 1:])
+            for k, p in enumerate(producers)]
 
 
 def host_request(ih, start, count):
@@ -164,8 +196,10 @@ class DeviceTaskMixin:
 
     def read_device(self, count=None):
         """Like ``read`` but the samples stay in HBM.  The result is a view of
-        this task's frame cache: consume it before reading from the task
-        again."""
+        this task's frame cache: it lives until the next read of this task,
+        directly or through a wrapper that hands its views on, so consume or
+        copy it before that (the combining tasks copy inputs that share a
+        producer)."""
         count = self._prepare_read(count, None)
         if count == 0:
             return DeviceArray((0,) + tuple(self.sample_shape), self._device_dtype)

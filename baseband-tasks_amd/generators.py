@@ -183,6 +183,9 @@ class DeviceNoiseGenerator(Base):
     the frame concerned is then made by NumPy and uploaded (``host_frames`` counts them; expect none
     in 10^12 samples)."""
     _produces_on_device = True
+    #: a cache fill takes a new block of the pool, so a view handed out earlier stays what it was
+    #: (`device_task.cache_producer`)
+    _views_keep_their_block = True
     #: relative margin of the comparisons left to NumPy (`hip.philox_normal`)
     _guard = hip.NOISE_GUARD
     _max_frames_per_call = None

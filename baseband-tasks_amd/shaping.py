@@ -98,7 +98,8 @@ class ChangeSampleShapeBase(DeviceTaskMixin, TaskBase):
     `GetItem` that keeps everything, an identity `Transpose`) no bytes move:
     ``read_device`` hands on the upstream device array under its new shape
     (same device pointer, no launch).  Like every ``read_device`` result that
-    is a view, it is valid until the next read from the stream it came from.
+    is a view, it lives until the next read of the task it came from; the
+    combining tasks copy inputs that share a producer.
 
     Parameters
     ----------
@@ -165,7 +166,13 @@ class ChangeSampleShapeBase(DeviceTaskMixin, TaskBase):
         else:
             self._get_plan().execute([x], out, stop - start)
 
+    @property
+    def _view_source(self):
+        return self.ih if self._identity and produces_on_device(self.ih) else None
+
     def read_device(self, count=None):
+        """As `DeviceTaskMixin.read_device`; where no element moves, the upstream device array
+        under the new shape, which lives until the next read of the task it came from."""
         if not (self._identity and produces_on_device(self.ih)):
             return super().read_device(count)
         count = self._prepare_read(count, None)

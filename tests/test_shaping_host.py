@@ -319,3 +319,74 @@ def test_abi_refusals():
     assert lib.bbt_gather_plan_destroy(plan) == 0 and lib.bbt_gather_plan_destroy(None) == 0
     with pytest.raises(hip.HipError, match='elem_bytes'):
         hip.GatherPlan([4], [0], [0], 3)
+
+
+# ---------------------------------------------------------------------------------------------
+# whose frame cache a ``read_device`` result lies in (device_task.cache_producer): the combining
+# tasks copy the views of inputs that share one
+def empty(shape=(640, 2, 3), spf=64, **kw):
+    return bt.EmptyStreamGenerator(shape, T0, 1e6, samples_per_frame=spf, **kw)
+
+
+def test_cache_producer_walks_through_the_wrappers_that_hand_views_on():
+    from baseband_tasks_amd.device_task import cache_producer, produces_on_device
+    host = empty(frequency=np.full((2, 3), 1e9), sideband=1)
+    assert cache_producer(host) is None and cache_producer(host[10:20]) is None      # (uploads: the caller's)
+    t = bt.Transpose(host, (2, 1))                      # moves elements: a device task with a frame cache
+    assert t.route == 'tile' and t._view_source is None and cache_producer(t) is t
+    wrappers = [t[64:200], t[64:200, :], bt.GetSlice(t, slice(64, 200)), bt.Reshape(t[64:200], (3, 2)),
+                bt.Reshape(t[64:200], (6,)), bt.Reshape(t, (2, 3)), bt.GetItem(t, slice(None)),
+                bt.GetItem(t[3:], (slice(0, 3), slice(None))), bt.Transpose(t[:128], (1, 2)),
+                bt.SetAttribute(t[64:192], frequency=np.full((3, 2), 2e9), sideband=-1),
+                bt.SetAttribute(t, start_time=bt.Time(T0) - 1e-3)[0:100]]
+    for w in wrappers:
+        assert produces_on_device(w) and w._view_source is not None, w
+        assert getattr(w, 'route', None) is None
+        assert cache_producer(w) is t, w
+    # mixed chains, several deep
+    deep = bt.SetAttribute(bt.Reshape(bt.GetItem(t[5:500], slice(None))[7:300, :], (6,)), polarization='X')[1:]
+    assert cache_producer(deep) is t
+    # a wrapper that moves elements, or over a host stream, owns the cache its views lie in
+    for own in (bt.GetItem(t, 0), t[64:200, 1], bt.Transpose(t[64:200], (2, 1)), bt.Reshape(host, (6,)),
+                bt.Stack([t, t]), bt.Stack([t, t])[3:9].ih):
+        assert cache_producer(own) is own and own is not t
+    assert cache_producer(bt.GetItem(t, 0)[1:5]).ih is t
+    # a SetAttribute that changes the framing reads on the host: its result is an upload
+    assert cache_producer(bt.SetAttribute(t, samples_per_frame=32)) is None
+    # distinct producers stay distinct, under whatever wrappers
+    t2 = bt.Transpose(host, (2, 1))
+    assert cache_producer(t2[:100]) is t2 and cache_producer(t2[:100]) is not cache_producer(t[:100])
+
+
+def test_cache_producer_exempts_resident_streams_and_fresh_blocks():
+    from baseband_tasks_amd.device_task import cache_producer
+
+    class Source(bt.EmptyStreamGenerator):
+        _produces_on_device = True
+
+    class Resident(Source):
+        _resident = True
+
+    assert bt.DeviceStream._resident and bt.DeviceNoiseGenerator._views_keep_their_block
+    args = ((64, 2), T0, 1e6)
+    other = Source(*args)
+    assert cache_producer(other) is other and cache_producer(other[3:9]) is other     # (unknown: its own)
+    assert cache_producer(Resident(*args)) is None and cache_producer(Resident(*args)[3:9]) is None
+    noise_dev = bt.DeviceNoiseGenerator((640, 2), T0, 1e6, 64, seed=1)
+    assert cache_producer(noise_dev) is None and cache_producer(bt.Reshape(noise_dev[5:], (2, 1))) is None
+
+
+def test_views_to_keep_marks_all_but_the_last_fetch_from_a_producer():
+    from baseband_tasks_amd.device_task import cache_producer, views_to_keep
+    a, b = object(), object()
+    assert views_to_keep([]) == []
+    assert views_to_keep([a]) == [False] and views_to_keep([None, None, None]) == [False] * 3
+    assert views_to_keep([a, b]) == [False, False]
+    assert views_to_keep([a, a]) == [True, False] and views_to_keep([a, a, a]) == [True, True, False]
+    assert views_to_keep([a, b, a, None, b, a]) == [True, True, True, False, False, False]
+    # as a combining task sees its inputs
+    host = empty()
+    t, t2 = bt.Transpose(host, (2, 1)), bt.Transpose(host, (2, 1))
+    ins = [t[0:100], host[0:100], t2[0:100], bt.Reshape(t[50:150], (3, 2)), t2[1:101, :]]
+    assert views_to_keep([cache_producer(ih) for ih in ins]) == [True, False, True, False, False]
+    assert not any(views_to_keep([cache_producer(ih) for ih in (t, t2, host, host)]))
