@@ -21,6 +21,7 @@ from .pfb import (sinc_hamming, PolyphaseFilterBank, PolyphaseFilterBankSamples,
                   InversePolyphaseFilterBank)
 from .functions import Square, Power
 from .integration import Integrate, Fold, PulseStack
+from .modulation import Modulate, modulate_samples
 from .conversion import Real2Complex
 from .shaping import (ChangeSampleShapeBase, ChangeSampleShape, Reshape, Transpose, ReshapeAndTranspose,
                       GetItem, GetSlice)

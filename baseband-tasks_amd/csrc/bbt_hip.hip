@@ -26,6 +26,7 @@
 #include "rtc.hpp"
 #include "fold_kernels.hpp"
 #include "phase_kernels.hpp"
+#include "modulate_kernels.hpp"
 #include "r2c_kernels.hpp"
 #include "gather_kernels.hpp"
 #include "pack_kernels.hpp"
@@ -35,7 +36,7 @@
 
 using namespace bbt;
 
-#define BBT_VERSION 160
+#define BBT_VERSION 161
 
 // ---------------------------------------------------------------------------
 // errors
@@ -3072,6 +3073,91 @@ extern "C" int bbt_phase_runs(const void* pieces_dev, int64_t n_piece, int n_coe
     HIP_TRY(hipMemcpyAsync(info, scalars, 16, hipMemcpyDeviceToHost, st));
     HIP_TRY(hipStreamSynchronize(st));
     return 0;
+}
+
+// ---------------------------------------------------------------------------
+// modulation by a pulse profile (modulate_kernels.hpp)
+static int modulate_args(const char* who, const void* in_dev, void* out_dev, int64_t n_in, int64_t n_float,
+                         const float* gain_dev, int64_t n_phase, int64_t gain_stride, ModArgs* A) {
+    ARG_TRY(in_dev && out_dev && gain_dev, "%s: null argument", who);
+    ARG_TRY(n_in >= 1 && n_float >= 1 && n_phase >= 1 && gain_stride >= 0, "%s: bad sizes", who);
+    ARG_TRY(n_float < (1ll << 30) && n_phase < (1ll << 31) && n_in <= (1ll << 41) / n_float,
+            "%s: too large for one call", who);
+    ARG_TRY(gain_stride == 0 || n_float == gain_stride || n_float == 2 * gain_stride,
+            "%s: the gain stride must be 0 or the elements of a sample (%lld floats, stride %lld)", who,
+            (long long)n_float, (long long)gain_stride);
+    ARG_TRY((((uintptr_t)in_dev | (uintptr_t)out_dev | (uintptr_t)gain_dev) & 3) == 0, "%s: arrays must be 4-byte aligned",
+            who);
+    A->in = (const float*)in_dev;
+    A->out = (float*)out_dev;
+    A->n_in = n_in;
+    A->n_float = n_in * n_float;
+    A->fps = (unsigned)n_float;
+    A->gain = gain_dev;
+    A->n_phase = n_phase;
+    A->gs = (unsigned)gain_stride;
+    A->cshift = gain_stride != 0 && n_float == 2 * gain_stride ? 1 : 0;
+    return 0;
+}
+
+// one launch: 16-byte accesses where both arrays allow them, whole samples per access where the
+// sample (and, for a gain per element, the gain table) allows that too
+template <int ROUTE>
+static int modulate_launch(const ModArgs& A, const ModRuns& R, const PhasePieces& P, hipStream_t st) {
+    const bool wide = (((uintptr_t)A.in | (uintptr_t)A.out) & 15) == 0;
+    const int w = wide ? 4 : 1;
+    const bool one = !wide || (A.fps % 4 == 0 && (A.gs == 0 || ((uintptr_t)A.gain & 15) == 0));
+    const long long n_acc = A.n_float / w;
+    const long long tiles = std::max(1ll, (n_acc + BBT_MOD_TILE - 1) / BBT_MOD_TILE);
+    const dim3 grid((unsigned)tiles), block(256);
+    if (!wide) hipLaunchKernelGGL((k_modulate<ROUTE, 1, true>), grid, block, 0, st, A, R, P);
+    else if (one) hipLaunchKernelGGL((k_modulate<ROUTE, 4, true>), grid, block, 0, st, A, R, P);
+    else hipLaunchKernelGGL((k_modulate<ROUTE, 4, false>), grid, block, 0, st, A, R, P);
+    HIP_TRY(hipGetLastError());
+    return 0;
+}
+
+extern "C" int bbt_modulate_runs(const void* in_dev, void* out_dev, int64_t n_in, int64_t n_float,
+                                 const float* gain_dev, int64_t n_phase, int64_t gain_stride,
+                                 const int64_t* run_begin_dev, const int64_t* run_bin_dev, int64_t n_run,
+                                 bbt_stream stream) {
+    ModArgs A;
+    if (modulate_args("bbt_modulate_runs", in_dev, out_dev, n_in, n_float, gain_dev, n_phase, gain_stride, &A) != 0)
+        return 1;
+    ARG_TRY(run_begin_dev && run_bin_dev, "bbt_modulate_runs: null argument");
+    ARG_TRY(n_run >= 1 && n_run <= n_in, "bbt_modulate_runs: bad sizes (%lld runs for %lld samples)", (long long)n_run,
+            (long long)n_in);
+    ModRuns R;
+    R.begin = (const long long*)run_begin_dev;
+    R.bin = (const long long*)run_bin_dev;
+    R.n_run = n_run;
+    PhasePieces P = {};
+    return modulate_launch<0>(A, R, P, (hipStream_t)stream);
+}
+
+extern "C" int bbt_modulate_pieces(const void* in_dev, void* out_dev, int64_t n_in, int64_t n_float,
+                                   const float* gain_dev, int64_t n_phase, int64_t gain_stride,
+                                   const void* pieces_dev, int64_t n_piece, int n_coeff, bbt_stream stream) {
+    ModArgs A;
+    if (modulate_args("bbt_modulate_pieces", in_dev, out_dev, n_in, n_float, gain_dev, n_phase, gain_stride, &A) != 0)
+        return 1;
+    ARG_TRY(pieces_dev, "bbt_modulate_pieces: null argument");
+    ARG_TRY(n_piece >= 1 && n_piece < (1ll << 31) && n_coeff >= 1 && n_coeff <= 64, "bbt_modulate_pieces: bad sizes");
+    ARG_TRY(((uintptr_t)pieces_dev & 7) == 0, "bbt_modulate_pieces: the pieces must be 8-byte aligned");
+    const long long* q = (const long long*)pieces_dev;
+    PhasePieces P;
+    P.lo = q;
+    P.m0 = q + (n_piece + 1);
+    P.row = P.m0 + n_piece;
+    P.dt0 = (const double*)(P.row + n_piece);
+    P.step = P.dt0 + n_piece;
+    P.ref_int = P.step + n_piece;
+    P.ref_frac = P.ref_int + n_piece;
+    P.coeff = P.ref_frac + n_piece;
+    P.n_piece = (int)n_piece;
+    P.n_coeff = n_coeff;
+    ModRuns R = {};
+    return modulate_launch<1>(A, R, P, (hipStream_t)stream);
 }
 
 // ---------------------------------------------------------------------------

@@ -99,6 +99,8 @@ SIGNATURES = {
     'bbt_phase_runs_work': [_i64, _i64, _i64, _pi64],
     'bbt_phase_runs': [_vp, _i64, _int, _i64, _i64, _i64, _vp, _i64, _i64, _i64, _i64, _i64, _vp, _vp, _vp, _vp,
                        _vp, _i64, _pi64, _vp],
+    'bbt_modulate_runs': [_vp, _vp, _i64, _i64, _vp, _i64, _i64, _vp, _vp, _i64, _vp],
+    'bbt_modulate_pieces': [_vp, _vp, _i64, _i64, _vp, _i64, _i64, _vp, _i64, _int, _vp],
     'bbt_philox_normal_work': [_i64, _i64, _pi64],
     'bbt_philox_normal': [_vp, _vp, _i64, _i64, _i64, C.c_double, _vp, _i64, _vp, _i64, _pi64, _pi64, _vp],
     'bbt_shift_plan_create': [_pvp, _int, _int, _pi32],
@@ -138,7 +140,7 @@ SIGNATURES = {
 }
 
 #: oldest libbbt_hip.so whose entry points and argument meanings this binding assumes
-MIN_LIB_VERSION = 160
+MIN_LIB_VERSION = 161
 
 _lib = None
 _lock = threading.Lock()
@@ -792,6 +794,14 @@ def fold_runs_device(in_dev, out_dev, n_elem, mode, slot_ptr, run_begin, run_end
                         run_end.ptr_to_read(), n_slot, n_out_f, scale, accumulate)
 
 
+def _piece_words(plan):
+    """The 8-byte words of the pieces of a plan (`~baseband_tasks_amd.fold_table.plan_pieces`),
+    as bbt_phase_runs and bbt_modulate_pieces read them."""
+    return np.concatenate([plan['lo'].astype(np.int64).view(np.float64), plan['m0'].astype(np.int64).view(np.float64),
+                           plan['row'].astype(np.int64).view(np.float64), plan['dt0'], plan['step'], plan['ref_int'],
+                           plan['ref_frac'], plan['coeff'].ravel()]).astype(np.float64, copy=False)
+
+
 def phase_runs(plan, n_phase, slot0=0, n_slot=None):
     """Run table of a chunk from polynomial phases, made on the GPU (bbt_phase_runs).
 
@@ -803,10 +813,7 @@ def phase_runs(plan, n_phase, slot0=0, n_slot=None):
     n_chunk_slot = n_row * int(n_phase)
     n_slot = n_chunk_slot + slot0 if n_slot is None else int(n_slot)
     n_coeff = plan['coeff'].shape[1]
-    words = np.concatenate([plan['lo'].astype(np.int64).view(np.float64), plan['m0'].astype(np.int64).view(np.float64),
-                            plan['row'].astype(np.int64).view(np.float64), plan['dt0'], plan['step'], plan['ref_int'],
-                            plan['ref_frac'], plan['coeff'].ravel()]).astype(np.float64, copy=False)
-    pieces = DeviceArray.from_host(words)
+    pieces = DeviceArray.from_host(_piece_words(plan))
     cell0 = np.concatenate(([0], np.cumsum(plan['n_cycle'] * int(n_phase))))
     n_cell = int(cell0[-1])
     rows = DeviceArray.from_host(np.concatenate([plan['k0'], plan['n_cycle'], cell0[:-1]]).astype(np.int64))
@@ -826,6 +833,64 @@ def phase_runs(plan, n_phase, slot0=0, n_slot=None):
                          f"describe it): status {info[1]}, {info[0]} runs for a capacity of {run_cap}")
     n_run = int(info[0])
     return slot_ptr, runs[0:1].reshape(run_cap)[:n_run], runs[1:2].reshape(run_cap)[:n_run], n_run, counts.to_host()
+
+
+def _modulate_sizes(who, in_dev, out_dev, n_elem, gain):
+    """Checks shared by `modulate_runs` and `modulate_pieces`: (n_in, floats per sample, n_phase,
+    gain stride)."""
+    n_elem = int(n_elem)
+    n_in = in_dev.shape[0] if in_dev.shape else 0
+    if in_dev.dtype not in (np.dtype(np.float32), np.dtype(np.complex64)) or out_dev.dtype != in_dev.dtype:
+        raise TypeError(f"{who}: input and output must both be float32 or both complex64")
+    if n_elem < 1 or n_in < 1 or in_dev.size != n_in * n_elem:
+        raise ValueError(f"{who}: input is not n_in >= 1 samples of n_elem elements")
+    if out_dev.size != in_dev.size:
+        raise ValueError(f"{who}: output is not the size of the input")
+    if gain.dtype != np.dtype(np.float32) or len(gain.shape) not in (1, 2) or gain.shape[0] < 1:
+        raise ValueError(f"{who}: the gains must be float32, (n_phase,) or (n_phase, n_elem)")
+    if len(gain.shape) == 2 and gain.shape[1] != n_elem:
+        raise ValueError(f"{who}: gains of {gain.shape[1]} elements for samples of {n_elem}")
+    n_float = n_elem * (2 if in_dev.dtype.kind == 'c' else 1)
+    return n_in, n_float, gain.shape[0], (n_elem if len(gain.shape) == 2 else 0)
+
+
+def modulate_runs(in_dev, out_dev, n_elem, gain, run_begin, run_bin):
+    """``out[n, e] = in[n, e] * gain[bin(n), e]`` (or ``gain[bin(n)]`` for gains of shape
+    (n_phase,)), with ``bin(n) = run_bin[r]`` for the run ``r`` that holds sample ``n`` (see
+    bbt_modulate_runs in include/bbt_hip.h).
+
+    ``gain`` is a float32 `DeviceArray`; ``run_begin`` / ``run_bin`` are host int64 arrays in time
+    order (checked here, then uploaded): the runs tile [0, n_in), the bins lie in [0, n_phase)."""
+    n_in, n_float, n_phase, stride = _modulate_sizes('modulate_runs', in_dev, out_dev, n_elem, gain)
+    run_begin = np.ascontiguousarray(run_begin, dtype=np.int64)
+    run_bin = np.ascontiguousarray(run_bin, dtype=np.int64)
+    if run_begin.ndim != 1 or run_begin.shape != run_bin.shape or len(run_begin) < 1:
+        raise ValueError("modulate_runs: run_begin and run_bin must be 1-d, of one length >= 1")
+    if run_begin[0] != 0 or run_begin[-1] >= n_in or np.any(np.diff(run_begin) <= 0):
+        raise ValueError("modulate_runs: the runs do not tile the input")
+    if run_bin.min() < 0 or run_bin.max() >= n_phase:
+        raise ValueError("modulate_runs: bins outside the profile")
+    n_run = len(run_begin)
+    table = DeviceArray.from_host(np.concatenate([run_begin, run_bin]))
+    tptr = table.ptr
+    check(lib().bbt_modulate_runs(in_dev.ptr_to_read(), out_dev.ptr, n_in, n_float, gain.ptr_to_read(), n_phase,
+                                  stride, tptr, tptr + 8 * n_run, n_run, _stream))
+    return out_dev
+
+
+def modulate_pieces(in_dev, out_dev, n_elem, gain, plan):
+    """`modulate_runs` with the bins evaluated on the GPU from polynomial pieces
+    (bbt_modulate_pieces): ``plan`` is what `~baseband_tasks_amd.fold_table.plan_pieces` returns
+    for the input's samples, whose pieces must tile [0, n_in)."""
+    n_in, n_float, n_phase, stride = _modulate_sizes('modulate_pieces', in_dev, out_dev, n_elem, gain)
+    lo = np.asarray(plan['lo'], dtype=np.int64)
+    n_piece = len(plan['row'])
+    if n_piece < 1 or len(lo) != n_piece + 1 or lo[0] != 0 or lo[-1] != n_in or np.any(np.diff(lo) <= 0):
+        raise ValueError("modulate_pieces: the pieces do not tile the input")
+    pieces = DeviceArray.from_host(_piece_words(plan))
+    check(lib().bbt_modulate_pieces(in_dev.ptr_to_read(), out_dev.ptr, n_in, n_float, gain.ptr_to_read(), n_phase,
+                                    stride, pieces.ptr, n_piece, int(plan['coeff'].shape[1]), _stream))
+    return out_dev
 
 
 #: relative margin inside which a comparison of the normal sampler that goes through exp / log1p is

@@ -389,6 +389,33 @@ int bbt_phase_runs(const void* pieces_dev, int64_t n_piece, int n_coeff, int64_t
                    int64_t* run_end_dev, int64_t* counts_dev, void* work_dev, int64_t work_bytes,
                    int64_t* info, bbt_stream stream);
 
+/* ---- modulation by a pulse profile ----------------------------------------------
+ * Replaces the per-frame callable of the reference's generic Task when it multiplies a stream by
+ * a pulse profile (base.py:798-889 with a callable as in tests/test_simulate.py:26-118), with the
+ * bin rule of Fold (integration.py:389-391) instead of one gain per frame:
+ *   out[n, e] = in[n, e] * gain[bin(n) * gain_stride + e]      0 <= n < n_in
+ * `in` and `out` hold n_in samples of n_float float32 each; a complex element is two floats that
+ * share a gain.  gain (float32, device) has n_phase rows of gain_stride floats: 0 (one gain per
+ * bin, n_phase floats in all), n_float (a gain per float32 element) or n_float / 2 (a gain per
+ * complex element).  A product is one float32 multiply: results do not depend on the launch.
+ * Accesses are 16 bytes wide where `in` and `out` are 16-byte aligned, whatever n_float (for a
+ * gain per element they stay whole only if n_float % 4 == 0 and gain is 16-byte aligned too);
+ * otherwise 4 bytes.  Asynchronous on `stream`; in == out is allowed.
+ *   bbt_modulate_runs    bin(n) = run_bin[r] for the run r with run_begin[r] <= n < run_begin[r+1]
+ *                        (int64 arrays in device memory; run_begin[0] = 0, strictly increasing,
+ *                        below n_in; 0 <= run_bin[r] < n_phase; n_run <= n_in)
+ *   bbt_modulate_pieces  bin(n) = k mod n_phase (non-negative), k the unwrapped bin of sample n of
+ *                        the polynomial pieces (pieces_dev, n_piece, n_coeff as for bbt_phase_runs,
+ *                        with lo[0] = 0 and lo[n_piece] = n_in; `row` is not used)
+ * Null pointers and sizes that are not positive are refused before anything is launched. */
+int bbt_modulate_runs(const void* in_dev, void* out_dev, int64_t n_in, int64_t n_float,
+                      const float* gain_dev, int64_t n_phase, int64_t gain_stride,
+                      const int64_t* run_begin_dev, const int64_t* run_bin_dev, int64_t n_run,
+                      bbt_stream stream);
+int bbt_modulate_pieces(const void* in_dev, void* out_dev, int64_t n_in, int64_t n_float,
+                        const float* gain_dev, int64_t n_phase, int64_t gain_stride,
+                        const void* pieces_dev, int64_t n_piece, int n_coeff, bbt_stream stream);
+
 /* ---- real streams to complex baseband: Real2Complex ---------------------------
  * Replaces Real2Complex.task (conversion.py:77-101): every frame of 2 M real samples of each of
  * the S streams (fft, one-sided spectrum, ifft, times exp(-i pi n / 2), every second sample) gives
