@@ -12,6 +12,7 @@ import baseband_tasks_amd as bt
 from baseband_tasks_amd import hip
 from baseband_tasks_amd import units as u
 from baseband_tasks_amd.fold_table import unwrapped_bin
+from fold_cases import numpy_fold
 
 pytestmark = pytest.mark.gpu
 
@@ -206,20 +207,6 @@ def test_integrate_stack(pulsar):
 
 
 # -- randomised parity against NumPy --------------------------------------------------
-def numpy_fold(x, edges, n_phase, ph, rate, t0):
-    """float64 fold of x[edges[0]:edges[-1]] with the per-row times of the reference."""
-    n_row = len(edges) - 1
-    out = np.zeros((n_row, n_phase) + x.shape[1:], np.complex128 if x.dtype.kind == 'c' else np.float64)
-    cnt = np.zeros((n_row, n_phase), np.int64)
-    for r in range(n_row):
-        n = np.arange(edges[r], edges[r + 1])
-        t = (t0 + edges[r] / rate) + (n - edges[r]) / rate
-        b = unwrapped_bin(ph(t), n_phase) % n_phase
-        np.add.at(out[r], b, x[n])
-        np.add.at(cnt[r], b, 1)
-    return out, cnt
-
-
 def _stream(rng, n, shape, dtype):
     x = rng.standard_normal((n,) + shape)
     if np.dtype(dtype).kind == 'c':
