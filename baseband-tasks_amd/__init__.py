@@ -22,6 +22,7 @@ from .pfb import (sinc_hamming, PolyphaseFilterBank, PolyphaseFilterBankSamples,
 from .functions import Square, Power
 from .integration import Integrate, Fold, PulseStack
 from .modulation import Modulate, modulate_samples
+from .rfi import SpectralKurtosis, Excise, sk_limits, spectral_kurtosis, excise_flags, excise_samples
 from .conversion import Real2Complex
 from .shaping import (ChangeSampleShapeBase, ChangeSampleShape, Reshape, Transpose, ReshapeAndTranspose,
                       GetItem, GetSlice)

@@ -27,6 +27,7 @@
 #include "fold_kernels.hpp"
 #include "phase_kernels.hpp"
 #include "modulate_kernels.hpp"
+#include "sk_kernels.hpp"
 #include "r2c_kernels.hpp"
 #include "gather_kernels.hpp"
 #include "pack_kernels.hpp"
@@ -36,7 +37,7 @@
 
 using namespace bbt;
 
-#define BBT_VERSION 161
+#define BBT_VERSION 162
 
 // ---------------------------------------------------------------------------
 // errors
@@ -3158,6 +3159,81 @@ extern "C" int bbt_modulate_pieces(const void* in_dev, void* out_dev, int64_t n_
     P.n_coeff = n_coeff;
     ModRuns R = {};
     return modulate_launch<1>(A, R, P, (hipStream_t)stream);
+}
+
+// ---------------------------------------------------------------------------
+// spectral kurtosis and excision (sk_kernels.hpp; the tiling is sk_geo.hpp's)
+static int sk_args(const char* who, const void* x_dev, int64_t n_block, int64_t n, int64_t n_elem, int is_complex,
+                   double averaged, int64_t group, bool aligned16, long long slab, SkArgs* A, SkGeo* g) {
+    ARG_TRY(n >= 2 && n <= BBT_SK_MAX_N, "%s: n must be 2 ... 65536 (got %lld)", who, (long long)n);
+    ARG_TRY(averaged > 0. && averaged <= 1e9, "%s: averaged must be positive", who);
+    const char* err = sk_geo(n_block, n, n_elem, is_complex != 0, group, aligned16, slab, g);
+    ARG_TRY(!err, "%s: %s", who, err ? err : "");
+    ARG_TRY(n_block * n <= (1ll << 40) / n_elem, "%s: too large for one call", who);
+    ARG_TRY(((uintptr_t)x_dev & (is_complex ? 7 : 3)) == 0, "%s: arrays must be aligned to their elements", who);
+    A->x = x_dev;
+    A->n_block = n_block, A->n = n, A->n_elem = n_elem;
+    A->averaged = averaged;
+    A->group = (int)group;
+    return 0;
+}
+
+#define BBT_SK_LAUNCH(KERNEL)                                                                          \
+    do {                                                                                               \
+        const dim3 grid((unsigned)(g.n_tile * g.n_zgroup)), block(BBT_SK_THREADS);                     \
+        if (is_complex && g.v == 2) hipLaunchKernelGGL((KERNEL<true, 2>), grid, block, 0, st, A, g);   \
+        else if (is_complex) hipLaunchKernelGGL((KERNEL<true, 1>), grid, block, 0, st, A, g);          \
+        else if (g.v == 4) hipLaunchKernelGGL((KERNEL<false, 4>), grid, block, 0, st, A, g);           \
+        else hipLaunchKernelGGL((KERNEL<false, 1>), grid, block, 0, st, A, g);                         \
+        HIP_TRY(hipGetLastError());                                                                    \
+    } while (0)
+
+extern "C" int bbt_sk_estimate(const void* x_dev, float* sk_dev, int64_t n_block, int64_t n, int64_t n_elem,
+                               int is_complex, double averaged, bbt_stream stream) {
+    ARG_TRY(x_dev && sk_dev, "bbt_sk_estimate: null argument");
+    ARG_TRY(((uintptr_t)sk_dev & 3) == 0, "bbt_sk_estimate: sk must be 4-byte aligned");
+    SkArgs A = {};
+    SkGeo g = {};
+    if (sk_args("bbt_sk_estimate", x_dev, n_block, n, n_elem, is_complex, averaged, 1, ((uintptr_t)x_dev & 15) == 0, 0,
+                &A, &g) != 0)
+        return 1;
+    A.sk = sk_dev;
+    hipStream_t st = (hipStream_t)stream;
+    BBT_SK_LAUNCH(k_sk_estimate);
+    return 0;
+}
+
+// bytes of a slab: BBT_SK_SLAB, or what the environment's BBT_SK_SLAB_KIB asks for (for measuring;
+// no value of the output depends on it)
+static long long sk_slab_bytes() {
+    const char* e = getenv("BBT_SK_SLAB_KIB");
+    if (e && *e) {
+        const long long kib = atoll(e);
+        if (kib >= 1 && kib <= (1 << 20)) return kib * 1024;
+    }
+    return BBT_SK_SLAB;
+}
+
+extern "C" int bbt_sk_excise(const void* x_dev, void* out_dev, int64_t n_block, int64_t n, int64_t n_elem,
+                             int is_complex, double averaged, float lo, float hi, int64_t group, float* sk_or_null,
+                             uint8_t* flags_or_null, bbt_stream stream) {
+    ARG_TRY(x_dev && out_dev, "bbt_sk_excise: null argument");
+    ARG_TRY(lo <= hi, "bbt_sk_excise: the limits must be ordered, lo <= hi");
+    ARG_TRY(((uintptr_t)sk_or_null & 3) == 0, "bbt_sk_excise: sk must be 4-byte aligned");
+    ARG_TRY(((uintptr_t)out_dev & (is_complex ? 7 : 3)) == 0, "bbt_sk_excise: arrays must be aligned to their elements");
+    SkArgs A = {};
+    SkGeo g = {};
+    const bool aligned16 = (((uintptr_t)x_dev | (uintptr_t)out_dev) & 15) == 0;
+    if (sk_args("bbt_sk_excise", x_dev, n_block, n, n_elem, is_complex, averaged, group, aligned16, sk_slab_bytes(), &A,
+                &g) != 0)
+        return 1;
+    A.out = out_dev;
+    A.sk = sk_or_null;
+    A.flags = flags_or_null;
+    A.lo = lo, A.hi = hi;
+    hipStream_t st = (hipStream_t)stream;
+    BBT_SK_LAUNCH(k_sk_excise);
+    return 0;
 }
 
 // ---------------------------------------------------------------------------

@@ -101,6 +101,8 @@ SIGNATURES = {
                        _vp, _i64, _pi64, _vp],
     'bbt_modulate_runs': [_vp, _vp, _i64, _i64, _vp, _i64, _i64, _vp, _vp, _i64, _vp],
     'bbt_modulate_pieces': [_vp, _vp, _i64, _i64, _vp, _i64, _i64, _vp, _i64, _int, _vp],
+    'bbt_sk_estimate': [_vp, _vp, _i64, _i64, _i64, _int, C.c_double, _vp],
+    'bbt_sk_excise': [_vp, _vp, _i64, _i64, _i64, _int, C.c_double, C.c_float, C.c_float, _i64, _vp, _vp, _vp],
     'bbt_philox_normal_work': [_i64, _i64, _pi64],
     'bbt_philox_normal': [_vp, _vp, _i64, _i64, _i64, C.c_double, _vp, _i64, _vp, _i64, _pi64, _pi64, _vp],
     'bbt_shift_plan_create': [_pvp, _int, _int, _pi32],
@@ -140,7 +142,7 @@ SIGNATURES = {
 }
 
 #: oldest libbbt_hip.so whose entry points and argument meanings this binding assumes
-MIN_LIB_VERSION = 161
+MIN_LIB_VERSION = 162
 
 _lib = None
 _lock = threading.Lock()
@@ -891,6 +893,66 @@ def modulate_pieces(in_dev, out_dev, n_elem, gain, plan):
     check(lib().bbt_modulate_pieces(in_dev.ptr_to_read(), out_dev.ptr, n_in, n_float, gain.ptr_to_read(), n_phase,
                                     stride, pieces.ptr, n_piece, int(plan['coeff'].shape[1]), _stream))
     return out_dev
+
+
+#: bounds of the spectral-kurtosis entry points (csrc/sk_geo.hpp)
+SK_MAX_N, SK_MAX_GROUP = 65536, 64
+
+
+def _sk_sizes(who, x, n, n_elem, averaged):
+    """Checks shared by `sk_estimate` and `sk_excise`: (n_block, n, n_elem, is_complex, averaged)."""
+    if not isinstance(x, DeviceArray):
+        raise TypeError(f"{who}: the input must be a DeviceArray, not {type(x).__name__}")
+    if x.dtype not in (np.dtype(np.float32), np.dtype(np.complex64)):
+        raise TypeError(f"{who}: the input must be float32 or complex64, not {x.dtype}")
+    n, n_elem, averaged = int(n), int(n_elem), float(averaged)
+    if not 2 <= n <= SK_MAX_N:
+        raise ValueError(f"{who}: n must be 2 ... {SK_MAX_N}, not {n}")
+    if not 0. < averaged <= 1e9:
+        raise ValueError(f"{who}: averaged must be positive, not {averaged}")
+    n_in = x.shape[0] if x.shape else 0
+    if n_elem < 1 or n_in < 1 or x.size != n_in * n_elem or n_in % n:
+        raise ValueError(f"{who}: the input is not whole blocks of {n} samples of {n_elem} elements "
+                         f"(shape {tuple(x.shape)})")
+    return n_in // n, n, n_elem, int(x.dtype.kind == 'c'), averaged
+
+
+def sk_estimate(x, n, n_elem, averaged=1., out=None):
+    """Spectral kurtosis of every block of ``n`` samples and every element of a float32 (powers) or
+    complex64 `DeviceArray` ``x`` of ``n_block * n`` samples of ``n_elem`` elements
+    (bbt_sk_estimate in include/bbt_hip.h; `rfi.spectral_kurtosis` is the NumPy restatement).
+    Returns float32 ``(n_block, n_elem)`` (``out`` if given)."""
+    n_block, n, n_elem, cplx, averaged = _sk_sizes('sk_estimate', x, n, n_elem, averaged)
+    if out is None:
+        out = DeviceArray((n_block, n_elem), np.float32)
+    elif not isinstance(out, DeviceArray) or out.dtype != np.dtype(np.float32) or out.size != n_block * n_elem:
+        raise ValueError(f"sk_estimate: out must be a float32 DeviceArray of {n_block * n_elem} values")
+    check(lib().bbt_sk_estimate(x.ptr_to_read(), out.ptr, n_block, n, n_elem, cplx, averaged, _stream))
+    return out
+
+
+def sk_excise(x, out, n, n_elem, limits, averaged=1., group=1, sk=None, flags=None):
+    """``out`` = ``x`` with every (block of ``n`` samples, group of ``group`` adjacent elements)
+    zeroed in which an element's spectral kurtosis lies outside ``limits = (lo, hi)``, float32
+    (bbt_sk_excise; `rfi.excise_samples` is the NumPy restatement).  ``sk``, ``flags``: None, or
+    `DeviceArray`s that receive the estimator, float32 ``(n_block, n_elem)``, and the flags,
+    uint8 ``(n_block, n_elem / group)``.  Returns ``out``."""
+    n_block, n, n_elem, cplx, averaged = _sk_sizes('sk_excise', x, n, n_elem, averaged)
+    if not isinstance(out, DeviceArray) or out.dtype != x.dtype or out.size != x.size:
+        raise ValueError("sk_excise: the output must be a DeviceArray of the input's dtype and size")
+    group = int(group)
+    if not 1 <= group <= SK_MAX_GROUP or n_elem % group:
+        raise ValueError(f"sk_excise: a group of {group} elements must divide {n_elem} and be at most {SK_MAX_GROUP}")
+    lo, hi = (float(np.float32(v)) for v in limits)
+    if not lo <= hi:
+        raise ValueError(f"sk_excise: the limits must be ordered, not {(lo, hi)}")
+    for name, arr, dtype, size in (('sk', sk, np.float32, n_block * n_elem),
+                                   ('flags', flags, np.uint8, n_block * (n_elem // group))):
+        if arr is not None and (not isinstance(arr, DeviceArray) or arr.dtype != np.dtype(dtype) or arr.size != size):
+            raise ValueError(f"sk_excise: {name} must be a {np.dtype(dtype)} DeviceArray of {size} values")
+    check(lib().bbt_sk_excise(x.ptr_to_read(), out.ptr, n_block, n, n_elem, cplx, averaged, lo, hi, group,
+                              None if sk is None else sk.ptr, None if flags is None else flags.ptr, _stream))
+    return out
 
 
 #: relative margin inside which a comparison of the normal sampler that goes through exp / log1p is

@@ -416,6 +416,30 @@ int bbt_modulate_pieces(const void* in_dev, void* out_dev, int64_t n_in, int64_t
                         const float* gain_dev, int64_t n_phase, int64_t gain_stride,
                         const void* pieces_dev, int64_t n_piece, int n_coeff, bbt_stream stream);
 
+/* ---- spectral kurtosis and excision: SpectralKurtosis, Excise ------------------
+ * x holds n_block blocks of n samples (2 <= n <= 65536) of n_elem elements, float32 (a power, is_complex
+ * = 0) or complex64 (is_complex = 1: p = re^2 + im^2).  Per block and element, in float64 without
+ * contraction: S1 = sum p and S2 = sum p^2, each summed in segments of 32 consecutive samples (in sample
+ * order from 0; the last segment may be shorter) whose sums are added in segment order from 0; then, with
+ * M = n and Nd = averaged (the complex-voltage powers summed into each value: 1 for |z|^2),
+ *   c = (M Nd + 1) / (M - 1);  t = S1 * S1;  r = S2 / t;  r = M * r;  r = r - 1;  sk = (float)(c * r)
+ * That order is the contract: results do not depend on the launch, the tiling or the alignment.
+ *   bbt_sk_estimate   sk[n_block][n_elem], float32
+ *   bbt_sk_excise     flag = !(sk >= lo && sk <= hi) (a NaN is flagged); the `group` adjacent elements
+ *                     e, group dividing n_elem and <= 64, that share e / group share the OR of their
+ *                     flags; out = x where the block is kept, +0 where it is flagged (both parts of a
+ *                     complex element).  Optionally also writes sk (as above) and flags, uint8
+ *                     [n_block][n_elem / group].  out may not overlap x unless out == x.
+ * Accesses are 16 bytes wide where the arrays are 16-byte aligned and n_elem is a multiple of 2 (complex64)
+ * or 4 (float32), else one element wide.  Asynchronous on `stream`.  Null x, out or (estimate) sk, n outside
+ * 2 ... 65536, a group that does not divide n_elem or exceeds 64, and lo > hi are refused before anything
+ * is launched. */
+int bbt_sk_estimate(const void* x_dev, float* sk_dev, int64_t n_block, int64_t n, int64_t n_elem,
+                    int is_complex, double averaged, bbt_stream stream);
+int bbt_sk_excise(const void* x_dev, void* out_dev, int64_t n_block, int64_t n, int64_t n_elem,
+                  int is_complex, double averaged, float lo, float hi, int64_t group, float* sk_or_null,
+                  uint8_t* flags_or_null, bbt_stream stream);
+
 /* ---- real streams to complex baseband: Real2Complex ---------------------------
  * Replaces Real2Complex.task (conversion.py:77-101): every frame of 2 M real samples of each of
  * the S streams (fft, one-sided spectrum, ifft, times exp(-i pi n / 2), every second sample) gives

@@ -1,0 +1,386 @@
+"""Host side of `SpectralKurtosis` and `Excise` (no GPU): the NumPy twin against a plain
+per-column loop in the two-level order, `sk_limits` against its formula, construction, metadata,
+framing and repr, the argument checks of the wrappers and the two C entry points, the kernels'
+tiling (csrc/sk_geo.hpp) walked on the host by a stand-alone program under sanitizers, and a guard
+on the shared cases of sk_cases.py."""
+import json
+import os
+import subprocess
+
+import numpy as np
+import pytest
+
+import baseband_tasks_amd as bt
+from baseband_tasks_amd import hip, rfi
+
+import sk_cases
+from sk_cases import CASES, IDS
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+CSRC = os.path.join(ROOT, 'baseband-tasks_amd', 'csrc')
+T0 = bt.Time('2010-11-12T13:14:15')
+RATE = 1e4
+
+
+def _stream(n=4000, sample_shape=(4, 2), dtype=np.complex64, spf=200, **kwargs):
+    return bt.HostStream(np.zeros((n,) + sample_shape, dtype), T0, RATE, samples_per_frame=spf, pin=False,
+                         **kwargs)
+
+
+# -- the rule ---------------------------------------------------------------------------------
+def _loop_sk(column, n, averaged):
+    """One block of one element in Python floats (IEEE doubles), as the issue words the rule."""
+    s1 = s2 = 0.
+    for t0 in range(0, n, 32):
+        a1 = a2 = 0.
+        for t in range(t0, min(t0 + 32, n)):
+            v = column[t]
+            if isinstance(v, (complex, np.complexfloating)):
+                re, im = float(np.float32(v.real)), float(np.float32(v.imag))
+                p = re * re + im * im
+            else:
+                p = float(np.float32(v))
+            a1 += p
+            a2 += p * p
+        s1 += a1
+        s2 += a2
+    m = float(n)
+    c = (m * averaged + 1.) / (m - 1.)
+    t = s1 * s1
+    r = s2 / t
+    r = m * r
+    r = r - 1.
+    return np.float32(c * r)
+
+
+@pytest.mark.parametrize('dtype, n, averaged', [(np.complex64, 31, 1.), (np.complex64, 100, 1.), (np.float32, 64, 4.),
+                                                (np.float32, 33, 0.5), (np.complex64, 2, 1.)])
+def test_twin_against_a_plain_loop(dtype, n, averaged):
+    rng = np.random.default_rng(5)
+    shape = (3 * n + 1, 2, 3)
+    x = rng.standard_normal(shape) * 1e3
+    x = (x + 1j * rng.standard_normal(shape)).astype(dtype) if dtype is np.complex64 else (x * x).astype(dtype)
+    got = rfi.spectral_kurtosis(x, n, averaged)
+    assert got.shape == (3, 2, 3) and got.dtype == np.float32
+    for b in range(3):
+        for i in range(2):
+            for j in range(3):
+                want = _loop_sk(x[b * n:(b + 1) * n, i, j], n, averaged)
+                assert got[b, i, j].view(np.uint32) == want.view(np.uint32), (b, i, j)
+    assert np.all(np.isfinite(got))
+
+
+def test_twin_flags_and_zeroes():
+    rng = np.random.default_rng(6)
+    n = 64
+    x = (rng.standard_normal((4 * n + 7, 3, 2)) + 1j * rng.standard_normal((4 * n + 7, 3, 2))).astype(np.complex64)
+    x[n:2 * n, 1, 0] = 2.                                # a carrier: sk = 0
+    x[2 * n:3 * n, 2, 1] = 0.                            # nothing: NaN
+    x[3 * n + 5, 0, 0] = np.inf
+    sk = rfi.spectral_kurtosis(x, n)
+    assert sk[1, 1, 0] == 0. and np.isnan(sk[2, 2, 1]) and np.isnan(sk[3, 0, 0])
+    limits = rfi.sk_limits(n)
+    flags = rfi.excise_flags(sk, limits)
+    want = np.zeros((4, 3, 2), bool)
+    want[1, 1, 0] = want[2, 2, 1] = want[3, 0, 0] = True
+    chance = flags & ~want                               # (3 sigma flags about 1 % of noise: none of 21 here)
+    assert not chance.any()
+    joined = rfi.excise_flags(sk, limits, join=1)
+    np.testing.assert_array_equal(joined, want.any(-1))
+    np.testing.assert_array_equal(rfi.excise_flags(sk, limits, join=2), want.any((-1, -2)))
+    out = rfi.excise_samples(x, n, limits, join=1)
+    assert out.shape == (4 * n, 3, 2) and out.dtype == np.complex64
+    keep = np.repeat(~joined, n, axis=0)[..., np.newaxis] & np.ones(2, bool)
+    assert sk_cases.same_bits(out[keep], x[:4 * n][keep])
+    assert not out[~keep].view(np.uint32).any()          # +0 in both parts
+    with pytest.raises(ValueError):
+        rfi.excise_flags(sk, limits, join=3)
+    with pytest.raises(ValueError):
+        rfi.excise_flags(sk, (2., 1.))
+    with pytest.raises(ValueError, match='at most 64'):
+        rfi.excise_samples(np.zeros((8, 5, 13), np.float32), 4, (0., 2.), join=2)
+    with pytest.raises(TypeError):
+        rfi.spectral_kurtosis(np.zeros((8, 2)), 4)
+    for n_bad in (1, 65537):
+        with pytest.raises(ValueError):
+            rfi.spectral_kurtosis(np.zeros((8, 2), np.float32), n_bad)
+
+
+@pytest.mark.parametrize('n, nsigma, averaged', [(16, 3., 1.), (1024, 3., 1.), (256, 4.5, 8.), (100, 2., 0.5),
+                                                 (65536, 3., 2.)])
+def test_limits_follow_the_formula(n, nsigma, averaged):
+    m, nd = float(n), float(averaged)
+    var = 2. * nd * (nd + 1.) * m ** 2 / ((m - 1.) * (m * nd + 2.) * (m * nd + 3.))
+    lo, hi = bt.sk_limits(n, nsigma, averaged)
+    assert lo.dtype == np.float32 and hi.dtype == np.float32
+    assert lo == np.float32(1. - nsigma * var ** 0.5) and hi == np.float32(1. + nsigma * var ** 0.5)
+    if averaged == 1.:
+        assert abs(var - 4. / m) < 20. / m ** 2                # (the familiar 4 / M, to first order)
+    with pytest.raises(ValueError):
+        bt.sk_limits(1)
+    with pytest.raises(ValueError):
+        bt.sk_limits(64, nsigma=0.)
+    with pytest.raises(ValueError):
+        bt.sk_limits(64, averaged=0.)
+
+
+def test_the_estimator_is_unbiased_for_noise():
+    """Noise of every kind `averaged` describes has mean 1 and the variance of `sk_limits`."""
+    rng = np.random.default_rng(8)
+    n, cols = 64, 4000
+    z = rng.standard_normal((8, n, cols)) ** 2
+    for averaged, p in ((1., z[:2].sum(0)), (4., z.sum(0)), (0.5, z[0])):
+        sk = rfi.spectral_kurtosis(p.astype(np.float32), n, averaged)[0].astype(np.float64)
+        lo, hi = rfi.sk_limits(n, 1., averaged)
+        sigma = (float(hi) - float(lo)) / 2.
+        assert abs(sk.mean() - 1.) < 5. * sigma / cols ** 0.5
+        assert abs(sk.std() / sigma - 1.) < 0.1
+
+
+# -- the tasks ----------------------------------------------------------------------------------
+def test_spectral_kurtosis_construction_and_metadata():
+    sh = _stream(frequency=np.arange(4.)[:, None] * 1e6 + 3e8, sideband=1, polarization=np.array(['X', 'Y']))
+    kh = bt.SpectralKurtosis(sh, 128)
+    assert kh.shape == (31, 4, 2) and kh.dtype == np.float32 and kh.samples_per_frame == 1
+    assert kh.sample_rate == sh.sample_rate / 128 and kh.start_time == sh.start_time
+    assert abs((kh.stop_time - sh.start_time) - 31 * 128 / RATE) < 1e-9
+    np.testing.assert_array_equal(kh.frequency, sh.frequency)
+    np.testing.assert_array_equal(kh.sideband, sh.sideband)
+    np.testing.assert_array_equal(kh.polarization, sh.polarization)
+    assert kh._produces_on_device
+    r = repr(kh).split('\nih:')[0]
+    assert r.startswith('SpectralKurtosis(ih') and 'n=128' in r and 'averaged' not in r and 'samples_per_frame' not in r
+    k2 = bt.SpectralKurtosis(sh, 100, averaged=0.5, samples_per_frame=8)
+    assert k2.shape == (40, 4, 2) and k2.samples_per_frame == 8
+    r = repr(k2).split('\nih:')[0]
+    assert 'averaged=0.5' in r and 'samples_per_frame=8' in r
+    assert k2._input_span(1, 3) == (sh, 800, 1600)
+    with pytest.raises(TypeError, match='float32'):
+        bt.SpectralKurtosis(_stream(dtype=np.int16), 16)
+    with pytest.raises(TypeError):
+        bt.SpectralKurtosis(_stream(dtype=np.complex128), 16)
+    with pytest.raises(ValueError, match='less than one block'):
+        bt.SpectralKurtosis(_stream(n=100), 128)
+    for n_bad in (1, 0, 65537):
+        with pytest.raises(ValueError):
+            bt.SpectralKurtosis(sh, n_bad)
+    with pytest.raises(ValueError):
+        bt.SpectralKurtosis(sh, 16, averaged=0.)
+    kh.close()
+    assert kh.closed
+
+
+def test_excise_construction_framing_and_repr():
+    sh = _stream(frequency=np.arange(4.)[:, None] * 1e6 + 3e8, sideband=1, polarization=np.array(['X', 'Y']))
+    eh = bt.Excise(sh, 128)
+    assert eh.shape == (31 * 128, 4, 2) and eh.dtype == np.complex64
+    assert eh.samples_per_frame == 256                   # the smallest multiple of 128 that is >= 200
+    assert eh.sample_rate == sh.sample_rate and eh.start_time == sh.start_time
+    np.testing.assert_array_equal(eh.frequency, sh.frequency)
+    np.testing.assert_array_equal(eh.polarization, sh.polarization)
+    assert eh.limits == bt.sk_limits(128) and all(v.dtype == np.float32 for v in eh.limits)
+    assert eh._produces_on_device and eh._view_source is None
+    r = repr(eh).split('\nih:')[0]
+    assert r.startswith('Excise(ih') and 'n=128' in r
+    for absent in ('limits', 'nsigma', 'averaged', 'join', 'samples_per_frame'):
+        assert absent not in r
+    e2 = bt.Excise(sh, 100, (0.5, 1.5), averaged=2., join=1, samples_per_frame=500)
+    assert e2.shape == (4000, 4, 2) and e2.samples_per_frame == 500 and e2.limits == (np.float32(0.5), np.float32(1.5))
+    r = repr(e2).split('\nih:')[0]
+    assert 'limits=(0.5, 1.5)' in r and 'averaged=2.0' in r and 'join=1' in r and 'samples_per_frame=500' in r
+    assert bt.Excise(sh, 100, nsigma=4.).limits == bt.sk_limits(100, 4.)
+    assert 'nsigma=4.0' in repr(bt.Excise(sh, 100, nsigma=4.))
+    assert bt.Excise(sh, 200).samples_per_frame == 200 and bt.Excise(sh, 1000).samples_per_frame == 1000
+    # a byte budget makes chunks of whole blocks
+    e2.excise_budget = 250 * 64
+    assert e2._chunk_samples() == 200
+    e2.excise_budget = 1
+    assert e2._chunk_samples() == 100
+    assert e2._input_span(0, 1) is None
+    e2.excise_budget = 1 << 20
+    assert e2._input_span(1, 3) == (sh, 500, 1000)
+    for spf in (150, 50, 0):
+        with pytest.raises(ValueError, match='multiple'):
+            bt.Excise(sh, 100, samples_per_frame=spf)
+    with pytest.raises(TypeError, match='float32'):
+        bt.Excise(_stream(dtype=np.int8), 16)
+    with pytest.raises(ValueError, match='less than one block'):
+        bt.Excise(_stream(n=100), 128)
+    with pytest.raises(ValueError):
+        bt.Excise(sh, 1)
+    with pytest.raises(ValueError):
+        bt.Excise(sh, 16, (2., 1.))
+    with pytest.raises(ValueError):
+        bt.Excise(sh, 16, join=3)
+    with pytest.raises(ValueError, match='at most 64'):
+        bt.Excise(_stream(sample_shape=(13, 5)), 16, join=2)
+    assert bt.Excise(_stream(sample_shape=(32, 2)), 16, join=2)._group == 64
+    assert eh.seek(300) == 300 and eh.tell() == 300
+
+
+# -- wrappers and C entry points: refusals before any launch --------------------------------------
+def _fake(shape, dtype):
+    d = hip.DeviceArray.__new__(hip.DeviceArray)       # (never dereferenced: checks come first)
+    d.shape, d.dtype = shape, np.dtype(dtype)
+    return d
+
+
+def test_wrappers_check_their_arguments():
+    x, out = _fake((64, 6), np.complex64), _fake((64, 6), np.complex64)
+    with pytest.raises(TypeError):
+        hip.sk_estimate(np.zeros((64, 6), np.float32), 16, 6)
+    with pytest.raises(TypeError):
+        hip.sk_estimate(_fake((64, 6), np.float64), 16, 6)
+    for n, n_elem in ((1, 6), (65537, 6), (24, 6), (16, 5), (16, 0)):
+        with pytest.raises(ValueError):
+            hip.sk_estimate(x, n, n_elem)
+        with pytest.raises(ValueError):
+            hip.sk_excise(x, out, n, n_elem, (0., 2.))
+    with pytest.raises(ValueError):
+        hip.sk_estimate(x, 16, 6, averaged=0.)
+    with pytest.raises(ValueError):
+        hip.sk_estimate(x, 16, 6, out=_fake((4, 5), np.float32))
+    with pytest.raises(ValueError):
+        hip.sk_excise(x, _fake((64, 6), np.float32), 16, 6, (0., 2.))
+    with pytest.raises(ValueError):
+        hip.sk_excise(x, _fake((48, 6), np.complex64), 16, 6, (0., 2.))
+    for group in (0, 4, 65):
+        with pytest.raises(ValueError):
+            hip.sk_excise(x, out, 16, 6, (0., 2.), group=group)
+    with pytest.raises(ValueError):
+        hip.sk_excise(x, out, 16, 6, (2., 1.))
+    with pytest.raises(ValueError):
+        hip.sk_excise(x, out, 16, 6, (np.nan, 1.))
+    with pytest.raises(ValueError):
+        hip.sk_excise(x, out, 16, 6, (0., 2.), sk=_fake((4, 6), np.float64))
+    with pytest.raises(ValueError):
+        hip.sk_excise(x, out, 16, 6, (0., 2.), group=2, flags=_fake((4, 6), np.uint8))
+
+
+def test_entry_points_validate_arguments():
+    lib = hip.lib()
+    assert lib.bbt_version() >= 162
+    buf = np.zeros(256, np.float32)
+    p = buf.ctypes.data + (-buf.ctypes.data) % 16
+    for args in ((None, p, 1, 16, 4, 1, 1., None), (p, None, 1, 16, 4, 1, 1., None)):
+        assert lib.bbt_sk_estimate(*args) != 0
+        assert b'bbt_sk_estimate: null' in lib.bbt_last_error()
+    for n in (1, 0, -4, 65537):
+        assert lib.bbt_sk_estimate(p, p, 1, n, 4, 1, 1., None) != 0
+        assert b'n must be 2 ... 65536' in lib.bbt_last_error()
+        assert lib.bbt_sk_excise(p, p, 1, n, 4, 1, 1., 0., 2., 1, None, None, None) != 0
+        assert b'bbt_sk_excise: n must be 2 ... 65536' in lib.bbt_last_error()
+    for args in ((p, p, 0, 16, 4, 1, 1., None), (p, p, 1, 16, 0, 1, 1., None), (p, p, -1, 16, 4, 0, 1., None)):
+        assert lib.bbt_sk_estimate(*args) != 0
+        assert b'empty axis' in lib.bbt_last_error()
+    assert lib.bbt_sk_estimate(p, p, 1, 16, 4, 1, 0., None) != 0 and b'averaged' in lib.bbt_last_error()
+    assert lib.bbt_sk_estimate(p, p, 1, 16, 4, 1, float('nan'), None) != 0 and b'averaged' in lib.bbt_last_error()
+    assert lib.bbt_sk_estimate(p + 4, p, 1, 16, 4, 1, 1., None) != 0 and b'aligned' in lib.bbt_last_error()
+    assert lib.bbt_sk_estimate(p, p + 2, 1, 16, 4, 0, 1., None) != 0 and b'aligned' in lib.bbt_last_error()
+    for args in ((None, p, 1, 16, 4, 1, 1., 0., 2., 1, None, None, None),
+                 (p, None, 1, 16, 4, 1, 1., 0., 2., 1, None, None, None)):
+        assert lib.bbt_sk_excise(*args) != 0
+        assert b'bbt_sk_excise: null' in lib.bbt_last_error()
+    for group, what in ((3, b'does not divide'), (0, b'1 ... 64'), (-2, b'1 ... 64'), (65, b'1 ... 64')):
+        assert lib.bbt_sk_excise(p, p, 1, 16, 130, 0, 1., 0., 2., group, None, None, None) != 0
+        assert what in lib.bbt_last_error()
+    assert lib.bbt_sk_excise(p, p, 1, 16, 4, 1, 1., 2., 1., 1, None, None, None) != 0
+    assert b'lo <= hi' in lib.bbt_last_error()
+    assert lib.bbt_sk_excise(p, p, 1, 16, 4, 1, 1., float('nan'), 1., 1, None, None, None) != 0
+    assert b'lo <= hi' in lib.bbt_last_error()
+    assert lib.bbt_sk_excise(p, p + 4, 1, 16, 4, 1, 1., 0., 2., 1, None, None, None) != 0
+    assert b'aligned' in lib.bbt_last_error()
+    assert lib.bbt_sk_excise(p, p, 1, 16, 4, 1, 1., 0., 2., 1, p + 2, None, None) != 0
+    assert b'aligned' in lib.bbt_last_error()
+    assert lib.bbt_sk_excise(p, p, 1 << 31, 16, 4, 1, 1., 0., 2., 1, None, None, None) != 0
+    assert lib.bbt_sk_excise(p, p, 1 << 24, 65536, 1 << 10, 1, 1., 0., 2., 1, None, None, None) != 0
+    assert b'too large' in lib.bbt_last_error()
+
+
+# -- the kernels' tiling, on the host ------------------------------------------------------------------
+def _geo_shapes():
+    """(n_block, n, n_elem, is_complex, group, 16-byte aligned, slab bytes): the shapes of the
+    cases, as the tasks launch them (whole, and from an odd sample of a `DeviceStream`, where an
+    odd-width float32 or complex64 stream is not aligned), the estimate's widest tiles (slab 0),
+    small slabs that force many tiles, and the widest groups."""
+    shapes = []
+    for c in CASES:
+        n_elem = int(np.prod(c.sample_shape, dtype=int))
+        g = int(np.prod(c.sample_shape[len(c.sample_shape) - c.join:], dtype=int))
+        n_block = min(c.samples // c.n, 5)
+        for aligned in (1, 0):
+            shapes.append((n_block, c.n, n_elem, int(c.dtype.kind == 'c'), g, aligned, 128 * 1024))
+        shapes.append((n_block, c.n, n_elem, int(c.dtype.kind == 'c'), 1, 1, 0))
+    shapes += [(3, 100, 1024, 1, 2, 1, 4096), (3, 4096, 8, 0, 1, 1, 1024), (2, 65536, 2, 1, 1, 1, 128 * 1024),
+               (3, 40, 640, 0, 64, 1, 128 * 1024), (3, 40, 192, 1, 64, 1, 128 * 1024), (7, 2, 63, 0, 63, 0, 128 * 1024),
+               (1, 70, 2048, 0, 1, 1, 0), (5, 33, 2046, 1, 1, 1, 0), (1, 2, 1, 0, 1, 1, 128 * 1024),
+               (40, 256, 2048, 1, 2, 1, 128 * 1024), (16, 4096, 2048, 1, 1, 1, 0)]
+    return shapes
+
+
+def test_kernel_tiling_on_the_host(tmp_path):
+    """Every access read once and stored once, every LDS index inside its array, every sk and flag
+    written once, segments added in order: the program exits non-zero otherwise, and the
+    sanitizers abort it on a wild index of its own."""
+    exe = str(tmp_path / 'sk_geo_check')
+    subprocess.check_call(['g++', '-O1', '-g', '-std=c++17', '-fsanitize=address,undefined',
+                           '-fno-sanitize-recover=undefined', '-I', CSRC,
+                           os.path.join(ROOT, 'tests', 'sk_geo_check.cpp'), '-o', exe])
+    shapes = _geo_shapes()
+    out = subprocess.run([exe] + [str(v) for shape in shapes for v in shape], stdout=subprocess.PIPE,
+                         stderr=subprocess.PIPE, text=True)
+    assert out.returncode == 0, out.stdout + out.stderr
+    plans = [json.loads(line) for line in out.stdout.splitlines()]
+    assert len(plans) == len(shapes)
+    for (n_block, n, n_elem, cplx, group, aligned, slab), g in zip(shapes, plans):
+        assert g['walk'] == 0, (n_block, n, n_elem, cplx, group, aligned, slab, g)
+        wide = 2 if cplx else 4
+        assert g['v'] == (wide if aligned and n_elem % wide == 0 else 1)
+        assert g['w'] % g['v'] == 0 and g['w'] % group == 0 and g['nx'] * g['ny'] * g['nz'] <= 256
+        assert g['ny'] <= -(-n // 32) and g['n_tile'] * g['w'] >= n_elem > (g['n_tile'] - 1) * g['w']
+        if slab and g['n_tile'] > 1:
+            # a slab of the asked size, or the narrowest tile: 128 bytes of a sample, whole groups and accesses
+            item = 8 if cplx else 4
+            unit = np.lcm(group, g['v'])
+            assert n * g['w'] * item <= slab or g['w'] <= -(-(128 // item) // unit) * unit
+    # the workload's layout: slabs of 128 KiB, 64 elements wide, a segment a thread; with only four
+    # blocks the tiles narrow to a cache line of a sample and a workgroup takes all four
+    at = shapes.index((40, 256, 2048, 1, 2, 1, 128 * 1024))
+    assert plans[at] == {'v': 2, 'w': 64, 'nx': 32, 'ny': 8, 'nz': 1, 'n_tile': 32, 'n_zgroup': 40, 'walk': 0}
+    at = shapes.index((4, 256, 2048, 1, 2, 1, 128 * 1024))
+    assert plans[at] == {'v': 2, 'w': 16, 'nx': 8, 'ny': 8, 'nz': 4, 'n_tile': 128, 'n_zgroup': 1, 'walk': 0}
+    # the estimate of few long blocks: narrower tiles rather than idle CUs
+    at = shapes.index((16, 4096, 2048, 1, 1, 1, 0))
+    assert plans[at]['w'] == 32 and plans[at]['ny'] == 16 and plans[at]['n_tile'] * plans[at]['n_zgroup'] == 1024
+    # what the library refuses
+    bad = subprocess.run([exe] + '1 1 4 1 1 1 0  1 16 4 1 3 1 0  1 16 130 0 65 1 0  0 16 4 1 1 1 0'.split(),
+                         stdout=subprocess.PIPE, text=True)
+    assert bad.returncode == 0
+    errors = [json.loads(line)['error'] for line in bad.stdout.splitlines()]
+    assert '65536' in errors[0] and 'divide' in errors[1] and '64' in errors[2] and 'empty' in errors[3]
+
+
+# -- a guard on the cases --------------------------------------------------------------------------------
+@pytest.mark.parametrize('case', CASES, ids=IDS)
+def test_cases_flag_some_keep_some_and_stay_clear_of_the_limits(case):
+    """A condition on the inputs, not a tolerance: with an estimator within a few ulp of a limit
+    the GPU tests would be testing the last bit of a division, not the kernels."""
+    x = sk_cases.data(case)
+    assert x.shape == (case.samples,) + case.sample_shape and x.dtype == case.dtype
+    sk, flags, out = sk_cases.expected(case)
+    n_block = case.samples // case.n
+    assert sk.shape == (n_block,) + case.sample_shape and out.shape == (n_block * case.n,) + case.sample_shape
+    assert np.all(np.isfinite(sk))
+    lo, hi = sk_cases.limits_of(case)
+    assert flags.any() and not flags.all()
+    assert (sk > hi).any() and ((sk < lo).any() or lo < 0.)      # on both sides, where the band has two
+    frac = flags.mean()
+    assert 0.05 < frac < 0.7, frac
+    for lim in (lo, hi):
+        gap = np.abs(sk.astype(np.float64) - np.float64(lim)) / np.spacing(np.abs(lim))
+        assert gap.min() > 16., (lim, gap.min())
+    # the zero pattern is the flags', the rest is the input's
+    keep = np.repeat(~flags, case.n, axis=0).reshape((n_block * case.n,) + flags.shape[1:] + (1,) * case.join)
+    keep = np.broadcast_to(keep, out.shape)
+    assert sk_cases.same_bits(out[keep], x[:n_block * case.n][keep])
+    assert not np.ascontiguousarray(out[~keep]).view(np.uint32).any()
