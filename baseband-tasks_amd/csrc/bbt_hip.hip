@@ -4246,9 +4246,10 @@ extern "C" int bbt_from_half(const void* in_dev, void* out_dev, int64_t n, bbt_s
 
 // ---------------------------------------------------------------------------
 // PSRFITS fold-mode rows (psrfits_kernels.hpp): float32 profiles (row, bin, chan, pol) <-> big-endian
-// int16 codes (row, pol, chan, bin) with a scale and an offset per (row, pol, chan).
+// int16 codes (row, pol, chan, bin) with a scale and an offset per (row, pol, chan).  The tiling is
+// psrfits_geo.hpp's; `x_dev` is the array of floats, read or written.
 static int psrfits_shape(const char* who, int64_t n_row, int64_t n_bin, int64_t n_chan, int64_t n_pol,
-                         long long* n_tile, int* tc) {
+                         const void* x_dev, const void* codes_dev, PsrFitsGeo* g) {
     ARG_TRY(n_row >= 0 && n_bin >= 1 && n_chan >= 1 && n_pol >= 1,
             "%s: %lld rows of %lld bins, %lld channels, %lld polarizations", who, (long long)n_row,
             (long long)n_bin, (long long)n_chan, (long long)n_pol);
@@ -4256,34 +4257,32 @@ static int psrfits_shape(const char* who, int64_t n_row, int64_t n_bin, int64_t 
             "%s: an axis of 2^31 or more elements", who);
     ARG_TRY((double)n_row * (double)n_bin * (double)(n_chan * n_pol) <= (double)BBT_PACK_MAX,
             "%s: more than 2^40 samples", who);
-    *tc = n_chan * n_pol >= 32 ? 32 : 4;           // (few columns: narrow tiles, long along the bins)
-    *n_tile = (n_chan * n_pol + *tc - 1) / *tc;
-    ARG_TRY(n_row * *n_tile < (1ll << 31), "%s: too many tiles for one call", who);
+    const char* bad = psrfits_geo(n_bin, n_chan, n_pol, ((uintptr_t)x_dev & 15u) == 0,
+                                  ((uintptr_t)codes_dev & 3u) == 0, g);
+    ARG_TRY(!bad, "%s: %s", who, bad ? bad : "");
+    ARG_TRY(n_row * g->n_tile < (1ll << 31), "%s: too many tiles for one call", who);
     return 0;
 }
 extern "C" int bbt_psrfits_encode(const void* x_dev, void* codes_dev, void* scl_dev, void* offs_dev,
                                   void* n_finite_dev, int64_t n_row, int64_t n_bin, int64_t n_chan,
                                   int64_t n_pol, bbt_stream stream) {
     ARG_TRY(x_dev && codes_dev && scl_dev && offs_dev && n_finite_dev, "bbt_psrfits_encode: null argument");
-    long long n_tile;
-    int tc;
-    if (psrfits_shape("bbt_psrfits_encode", n_row, n_bin, n_chan, n_pol, &n_tile, &tc)) return 1;
+    PsrFitsGeo g;
+    if (psrfits_shape("bbt_psrfits_encode", n_row, n_bin, n_chan, n_pol, x_dev, codes_dev, &g)) return 1;
     ARG_TRY((((uintptr_t)x_dev | (uintptr_t)scl_dev | (uintptr_t)offs_dev | (uintptr_t)n_finite_dev) & 3u) == 0 &&
                 ((uintptr_t)codes_dev & 1u) == 0,
             "bbt_psrfits_encode: pointers must be aligned to their elements");
     if (n_row == 0) return 0;
-    const bool vec = ((uintptr_t)x_dev & 15u) == 0 && ((uintptr_t)codes_dev & 3u) == 0 &&
-                     (n_chan * n_pol) % 4 == 0 && n_bin % 2 == 0;
 #define BBT_PSR_ENC(T_, V_)                                                                                   \
-    hipLaunchKernelGGL((k_psrfits_encode<T_, V_>), dim3((unsigned)(n_row * n_tile)), dim3(BBT_PSRFITS_THREADS), \
+    hipLaunchKernelGGL((k_psrfits_encode<T_, V_>), dim3((unsigned)(n_row * g.n_tile)), dim3(BBT_PSRFITS_THREADS), \
                        0, (hipStream_t)stream, (const float*)x_dev, (unsigned short*)codes_dev,               \
                        (float*)scl_dev, (float*)offs_dev, (int*)n_finite_dev, (long long)n_bin,               \
-                       (long long)n_chan, (long long)n_pol, n_tile)
-    if (tc == 32) {
-        if (vec) BBT_PSR_ENC(32, true);
+                       (long long)n_chan, (long long)n_pol, g.n_tile)
+    if (g.tc == 32) {
+        if (g.vec) BBT_PSR_ENC(32, true);
         else BBT_PSR_ENC(32, false);
     } else {
-        if (vec) BBT_PSR_ENC(4, true);
+        if (g.vec) BBT_PSR_ENC(4, true);
         else BBT_PSR_ENC(4, false);
     }
 #undef BBT_PSR_ENC
@@ -4294,26 +4293,23 @@ extern "C" int bbt_psrfits_decode(const void* codes_dev, const void* scl_dev, co
                                   const void* wts_dev, float zero_off, void* out_dev, int64_t n_row,
                                   int64_t n_bin, int64_t n_chan, int64_t n_pol, bbt_stream stream) {
     ARG_TRY(codes_dev && scl_dev && offs_dev && out_dev, "bbt_psrfits_decode: null argument");
-    long long n_tile;
-    int tc;
-    if (psrfits_shape("bbt_psrfits_decode", n_row, n_bin, n_chan, n_pol, &n_tile, &tc)) return 1;
+    PsrFitsGeo g;
+    if (psrfits_shape("bbt_psrfits_decode", n_row, n_bin, n_chan, n_pol, out_dev, codes_dev, &g)) return 1;
     ARG_TRY((((uintptr_t)out_dev | (uintptr_t)scl_dev | (uintptr_t)offs_dev | (uintptr_t)wts_dev) & 3u) == 0 &&
                 ((uintptr_t)codes_dev & 1u) == 0,
             "bbt_psrfits_decode: pointers must be aligned to their elements");
     ARG_TRY(zero_off == zero_off, "bbt_psrfits_decode: zero_off is not a number");
     if (n_row == 0) return 0;
-    const bool vec = ((uintptr_t)out_dev & 15u) == 0 && ((uintptr_t)codes_dev & 3u) == 0 &&
-                     (n_chan * n_pol) % 4 == 0 && n_bin % 2 == 0;
 #define BBT_PSR_DEC(T_, V_)                                                                                   \
-    hipLaunchKernelGGL((k_psrfits_decode<T_, V_>), dim3((unsigned)(n_row * n_tile)), dim3(BBT_PSRFITS_THREADS), \
+    hipLaunchKernelGGL((k_psrfits_decode<T_, V_>), dim3((unsigned)(n_row * g.n_tile)), dim3(BBT_PSRFITS_THREADS), \
                        0, (hipStream_t)stream, (const unsigned short*)codes_dev, (const float*)scl_dev,       \
                        (const float*)offs_dev, (const float*)wts_dev, zero_off, (float*)out_dev,              \
-                       (long long)n_bin, (long long)n_chan, (long long)n_pol, n_tile)
-    if (tc == 32) {
-        if (vec) BBT_PSR_DEC(32, true);
+                       (long long)n_bin, (long long)n_chan, (long long)n_pol, g.n_tile)
+    if (g.tc == 32) {
+        if (g.vec) BBT_PSR_DEC(32, true);
         else BBT_PSR_DEC(32, false);
     } else {
-        if (vec) BBT_PSR_DEC(4, true);
+        if (g.vec) BBT_PSR_DEC(4, true);
         else BBT_PSR_DEC(4, false);
     }
 #undef BBT_PSR_DEC

@@ -24,14 +24,14 @@
 //
 // VEC: 16-byte loads / stores of floats (x / out 16-byte aligned, n_chan * n_pol a multiple of 4)
 // and 4-byte accesses of code pairs (codes 4-byte aligned, n_bin even); otherwise scalar accesses.
+// Which instantiation runs and the shape of its tile are psrfits_geo.hpp's.
 // Index arithmetic is 64-bit across the array.
 #pragma once
 #include <hip/hip_runtime.h>
 
-namespace bbt {
+#include "psrfits_geo.hpp"
 
-#define BBT_PSRFITS_THREADS 256
-#define BBT_PSRFITS_TILE 4096            // samples of a tile: TC columns x TB bins
+namespace bbt {
 
 __device__ __forceinline__ bool psr_finite(float x) {
     return (__float_as_uint(x) & 0x7f800000u) != 0x7f800000u;
@@ -93,9 +93,10 @@ __global__ __launch_bounds__(BBT_PSRFITS_THREADS) void k_psrfits_encode(
     float* __restrict__ offs, int* __restrict__ n_finite, long long n_bin, long long n_chan, long long n_pol,
     long long n_tile) {
     constexpr int NT = BBT_PSRFITS_THREADS;
-    constexpr int CPT = VEC ? 4 : 1;                 // columns of a thread
-    constexpr int NX = TC / CPT, NY = NT / NX;       // threads across the columns, along the bins
-    constexpr int TB = BBT_PSRFITS_TILE / TC, NP = TB / 2, PITCH = NP + 1;
+    constexpr PsrFitsTile T = psrfits_tile(TC, VEC);
+    constexpr int CPT = T.cpt;                       // columns of a thread
+    constexpr int NX = T.nx, NY = T.ny;              // threads across the columns, along the bins
+    constexpr int TB = T.tb, NP = T.np, PITCH = T.enc_pitch;
     static_assert(NX >= 1 && NX * NY == NT && (NY & (NY - 1)) == 0 && NP % 2 == 0, "tile shape");
     __shared__ unsigned s_tile[TC * PITCH];
     __shared__ float s_mn[NT * CPT], s_mx[NT * CPT];
@@ -199,9 +200,10 @@ __global__ __launch_bounds__(BBT_PSRFITS_THREADS) void k_psrfits_decode(
     const float* __restrict__ wts, float zero_off, float* __restrict__ out, long long n_bin, long long n_chan,
     long long n_pol, long long n_tile) {
     constexpr int NT = BBT_PSRFITS_THREADS;
-    constexpr int CPT = VEC ? 4 : 1;
-    constexpr int NX = TC / CPT, NY = NT / NX;
-    constexpr int TB = BBT_PSRFITS_TILE / TC, NP = TB / 2, PITCH = TB + 1;
+    constexpr PsrFitsTile T = psrfits_tile(TC, VEC);
+    constexpr int CPT = T.cpt;
+    constexpr int NX = T.nx, NY = T.ny;
+    constexpr int TB = T.tb, NP = T.np, PITCH = T.dec_pitch;
     static_assert(NX >= 1 && NX * NY == NT, "tile shape");
     __shared__ float s_tile[TC * PITCH];
     __shared__ float s_scl[TC], s_offs[TC], s_w[TC];

@@ -10,14 +10,18 @@ import pytest
 import baseband_tasks_amd as bt
 from baseband_tasks_amd import hip, psrfits
 from baseband_tasks_amd import units as u
+import psrfits_cases as pc
 from test_psrfits_host import ARCHIVE, READ_OUT, profiles
 
 pytestmark = pytest.mark.gpu
 
-#: (rows, bins, chan, pol): the fixture's shape; odd bins and a minor axis smaller than any tile;
-#: ragged in both directions; one bin; many tiles (16 MiB)
-SHAPES = [(1, 2048, 1, 1), (2, 5, 3, 4), (3, 33, 70, 2), (1, 1, 7, 1), (2, 1024, 512, 4)]
-SHIFTED = (1, 64, 16, 4)             # as a view 4 bytes into an allocation: the unaligned path
+#: (rows, bins, chan, pol), from tests/psrfits_cases.py, where the host tests prove which instantiations
+#: and edges of the tiling they reach
+SHAPES = pc.FOLD_SHAPES
+SHIFTED = pc.FOLD_SHIFTED            # as a view 4 bytes into an allocation: the unaligned path
+SHIFTED_CODES = pc.FOLD_SHIFTED_CODES    # codes 2 bytes into their allocation, the floats aligned
+#: (in the order in which the tests got their names)
+PARAMS = pc.FOLD_OLD + [SHIFTED] + pc.FOLD_NEW
 
 
 @pytest.fixture(scope='module', autouse=True)
@@ -26,14 +30,14 @@ def _need_gpu():
         pytest.fail("no GPU / libbbt_hip.so: the -m gpu suite must run on an MI355X")
 
 
-def shifted(a):
-    """``a`` in HBM as a view that starts 4 bytes into its allocation."""
+def shifted(a, by=4):
+    """``a`` in HBM as a view that starts ``by`` bytes into its allocation."""
     flat = np.ascontiguousarray(a).ravel()
-    per = 4 // flat.dtype.itemsize
+    per = by // flat.dtype.itemsize
     room = hip.DeviceArray((flat.size + per,), flat.dtype)
     view = room[per:]
     view.copy_from_host(flat)
-    assert view.ptr % 16 == 4
+    assert view.ptr % 16 == by
     return view.reshape(a.shape)
 
 
@@ -53,7 +57,7 @@ def same_bytes(got, want):
     assert bad.size == 0, (bad.size, bad[:8])
 
 
-@pytest.mark.parametrize('shape', SHAPES + [SHIFTED])
+@pytest.mark.parametrize('shape', PARAMS)
 def test_encode_is_byte_exact(cases, shape):
     x, want = cases[shape]
     dev = shifted(x) if shape == SHIFTED else hip.DeviceArray.from_host(x)
@@ -63,7 +67,44 @@ def test_encode_is_byte_exact(cases, shape):
         same_bytes(g.to_host(), np.ascontiguousarray(w))
 
 
-@pytest.mark.parametrize('shape', SHAPES + [SHIFTED])
+def test_encode_into_codes_off_a_dword(cases):
+    """Aligned profiles, through the C ABI into codes that start 2 bytes into their allocation: a shape
+    that has float4 loads and dword stores otherwise runs the scalar kernel because of that pointer
+    alone; nothing is stored before the first code or after the last."""
+    x, want = cases[SHIFTED_CODES]
+    n_row, n_bin, n_chan, n_pol = SHIFTED_CODES
+    dev = hip.DeviceArray.from_host(x)
+    room = hip.DeviceArray((want[0].size + 2,), np.dtype('>i2'))
+    room.copy_from_host(np.full(room.size, 0x5a5a, np.dtype('>i2')))
+    scl, offs = hip.DeviceArray(want[1].shape, np.float32), hip.DeviceArray(want[2].shape, np.float32)
+    n_finite = hip.DeviceArray(want[3].shape, np.int32)
+    assert dev.ptr % 16 == 0 and (room.ptr + 2) % 4 == 2
+    hip.check(hip.lib().bbt_psrfits_encode(dev.ptr, room.ptr + 2, scl.ptr, offs.ptr, n_finite.ptr, n_row, n_bin,
+                                           n_chan, n_pol, None))
+    back = room.to_host()
+    assert back[0] == 0x5a5a and back[-1] == 0x5a5a
+    got = back[1:-1].reshape(want[0].shape), scl.to_host(), offs.to_host(), n_finite.to_host()
+    for g, w in zip(got, want):
+        same_bytes(g, np.ascontiguousarray(w))
+
+
+def test_decode_of_codes_off_a_dword(cases):
+    """The same the other way: codes 2 bytes into their allocation, ``out`` aligned."""
+    shape = SHIFTED_CODES
+    _, (codes, scl, offs, _) = cases[shape]
+    d_codes, d_scl, d_offs = shifted(codes, 2), hip.DeviceArray.from_host(scl), hip.DeviceArray.from_host(offs)
+    got = hip.psrfits_decode(d_codes, d_scl, d_offs)
+    assert got.ptr % 16 == 0
+    same_bytes(got.to_host(), psrfits.decode_rows(codes, scl, offs))
+    wts = np.random.default_rng(3).integers(0, 3, (shape[0], shape[2])).astype(np.float32) * np.float32(0.7)
+    out = hip.DeviceArray((shape[0] * shape[1] * shape[2] * shape[3] + 1,), np.float32)
+    view = out[:out.size - 1]
+    res = hip.psrfits_decode(d_codes, d_scl, d_offs, hip.DeviceArray.from_host(wts), zero_off=0.5, out=view)
+    assert res.ptr == view.ptr and res.ptr % 16 == 0
+    same_bytes(res.to_host().reshape(shape), psrfits.decode_rows(codes, scl, offs, wts, zero_off=0.5))
+
+
+@pytest.mark.parametrize('shape', PARAMS)
 def test_decode_is_exact(cases, shape):
     _, (codes, scl, offs, _) = cases[shape]
     up = shifted if shape == SHIFTED else hip.DeviceArray.from_host
@@ -165,6 +206,37 @@ def test_fold_streams_into_an_archive(folded, tmp_path):
     # half a code step, and the roundings of coder and decoder: tests/test_psrfits_host.py
     scl = psrfits.encode_rows(profiles4)[1].astype(np.float64).transpose(0, 2, 1)      # (row, chan, pol)
     bound = 0.51 * scl + 4 * 2. ** -23 * np.abs(profiles4).max(axis=1)
+    err = np.abs(back.astype(np.float64) - profiles4).max(axis=1)
+    assert np.all(np.isfinite(profiles4)) and np.all(err <= bound), (err / bound).max()
+
+
+def test_full_stokes_fold_of_few_channels_streams_into_an_archive(tmp_path):
+    """5 channels x 4 polarizations with 64 phase bins: 20 columns, so one thread owns the four
+    columns of a tile and 256 threads run along the bins (<4,vec>), under the writer."""
+    rng = np.random.default_rng(12)
+    z = (rng.standard_normal((1 << 15, 5, 2)) + 1j * rng.standard_normal((1 << 15, 5, 2))).astype(np.complex64)
+    sh = bt.DeviceStream(hip.DeviceArray.from_host(z), T0, RATE, samples_per_frame=1 << 12,
+                         frequency=(400. + np.arange(5))[:, None] * u.MHz, sideband=1, polarization=['X', 'Y'])
+    fold = bt.Fold(bt.Power(sh), 64, phase, step=1 << 13)             # (2.7 turns a row: no empty bin)
+    assert fold.shape == (4, 64, 5, 4)
+    profiles4 = fold.read()
+    name, host_name = str(tmp_path / 'fold.fits'), str(tmp_path / 'host.fits')
+    fold.seek(0)
+    with psrfits.open(name, 'w', template=fold) as fw:
+        fold.read(out=fw)
+        assert fw.tell() == 4
+    with psrfits.open(host_name, 'w', template=fold) as fw:
+        fw.write(profiles4[:3])
+        fw.write(profiles4[3:])
+    with open(name, 'rb') as a, open(host_name, 'rb') as b:
+        assert a.read() == b.read()
+    codes, scl, offs, _ = psrfits.encode_rows(profiles4)
+    with psrfits.open(name, weighted=False) as fh:
+        assert fh.shape == fold.shape and fh.dtype == fold.dtype
+        back = fh.read()
+    same_bytes(back, psrfits.decode_rows(codes, scl, offs))
+    # half a code step, and the roundings of coder and decoder: tests/test_psrfits_host.py
+    bound = 0.51 * scl.astype(np.float64).transpose(0, 2, 1) + 4 * 2. ** -23 * np.abs(profiles4).max(axis=1)
     err = np.abs(back.astype(np.float64) - profiles4).max(axis=1)
     assert np.all(np.isfinite(profiles4)) and np.all(err <= bound), (err / bound).max()
 

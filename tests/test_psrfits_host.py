@@ -1,8 +1,10 @@
 """`bt.psrfits` without a GPU: the FITS layer on the reference's real archive (tests/golden/
 B1855+09.430.PUPPI.11y.x.sum.sm, with psrchive's read-out of it in B1855_nano.npz: the data of the
 reference's own test_psrfits_read.py), the NumPy coding `encode_rows` / `decode_rows` that the
-kernels are held to, and the bytes of a file written from host pieces, found with a card walker of
-this test's own."""
+kernels are held to, the bytes of a file written from host pieces, found with a card walker of
+this test's own, the tiling of the kernels (csrc/psrfits_geo.hpp) walked on the host by a stand-alone
+program under sanitizers, and the ledger of which instantiations and edges of that tiling the GPU
+cases of tests/psrfits_cases.py reach."""
 import os
 
 import numpy as np
@@ -11,6 +13,7 @@ import pytest
 import baseband_tasks_amd as bt
 from baseband_tasks_amd import psrfits
 from baseband_tasks_amd import units as u
+import psrfits_cases as pc
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 ARCHIVE = os.path.join(ROOT, 'tests', 'golden', 'B1855+09.430.PUPPI.11y.x.sum.sm')
@@ -331,3 +334,76 @@ def test_reader_refuses_two_subints_and_search_mode(written, tmp_path):
         psrfits.open(search)
     with pytest.raises(OSError, match='FITS'):
         psrfits.open(READ_OUT)
+
+
+# -- the kernels' tiling, on the host ------------------------------------------------------------
+@pytest.fixture(scope='module')
+def geo_check(tmp_path_factory):
+    return pc.compile_check('psrfits_geo_check', tmp_path_factory.mktemp('psrfits_geo'))
+
+
+def geo_shape(run):
+    _, (_, n_bin, n_chan, n_pol), x_aligned, codes_aligned = run
+    return n_bin, n_chan, n_pol, x_aligned, codes_aligned
+
+
+def test_kernel_tiling_on_the_host(geo_check):
+    """Every LDS index inside its array, the tree reading written cells only, every float and every
+    code touched once a pass, no vector access across the end of a row or off its alignment: the
+    program exits non-zero otherwise, and the sanitizers abort it on a wild index of its own.  On
+    what the GPU tests launch, and on a sweep over the edges of both tilings: every column count
+    to 70 with the bin counts around 1, a bin tile of the wide kernels (128), two, and one of the
+    narrow kernels (1024); every bin count to 260 and from 1020 to 1030 with the column counts
+    around a thread's four, a tile (32) and two."""
+    shapes = [geo_shape(run) for run in pc.fold_runs()]
+    edge_bins = [b for b in range(1, 1031) if min(abs(b - e) for e in (1, 128, 256, 1024)) <= 3]
+    edge_cols = [c for c in range(1, 71) if min(abs(c - e) for e in (4, 32, 64)) <= 3]
+    for bins in list(range(1, 261)) + list(range(1020, 1031)):
+        for cols in range(1, 71):
+            if bins not in edge_bins and cols not in edge_cols:
+                continue
+            n_pol = next(p for p in (4, 3, 2, 1) if cols % p == 0)
+            shapes.append((bins, cols // n_pol, n_pol, 1, 1))
+            if bins % 2 == 0 and cols % 4 == 0:              # (else the aligned run is scalar already)
+                shapes += [(bins, cols // n_pol, n_pol, 0, 1), (bins, cols // n_pol, n_pol, 1, 0)]
+    plans = pc.run_check(geo_check, shapes, through_stdin=True)
+    for (n_bin, n_chan, n_pol, x_aligned, codes_aligned), g in zip(shapes, plans):
+        assert g['walk'] == 0, (n_bin, n_chan, n_pol, x_aligned, codes_aligned, g)
+        assert g['tc'] == (32 if n_chan * n_pol >= 32 else 4) and g['n_tile'] == -(-n_chan * n_pol // g['tc'])
+        assert g['vec'] == int(x_aligned and codes_aligned and n_chan * n_pol % 4 == 0 and n_bin % 2 == 0)
+        assert g['tb'] * g['tc'] == 4096 and g['nx'] * g['ny'] == 256 and g['nx'] * (4 if g['vec'] else 1) == g['tc']
+        assert g['enc_pitch'] == g['tb'] // 2 + 1 and g['dec_pitch'] == g['tb'] + 1
+    assert plans[4] == {'tc': 32, 'vec': 1, 'n_tile': 64, 'tb': 128, 'nx': 8, 'ny': 32, 'enc_pitch': 65,
+                        'dec_pitch': 129, 'walk': 0}
+    # what the library refuses, given as arguments
+    errors = pc.run_check(geo_check, [(0, 1, 1, 1, 1), (4, 1 << 16, 1 << 16, 1, 1)])
+    assert 'empty' in errors[0]['error'] and '2^31' in errors[1]['error']
+
+
+# -- which paths of the kernels the GPU cases take -------------------------------------------------
+@pytest.fixture(scope='module')
+def geo(geo_check):
+    """(bins, chan, pol, floats aligned, codes aligned) -> the launcher's geometry, for every GPU run
+    and its aligned twin."""
+    shapes = sorted({s for run in pc.fold_runs() for s in (geo_shape(run), geo_shape(run)[:3] + (1, 1))})
+    plans = dict(zip(shapes, pc.run_check(geo_check, shapes)))
+    assert all(g['walk'] == 0 for g in plans.values())
+    return plans.__getitem__
+
+
+def test_gpu_cases_take_every_path(geo):
+    """The ledger: every (tc, vec) instantiation, ragged last column tiles of the wide kernels with
+    float4 and with scalar accesses, and 1, 2, odd, fewer than a tile's, a multiple of a tile's and
+    more than a tile's bins, the even ones with vector accesses."""
+    took = pc.fold_ledger(pc.fold_runs(), geo)
+    for path, names in took.items():
+        print(f'{path}: {", ".join(names)}')
+    assert pc.uncovered(took) == []
+
+
+def test_every_new_gpu_case_is_needed(geo):
+    """Without any one of the cases added for the ledger, a path is left uncovered."""
+    for shape in pc.FOLD_NEW:
+        rest = pc.fold_runs([s for s in pc.FOLD_SHAPES if s != shape])
+        assert pc.uncovered(pc.fold_ledger(rest, geo)), shape
+    assert pc.uncovered(pc.fold_ledger(pc.fold_runs(shifted_codes=False), geo))

@@ -13,18 +13,20 @@ import pytest
 import baseband_tasks_amd as bt
 from baseband_tasks_amd import hip, psrfits
 from baseband_tasks_amd import units as u
+import psrfits_cases as pc
 from test_psrfits_search_host import flat, noise
 
 pytestmark = pytest.mark.gpu
 
-#: ((nrow, nsblk, nchan, npol), nbits): one tile of 64 columns at every width (the 1-bit rows leave as
-#: bytes, the others as dwords); a byte a spectrum; 48 columns, not a power of two, nsblk neither;
-#: one sample a row; few columns, time across the lanes, more samples than a coding tile; 16 tiles
-CASES = [((3, 64, 16, 4), 8), ((3, 64, 16, 4), 4), ((3, 64, 16, 4), 2), ((3, 64, 16, 4), 1),
-         ((2, 32, 8, 1), 1), ((2, 48, 24, 2), 4), ((2, 48, 24, 2), 8), ((1, 1, 16, 2), 8),
-         ((2, 8192, 8, 2), 8), ((2, 64, 1024, 4), 8)]
-SHIFTED = ((2, 64, 16, 4), 8)         # input 4 bytes, codes 1 byte into their allocations: byte accesses
-IDS = [f'{s[0]}x{s[1]}x{s[2]}x{s[3]}-{b}bit' for s, b in CASES + [SHIFTED]]
+#: ((nrow, nsblk, nchan, npol), nbits), from tests/psrfits_cases.py, where the host tests prove which
+#: instantiations and edges of the tiling they reach
+CASES = pc.SEARCH_CASES
+SHIFTED = pc.SEARCH_SHIFTED_OLD       # input 4 bytes, codes 1 byte into their allocations: byte accesses
+SHIFTED_CODES = pc.SEARCH_SHIFTED_NEW    # codes 1 byte into their allocation: byte accesses of rows that have dwords
+IDS = [pc.search_id(c) for c in CASES]
+#: (shape, nbits, codes shifted) of every decode
+DECODES = [c + (False,) for c in CASES] + [c + (True,) for c in pc.SEARCH_SHIFTED]
+DECODE_IDS = IDS + [pc.search_id(c, True) for c in pc.SEARCH_SHIFTED]
 
 
 @pytest.fixture(scope='module', autouse=True)
@@ -37,7 +39,7 @@ def _need_gpu():
 def cases():
     """(shape, nbits) -> (samples, what `encode_search_rows` makes of them), made once."""
     out = {}
-    for shape, nbits in CASES + [SHIFTED]:
+    for shape, nbits in CASES + [SHIFTED]:                 # (the other shifted cases are among CASES)
         x = noise(shape, seed=sum(shape) + nbits)
         out[shape, nbits] = x, psrfits.encode_search_rows(flat(x), shape[1], nbits)
     return out
@@ -84,7 +86,7 @@ def check_encode(x, want, got, nsblk, nbits):
 
 
 # -- 1. encode ---------------------------------------------------------------------------------------
-@pytest.mark.parametrize('shape, nbits', CASES, ids=IDS[:-1])
+@pytest.mark.parametrize('shape, nbits', CASES, ids=IDS)
 def test_encode(cases, shape, nbits):
     x, want = cases[shape, nbits]
     got = hip.psrsearch_encode(hip.DeviceArray.from_host(flat(x)), shape[1], nbits, psrfits.SEARCH_NSIGMA[nbits])
@@ -111,20 +113,39 @@ def test_encode_of_unaligned_views(cases):
                  nsblk, nbits)
 
 
+@pytest.mark.parametrize('shape, nbits', SHIFTED_CODES, ids=[pc.search_id(c, True) for c in SHIFTED_CODES])
+def test_encode_into_unaligned_codes(cases, shape, nbits):
+    """Rows whose shape allows dword stores, through the C ABI into codes that start 1 byte into their
+    allocation: stored byte by byte, nothing before the first code or after the last."""
+    x, want = cases[shape, nbits]
+    n_row, nsblk, n_chan, n_pol = shape
+    dev = hip.DeviceArray.from_host(flat(x))
+    room = hip.DeviceArray((want[0].size + 2,), np.uint8)
+    room.copy_from_host(np.full(room.size, 0xa5, np.uint8))
+    scl, offs = hip.DeviceArray(want[1].shape, np.float32), hip.DeviceArray(want[2].shape, np.float32)
+    n_finite = hip.DeviceArray(want[3].shape, np.int32)
+    hip.check(hip.lib().bbt_psrsearch_encode(dev.ptr, room.ptr + 1, scl.ptr, offs.ptr, n_finite.ptr, n_row, nsblk,
+                                             n_chan, n_pol, nbits, psrfits.SEARCH_NSIGMA[nbits], None))
+    back = room.to_host()
+    assert back[0] == 0xa5 and back[-1] == 0xa5
+    check_encode(x, want, [back[1:-1].reshape(want[0].shape), scl.to_host(), offs.to_host(), n_finite.to_host()],
+                 nsblk, nbits)
+
+
 # -- 2. decode ---------------------------------------------------------------------------------------
-@pytest.mark.parametrize('shape, nbits', CASES + [SHIFTED], ids=IDS)
-def test_decode_is_exact(cases, shape, nbits):
+@pytest.mark.parametrize('shape, nbits, codes_shifted', DECODES, ids=DECODE_IDS)
+def test_decode_is_exact(cases, shape, nbits, codes_shifted):
     _, (codes, scl, offs, _) = cases[shape, nbits]
     n_row, nsblk, n_chan, n_pol = shape
     dims = (nsblk, n_chan, n_pol)
-    d_codes = shifted(codes, 1) if (shape, nbits) == SHIFTED else hip.DeviceArray.from_host(codes)
+    d_codes = shifted(codes, 1) if codes_shifted else hip.DeviceArray.from_host(codes)
     d_scl, d_offs = hip.DeviceArray.from_host(scl), hip.DeviceArray.from_host(offs)
     got = hip.psrsearch_decode(d_codes, d_scl, d_offs, None, 0., nbits, dims)
     assert got.shape == (n_row * nsblk, n_chan, n_pol)
     same_bytes(got.to_host(), psrfits.decode_search_rows(codes, scl, offs, nbits=nbits))
     wts = np.random.default_rng(3).integers(0, 3, (n_row, n_chan)).astype(np.float32) * np.float32(0.7)
     out = hip.DeviceArray((n_row * nsblk * n_chan * n_pol + 1,), np.float32)
-    view = out[1:] if (shape, nbits) == SHIFTED else out[:out.size - 1]
+    view = out[1:] if codes_shifted else out[:out.size - 1]
     res = hip.psrsearch_decode(d_codes, d_scl, d_offs, hip.DeviceArray.from_host(wts), 0.5, nbits, dims, out=view)
     assert res.ptr == view.ptr
     same_bytes(res.to_host().reshape(got.shape), psrfits.decode_search_rows(codes, scl, offs, wts, 0.5, nbits))
@@ -200,6 +221,47 @@ def test_waterfall_streams_into_a_file(waterfall, tmp_path, nbits):
     inside = (x >= offs) & (x <= offs + (2 ** nbits - 1) * scl)
     err = np.abs(decoded.reshape(x.shape) - x)
     assert np.all(np.isfinite(spectrum)) and np.all(err[inside] <= ((0.5 + 2. ** -12) * scl * np.ones_like(x))[inside])
+
+
+# -- 3b. ragged channel tiles under the writer ---------------------------------------------------------
+RAGGED_NSBLK = 40
+
+
+@pytest.mark.parametrize('n_chan, nbits', [(96, 1), (72, 2)])
+def test_ragged_spectrum_streams_into_a_file(tmp_path, n_chan, nbits):
+    """96 channels x 4 polarizations at 1 bit (dword stores, channel tiles 64 + 32) and 72 x 4 at 2 bits
+    (byte stores, 64 + 8), rows of 40 samples: written once from device pieces and once by the host
+    route, the two files are the same byte for byte, and the file reads back as the twin decodes it."""
+    rng = np.random.default_rng(n_chan + nbits)
+    z = (rng.standard_normal((10 * RAGGED_NSBLK, n_chan, 2))
+         + 1j * rng.standard_normal((10 * RAGGED_NSBLK, n_chan, 2))).astype(np.complex64)
+    voltages = bt.DeviceStream(hip.DeviceArray.from_host(z), T0, 1. * u.kHz, samples_per_frame=2 * RAGGED_NSBLK,
+                               frequency=(400. + 0.5 * np.arange(n_chan))[:, None] * u.MHz, sideband=1,
+                               polarization=['X', 'Y'])
+    stream = bt.Power(voltages)
+    assert stream.shape == (10 * RAGGED_NSBLK, n_chan, 4)
+    spectrum = stream.read()
+    name, host_name = str(tmp_path / 'device.fits'), str(tmp_path / 'host.fits')
+    keys = dict(template=stream, nbits=nbits, nsblk=RAGGED_NSBLK)
+    stream.seek(0)
+    with psrfits.open_search(name, 'w', **keys) as fw:
+        stream.read(out=fw)
+        assert fw.tell() == 10 * RAGGED_NSBLK
+    with psrfits.open_search(host_name, 'w', **keys) as fw:
+        fw.write(spectrum[:3 * RAGGED_NSBLK])
+        fw.write(spectrum[3 * RAGGED_NSBLK:])
+    with open(name, 'rb') as a, open(host_name, 'rb') as b:
+        assert a.read() == b.read()
+    rows = table(name)
+    data = np.array(rows['DATA']).reshape(10, RAGGED_NSBLK, 4, -1)
+    want = psrfits.encode_search_rows(spectrum, RAGGED_NSBLK, nbits)
+    same_bytes(data, want[0])
+    assert len(np.unique(psrfits.unpack_codes(data, nbits))) == 2 ** nbits         # (every level is in use)
+    with psrfits.open_search(name) as fh:
+        assert fh.shape == stream.shape and fh.dtype == stream.dtype and fh.samples_per_frame == RAGGED_NSBLK
+        assert fh.nbits == nbits
+        got = fh.read()
+    same_bytes(got, psrfits.decode_search_rows(data, rows['DAT_SCL'], rows['DAT_OFFS'], rows['DAT_WTS'], nbits=nbits))
 
 
 # -- 4. argument checks ----------------------------------------------------------------------------------

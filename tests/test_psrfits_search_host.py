@@ -1,8 +1,9 @@
 """PSRFITS search mode without a GPU: the bit order of packed codes pinned from the PSRFITS
 definition, the NumPy coding `encode_search_rows` / `decode_search_rows` that the kernels are held
 to, the bytes of a file written from host pieces (found with the card walker of
-test_psrfits_host.py), the writer's refusals, and the tiling of the kernels
-(csrc/psrsearch_geo.hpp) walked on the host by a stand-alone program under sanitizers."""
+test_psrfits_host.py), the writer's refusals, the tiling of the kernels (csrc/psrsearch_geo.hpp)
+walked on the host by a stand-alone program under sanitizers, and the ledger of which instantiations
+and edges of that tiling the GPU cases of tests/psrfits_cases.py reach."""
 import json
 import os
 import subprocess
@@ -13,10 +14,9 @@ import pytest
 import baseband_tasks_amd as bt
 from baseband_tasks_amd import psrfits
 from baseband_tasks_amd import units as u
+import psrfits_cases as pc
 from test_psrfits_host import WIDTHS, walk
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CSRC = os.path.join(ROOT, 'baseband-tasks_amd', 'csrc')
 F32 = np.float32
 
 
@@ -335,22 +335,26 @@ def test_writer_refuses_what_it_cannot_store(tmp_path):
 
 
 # -- the kernels' tiling, on the host ----------------------------------------------------------------------
-#: (nsblk, nchan, npol, nbits, codes 4-byte aligned): the shapes of tests/test_psrfits_search_gpu.py,
-#: the usual 1024 x 4 at every width, ragged last tiles, three and 32 polarizations
+#: (nsblk, nchan, npol, nbits, codes 4-byte aligned): the first shapes of tests/test_psrfits_search_gpu.py,
+#: the usual 1024 x 4 at every width, ragged last tiles, three and 32 polarizations; then everything
+#: that the GPU tests launch today (tests/psrfits_cases.py)
 GEO_SHAPES = [(64, 16, 4, 8, 1), (64, 16, 4, 4, 1), (64, 16, 4, 2, 1), (64, 16, 4, 1, 1), (64, 16, 4, 8, 0),
               (32, 8, 1, 1, 1), (48, 24, 2, 4, 1), (48, 24, 2, 8, 1), (1, 16, 2, 8, 1), (8192, 8, 2, 8, 1),
               (64, 1024, 4, 8, 1), (64, 1024, 4, 4, 1), (64, 1024, 4, 2, 1), (64, 1024, 4, 1, 1), (64, 1024, 4, 2, 0),
               (10, 21, 3, 8, 1), (10, 96, 3, 4, 1), (10, 8, 32, 1, 1), (10, 40, 5, 2, 1), (7, 4096, 1, 1, 1),
               (7, 100, 1, 8, 1), (7, 72, 4, 1, 1), (5, 1000, 2, 4, 0)]
+GEO_SHAPES += [shape for _, shape in pc.search_runs() if shape not in GEO_SHAPES]
 
 
-def test_kernel_tiling_on_the_host(tmp_path):
+@pytest.fixture(scope='module')
+def geo_check(tmp_path_factory):
+    return pc.compile_check('psrsearch_geo_check', tmp_path_factory.mktemp('psrsearch_geo'))
+
+
+def test_kernel_tiling_on_the_host(geo_check):
     """Every LDS index inside the tile, every column and every stored byte owned once: the
     program exits non-zero otherwise, and the sanitizers abort it on a wild index of its own."""
-    exe = str(tmp_path / 'psrsearch_geo_check')
-    subprocess.check_call(['g++', '-O1', '-g', '-std=c++17', '-fsanitize=address,undefined',
-                           '-fno-sanitize-recover=undefined', '-I', CSRC,
-                           os.path.join(ROOT, 'tests', 'psrsearch_geo_check.cpp'), '-o', exe])
+    exe = geo_check
     args = [str(v) for shape in GEO_SHAPES for v in shape]
     out = subprocess.run([exe] + args, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True)
     assert out.returncode == 0, out.stdout + out.stderr
@@ -369,3 +373,45 @@ def test_kernel_tiling_on_the_host(tmp_path):
     assert bad.returncode == 0
     errors = [json.loads(line)['error'] for line in bad.stdout.splitlines()]
     assert 'nbits' in errors[0] and 'multiple of 8' in errors[1] and 'polarizations' in errors[2]
+
+
+# -- which paths of the kernels the GPU cases take ---------------------------------------------------------
+@pytest.fixture(scope='module')
+def geo(geo_check):
+    """(nsblk, nchan, npol, nbits, aligned) -> the launcher's geometry, for every GPU run and its
+    aligned twin."""
+    shapes = sorted({s[:4] + (a,) for _, s in pc.search_runs() for a in (s[4], 1)})
+    plans = dict(zip(shapes, pc.run_check(geo_check, shapes)))
+    assert all(g['walk'] == 0 for g in plans.values())
+    return plans.__getitem__
+
+
+def test_gpu_cases_take_every_path(geo):
+    """The ledger: every (nbits, vec) instantiation, ragged last tiles and tiles beyond the LDS skew at
+    every sub-byte width with dword and with byte stores, three polarizations, a thread count a column
+    that is no power of two, and a row shorter than, a multiple of and several times longer than a
+    coding tile."""
+    took = pc.search_ledger(pc.search_runs(), geo)
+    for path, names in took.items():
+        print(f'{path}: {", ".join(names)}')
+    assert pc.uncovered(took) == []
+    # what the issue tabulated for the new shapes
+    assert geo((40, 96, 4, 1, 1)) == {'ct': 64, 'unit': 32, 'vec': 1, 'ny': 1, 'pol_pitch': 72, 'ts': 28, 'n_tile': 2,
+                                      'walk': 0}
+    assert geo((40, 96, 4, 2, 1))['unit'] == 16 and geo((40, 80, 4, 4, 1))['unit'] == 8
+    assert [geo((40, 72, 4, b, 1))['vec'] for b in (1, 2)] == [0, 0] and geo((40, 66, 4, 4, 1))['vec'] == 0
+    g = geo((50, 100, 3, 8, 1))
+    assert (g['ct'], g['pol_pitch'], g['vec'], g['n_tile']) == (84, 97, 1, 2) and geo((50, 100, 3, 2, 1))['vec'] == 0
+    g = geo((50, 8, 3, 8, 1))
+    assert (g['ny'], g['pol_pitch']) == (10, 33)
+    assert geo((600, 8, 2, 8, 1))['ts'] == 256
+
+
+def test_every_new_gpu_case_is_needed(geo):
+    """Without any one of the cases added for the ledger, a path is left uncovered."""
+    for case in pc.SEARCH_NEW:
+        rest = pc.search_runs([c for c in pc.SEARCH_CASES if c != case])
+        assert pc.uncovered(pc.search_ledger(rest, geo)), case
+    for case in pc.SEARCH_SHIFTED_NEW:
+        rest = pc.search_runs(shifted=[c for c in pc.SEARCH_SHIFTED if c != case])
+        assert pc.uncovered(pc.search_ledger(rest, geo)), case
