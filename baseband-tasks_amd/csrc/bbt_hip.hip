@@ -23,6 +23,7 @@
 #include "big_kernels.hpp"
 #include "gen2_host.hpp"
 #include "gen_host.hpp"
+#include "osm_geo.hpp"
 #include "rtc.hpp"
 #include "fold_kernels.hpp"
 #include "phase_kernels.hpp"
@@ -65,8 +66,6 @@ static int fail(const char* fmt, ...) {
     do {                   \
         if (!(cond)) return fail(__VA_ARGS__); \
     } while (0)
-
-static bool is_pow2(int64_t n) { return n > 0 && (n & (n - 1)) == 0; }
 
 // ---------------------------------------------------------------------------
 // twiddle tables, per device
@@ -160,35 +159,9 @@ static int get_wroot(cf** out) {
     return 0;
 }
 
-static bool fft_len_ok(int64_t n) { return is_pow2(n) && n >= 256 && n <= 4096; }
-
 // ---- lengths 2^a 3^b 5^c 7^d (fft_generic.hpp) ------------------------------
-// (stage lists, workgroup size, split and tile rules: gen_host.hpp)
-static int rtc_mode() {                     // 0 off, 1 on, 2 required
-    const char* e = getenv("BBT_RTC");
-    if (!e || !*e) return 1;
-    if (!strcmp(e, "0")) return 0;
-    if (!strcmp(e, "require")) return 2;
-    return 1;
-}
-static bool is_7smooth(int64_t n) {
-    if (n < 1) return false;
-    for (int r : {2, 3, 5, 7})
-        while (n % r == 0) n /= r;
-    return n == 1;
-}
-// N = N1 * N2 for a two-level plan (gen_host.hpp: gen_split)
-static bool split_7smooth(int64_t n, int* n1, int* n2) {
-    if (const char* env = getenv("BBT_GEN_N1")) {            // (dev: force the split)
-        const int64_t d = atoll(env);
-        if (d > 1 && n % d == 0 && n / d <= BBT_GEN_MAX_LEN && d <= BBT_GEN_MAX_LEN) {
-            *n1 = (int)d;
-            *n2 = (int)(n / d);
-            return true;
-        }
-    }
-    return gen_split(n, rtc_mode() != 0, n1, n2);
-}
+// (stage lists, workgroup size, split and tile rules: gen_host.hpp; BBT_RTC and the split of a
+// plan: osm_geo.hpp)
 static std::map<std::pair<int, int>, cf*> g_gen_tables;    // (device, n) -> stage twiddles; -n: stages reversed
 static int get_gen_table(GenGeo* g, cf** out, bool reversed = false);
 // The same stages in reversed order: what the inverse of a convolution runs (fft_generic.hpp,
@@ -672,7 +645,6 @@ struct bbt_fir_plan {
 };
 static constexpr int BBT_FIR_R = 8;
 
-#define BBT_MAX_LANES 8
 // Events that only order streams of this device among each other (fork / join of the lanes, end
 // of a call) and the per-pass timing events: no system-scope fence.  A default HIP event writes
 // the caches back and invalidates them when it is recorded -- at every call boundary that emptied
@@ -1275,13 +1247,8 @@ static int osm_run_all(bbt_osm_plan* p, const float2* in, float2* out, int64_t n
     // (lanes keep alternating across deferred calls; a joined call starts on lane 0 as ever)
     const int l0 = call.deferred ? p->lane_cursor : 0;
     // regular runs (the fused channelizer's per-block shift and seam slot follow from the hop: osm_block)
-    const bool regular_ok = p->cap > p->chunk;
+    const bool regular_ok = osm_regular_ok(p->chunk, p->cap);
     const int mask = so.n_chan ? so.n_chan - 1 : 0;
-    auto follows = [mask](const OsmBlock& a, const OsmBlock& b, long long d) {
-        return b.in_off - a.in_off == d && b.out_off - a.out_off == d && b.valid_start == a.valid_start &&
-               b.valid_count == a.valid_count && !a.flat && !b.flat &&
-               b.shift == (int)(((long long)a.shift - d) & mask);      // (index: the fills count blocks up)
-    };
     int64_t c = 0;
     auto launch = [&](const OsmChunk& ch) {
         const int l = fork ? (int)((l0 + c) % p->lanes) : 0;
@@ -1298,18 +1265,15 @@ static int osm_run_all(bbt_osm_plan* p, const float2* in, float2* out, int64_t n
             OsmBlock nx = {};
             fill(nx, b0 + 1);
             hop = nx.in_off - ch.b[0].in_off;
-            if (hop > 0 && follows(ch.b[0], nx, hop))
+            if (hop > 0 && osm_follows(ch.b[0], nx, hop, mask))
                 for (run = 2; b0 + run < n_blocks; ++run) {
                     fill(nx, b0 + run);
-                    if (!follows(ch.b[0], nx, hop * run)) break;
+                    if (!osm_follows(ch.b[0], nx, hop * run, mask)) break;
                 }
         }
         if (run > p->chunk) {
-            // launches of equal size, as few as the work buffer allows -- one per lane at least when
-            // each still gets more than a chunk of descriptors would hold
-            int64_t parts = (run + p->cap - 1) / p->cap;
-            if (fork && parts < p->lanes && run >= (int64_t)p->lanes * 2 * p->chunk) parts = p->lanes;
-            const int64_t per = (run + parts - 1) / parts;
+            int64_t parts, per;            // (launches of equal size: osm_geo.hpp)
+            osm_run_parts(run, p->chunk, p->cap, p->lanes, fork, &parts, &per);
             const OsmBlock first = ch.b[0];
             for (int64_t r0 = 0; r0 < run; r0 += per) {
                 OsmChunk rc = {};
@@ -1374,285 +1338,153 @@ static void launch_seam_fix(bbt_osm_plan* p, float2* out, const std::vector<Seam
     }
 }
 
-extern "C" {
-
-int bbt_osm_plan_create(bbt_osm_plan** plan, int64_t n_fft, int n_stream, int n_resp,
-                        const void* resp, int resp_on_device, const int32_t* resp_index) {
-    ARG_TRY(plan && resp, "bbt_osm_plan_create: null argument");
-    *plan = nullptr;
-    const bool fast = is_pow2(n_fft) && n_fft >= 256 && n_fft <= (1 << 24);
-    int gn1 = 1, gn2 = 0;
-    ARG_TRY(fast || (is_7smooth(n_fft) && n_fft >= 2 &&
-                     (n_fft <= BBT_GEN_MAX_LEN || split_7smooth(n_fft, &gn1, &gn2))),
-            "bbt_osm_plan_create: n_fft=%lld must be a power of two in [256, 2^24] or a product of "
-            "2, 3, 5, 7 that is <= 8192 or splits into two such factors",
-            (long long)n_fft);
-    const bool single = n_stream == 1 && fast;
-    ARG_TRY(single || (n_stream >= 2 && n_stream % 2 == 0 && n_stream <= 65535 * 2),
-            "bbt_osm_plan_create: n_stream=%d must be even and >= 2 (or 1 with a power-of-two block "
-            "length)", n_stream);
-    ARG_TRY(n_resp >= 1, "bbt_osm_plan_create: n_resp=%d must be >= 1", n_resp);
-    std::vector<int> idx(single ? 2 : n_stream, 0);
-    if (resp_index)
-        for (int s = 0; s < n_stream; ++s) {
-            ARG_TRY(resp_index[s] >= 0 && resp_index[s] < n_resp,
-                    "bbt_osm_plan_create: resp_index[%d]=%d out of range", s, resp_index[s]);
-            idx[s] = resp_index[s];
+// ---- making a plan: what osm_geo.hpp decided, put on the device ----------------------------------
+// The kernels specialised on a generic length (fft_gen2.hpp), compiled now; if that is not
+// possible the plan runs on the general ones.  `why_not`: osm_levels found no plan for them.
+// 1: an error (BBT_RTC=require), else p->rtc says whether they are in use.
+static int osm_compile(bbt_osm_plan* p, const OsmGeo& geo, const OsmKnobs& knobs, const std::string& why_not) {
+    bool ok = geo.compiled;
+    if (!ok) fail("%s", why_not.c_str());
+    if (ok) {
+        const OsmSource src = osm_g2_source(geo);
+        hipFunction_t f[3] = {};
+        ok = !g2_build(src.text, src.names, f);
+        if (ok && p->n1 == 1) {
+            p->k2_small = f[0];
+        } else if (ok) {
+            p->k2_row = f[0];
+            p->k2_first = f[1];
+            p->k2_last = f[2];
         }
-    if (single) idx[1] = idx[0];            // both halves of a pair of blocks are the one stream
-    bbt_osm_plan* p = new bbt_osm_plan;
-    auto bail = [&](int) {
-        bbt_osm_plan_destroy(p);
+    }
+    if (ok) ok = !(get_g2_table(p->q2, &p->qw2) || get_g2_table(p->q2r, &p->qw2r) ||
+                   (p->n1 > 1 && get_g2_table(p->q1, &p->qw1)));
+    if (!ok && knobs.rtc == 2) return 1;
+    if (!ok) g2_warn_once("bbt_osm_plan_create");
+    p->rtc = ok;
+    return 0;
+}
+
+// Tables of a generic plan: the stages of both factors and the four-step twiddles between them.
+static int osm_generic_tables(bbt_osm_plan* p, const OsmGeo& geo, const OsmKnobs& knobs, const std::string& why_not) {
+    if (get_gen_table(&p->g2, &p->wn2) || get_reversed(p->g2, &p->g2r, &p->wn2r)) return 1;
+    if (knobs.rtc && osm_compile(p, geo, knobs, why_not)) return 1;
+    if (p->n1 == 1) return 0;
+    if (get_gen_table(&p->g1, &p->wn1) || make_big_twiddle(p->n, &p->tlo, &p->thi)) return 1;
+    // the uniform factors of the row kernel's four-step twiddles (GenRowSrc): the first
+    // forward and the last inverse stage have radix r0
+    const int r0 = p->rtc ? p->q2.fac[0] : p->g2.fac[0];
+    const long long m = p->n2 / r0;
+    std::vector<cf> t((size_t)p->n1 * r0);
+    for (int k1 = 0; k1 < p->n1; ++k1)
+        for (int r = 0; r < r0; ++r)
+            t[(size_t)k1 * r0 + r] = unit_root((long long)k1 * m % p->n * r, p->n);
+    return upload(&p->tws, t);
+}
+
+// Twiddle tables of a power-of-two plan.
+static int osm_pow2_tables(bbt_osm_plan* p) {
+    const int64_t n_fft = p->n;
+    if (p->n2 > 4096) {
+        if (get_big_table(p->n2, &p->big_tw)) return 1;
+    } else if (get_tables(p->n2, &p->tab2)) {
         return 1;
-    };
-    if (hipGetDevice(&p->device) != hipSuccess) return bail(fail("hipGetDevice failed"));
-    p->n = n_fft;
-    p->S = n_stream;
-    p->npair = single ? 1 : n_stream / 2;
-    p->single = single;
-    p->C = n_resp;
-    if (!fast) {
-        p->generic = true;
-        if (n_fft <= BBT_GEN_MAX_LEN) {
-            gn1 = 1;
-            gn2 = (int)n_fft;
-        }
-        p->n1 = gn1;
-    } else if (n_fft <= 4096 ||
-               ((n_fft == 8192 || n_fft == 16384) && (single || (n_stream / 2) % 8 != 0) && !getenv("BBT_OSM_NO_BIG"))) {
-        // (8192 / 16384 samples: one workgroup of 512 / 1024 threads, big_kernels.hpp -- one stream pair
-        // per workgroup, 16 bytes of every complete sample: with pairs in eights the two-level plan, whose
-        // 16-point column passes then move whole lines, is as fast at 8192 and faster at 16384 samples:
-        // 16 / 128 / 2048 streams 113 / 109 / 84 against 84 / 88 / 58 G stream-samples/s)
-        p->n1 = 1;
-    } else if (n_fft <= (1 << 16)) {
-        p->n1 = 16;
-    } else if (n_fft <= (1 << 20)) {
-        p->n1 = 256;
-    } else if (n_fft == (1 << 21)) {
-        // 512 x 4096: still two levels -- three streaming passes where 256 x 16 x 512 takes five.
-        // (A 512-point column pass holds 8 columns in 48 KiB of exchange area, three workgroups
-        // per CU; the row pass is the 4096-point one of the 2^20 blocks.)
-        p->n1 = 512;
-    } else if (n_fft == (1 << 22) && (single || (n_stream / 2) % 8 != 0)) {
-        // (stream pairs in eights: three levels, whose 256-point column passes take 8 pairs per workgroup --
-        // 16 / 128 streams 59.9 / 66.4 against 54.3 / 59.7 G stream-samples/s; at 2^21 two levels stay ahead)
-        p->n1 = 1024;            // 1024 x 4096, likewise (8 columns: 80 KiB, two workgroups per CU)
-    } else {
-        p->outer = 256;          // three levels, 256 x 16 x N2
-        p->n1 = 16;
-        if (n_stream / 2 > 255)
-            return bail(fail("bbt_osm_plan_create: blocks longer than 2^20 support at most 510 streams"));
     }
-    p->n2 = (int)(n_fft / p->n1 / p->outer);
-    if (p->generic) {
-        if (!gen_factor_7smooth(p->n2, &p->g2) || (p->n1 > 1 && !gen_factor_7smooth(p->n1, &p->g1)))
-            return bail(fail("bbt_osm_plan_create: cannot factor %d x %d", p->n1, p->n2));
-        if (get_gen_table(&p->g2, &p->wn2) || get_reversed(p->g2, &p->g2r, &p->wn2r)) return bail(1);
-        // columns per tile of the column passes (gen_host.hpp: gen_col_ct_wanted)
-        p->gen_ct = gen_col_ct_wanted(n_fft, p->n1, rtc_mode() != 0,
-                                      getenv("BBT_GEN_CT") ? std::max(1, atoi(getenv("BBT_GEN_CT"))) : 0);     // (dev)
-        // The kernels specialised on this length (fft_gen2.hpp), compiled now; if that is not
-        // possible the plan runs on the general ones.
-        if (rtc_mode()) {
-            // (short rows: several neighbouring rows per workgroup, gen2_host.hpp g2_row_ct)
-            const int row_ct = p->n1 > 1 ? g2_row_ct(p->n2, g2_pmax(BBT_G2_KIND_ROW)) : 1;
-            bool ok = g2_plan(p->n2, row_ct, &p->q2, g2_pmax(BBT_G2_KIND_ROW));
-            if (ok) p->q2r = g2_reversed(p->q2);
-            if (ok && p->n1 > 1) {
-                // (a column tile is one workgroup: at most 1024 threads and 64 KiB of exchange area)
-                ok = g2_fit_col_plan(p->n1, &p->gen_ct, &p->q1);
-            }
-            ok = ok && p->q2.threads() <= 1024 && std::max(p->q2.lds_elems, p->q2r.lds_elems) * 8 <= 96 * 1024;
-            if (!ok) fail("no stage list within a workgroup for %d x %d", p->n1, p->n2);
-            if (ok) {
-                std::string src = "#include \"gen2_kernels.hpp\"\n" + g2_trait_source("GA", p->q2) +
-                                  g2_trait_source("GB", p->q2r);
-                // (workgroups of 7 waves or more: at most 128 registers, two of them per CU)
-                const std::string w2 = p->q2.threads() >= 448 ? "4" : "0";
-                if (p->n1 == 1) {
-                    src += "BBT_G2_KERNEL_OSM_SMALL(k_small, GA, GB, " + w2 + ")\n";
-                    ok = !g2_build(src, {"k_small"}, &p->k2_small);
-                } else {
-                    const std::string w1 = p->q1.threads() >= 448 ? "4" : "0";
-                    src += g2_trait_source("GC", p->q1) + "BBT_G2_KERNEL_ROW(k_row, GA, GB, " + w2 + ")\n"
-                           "BBT_G2_KERNEL_COL(k_first, GC, true, " + w1 + ")\nBBT_G2_KERNEL_COL(k_last, GC, false, " + w1 + ")\n";
-                    hipFunction_t f[3];
-                    ok = !g2_build(src, {"k_row", "k_first", "k_last"}, f);
-                    if (ok) {
-                        p->k2_row = f[0];
-                        p->k2_first = f[1];
-                        p->k2_last = f[2];
-                    }
-                }
-            }
-            if (ok) ok = !(get_g2_table(p->q2, &p->qw2) || get_g2_table(p->q2r, &p->qw2r) ||
-                           (p->n1 > 1 && get_g2_table(p->q1, &p->qw1)));
-            if (!ok && rtc_mode() == 2) return bail(1);
-            if (!ok) g2_warn_once("bbt_osm_plan_create");
-            p->rtc = ok;
-        }
-        if (p->n1 > 1) {
-            if (get_gen_table(&p->g1, &p->wn1) || make_big_twiddle(n_fft, &p->tlo, &p->thi))
-                return bail(1);
-            {   // the uniform factors of the row kernel's four-step twiddles (GenRowSrc): the first
-                // forward and the last inverse stage have radix r0
-                const int r0 = p->rtc ? p->q2.fac[0] : p->g2.fac[0];
-                const long long m = p->n2 / r0;
-                std::vector<cf> t((size_t)p->n1 * r0);
-                for (int k1 = 0; k1 < p->n1; ++k1)
-                    for (int r = 0; r < r0; ++r)
-                        t[(size_t)k1 * r0 + r] = unit_root((long long)k1 * m % n_fft * r, n_fft);
-                if (upload(&p->tws, t)) return bail(1);
-            }
-        }
-    } else {
-        if (p->n2 > 4096) {
-            if (get_big_table(p->n2, &p->big_tw)) return bail(1);
-        } else if (get_tables(p->n2, &p->tab2)) {
-            return bail(1);
-        }
-        if ((p->n1 == 256 || p->outer == 256) && get_tables(256, &p->tab1)) return bail(1);
-        if ((p->n1 == 512 || p->n1 == 1024) && get_tables(p->n1, &p->tab1)) return bail(1);
-        if (get_wroot(&p->wroot)) return bail(1);
-        if ((p->n1 == 16 || p->n1 == 256 || p->n1 == 512 || p->n1 == 1024) && (p->outer == 1 || p->outer == 256)) {
-            // (three-level plans: these are the twiddles of the inner transform of n1 * n2 points)
-            const int t = p->n2 / 16;
-            const long long inner = (long long)p->n1 * p->n2;
-            std::vector<cf> row((size_t)p->n1 * 16), base((size_t)p->n1 * t);
-            for (int k1 = 0; k1 < p->n1; ++k1) {
-                for (int j = 0; j < 16; ++j) row[(size_t)k1 * 16 + j] = unit_root((long long)k1 * j, 16ll * p->n1);
-                for (int tau = 0; tau < t; ++tau)
-                    base[(size_t)k1 * t + tau] = unit_root((long long)k1 * tau, inner);
-            }
-            if (upload(&p->tw4row, row) || upload(&p->tw4base, base)) return bail(1);
-            if (p->outer > 1) {
-                std::vector<cf> o((size_t)p->outer * t), uu((size_t)p->outer * p->n1 * 16);
-                for (int k1o = 0; k1o < p->outer; ++k1o) {
-                    for (int tau = 0; tau < t; ++tau) o[(size_t)k1o * t + tau] = unit_root((long long)k1o * tau, n_fft);
-                    for (int k1 = 0; k1 < p->n1; ++k1)
-                        for (int j = 0; j < 16; ++j) {
-                            // W_{16 n1}^{k1 j} W_65536^{k1o j} as one angle over 65536 * 16 n1 / gcd ...: in double
-                            const double a = -2.0 * M_PI * ((double)((long long)k1 * j % (16ll * p->n1)) / (16.0 * p->n1) +
-                                                            (double)((long long)k1o * j % 65536) / 65536.0);
-                            uu[((size_t)k1o * p->n1 + k1) * 16 + j] = make_float2((float)cos(a), (float)sin(a));
-                        }
-                }
-                if (upload(&p->tw4o, o) || upload(&p->tw4u, uu)) return bail(1);
-            }
-            // twiddles in the column passes: only with 256- / 512-point columns (T1 = n1 / 16 threads
-            // per column, thread tau holds rows tau + T1 j: factors a g^j, a = W_N^{tau n2}, g = W_N^{T1 n2})
-            if (p->n1 >= 256 && p->outer == 1) {
-                const int t1 = p->n1 / 16;
-                std::vector<cf> a((size_t)t1 * p->n2), g((size_t)4 * p->n2);
-                for (int n2 = 0; n2 < p->n2; ++n2) {
-                    for (int i = 0; i < 4; ++i) g[(size_t)i * p->n2 + n2] = unit_root(((long long)t1 << i) * n2, n_fft);
-                    for (int tau = 0; tau < t1; ++tau) a[(size_t)tau * p->n2 + n2] = unit_root((long long)tau * n2, n_fft);
-                }
-                if (upload(&p->twa, a) || upload(&p->twg, g)) return bail(1);
-                p->tw_col = true;
-            }
-        }
+    if ((p->n1 == 256 || p->outer == 256) && get_tables(256, &p->tab1)) return 1;
+    if ((p->n1 == 512 || p->n1 == 1024) && get_tables(p->n1, &p->tab1)) return 1;
+    if (get_wroot(&p->wroot)) return 1;
+    if (p->n1 == 1) return 0;
+    // (three-level plans: these are the twiddles of the inner transform of n1 * n2 points)
+    const int t = p->n2 / 16;
+    const long long inner = (long long)p->n1 * p->n2;
+    std::vector<cf> row((size_t)p->n1 * 16), base((size_t)p->n1 * t);
+    for (int k1 = 0; k1 < p->n1; ++k1) {
+        for (int j = 0; j < 16; ++j) row[(size_t)k1 * 16 + j] = unit_root((long long)k1 * j, 16ll * p->n1);
+        for (int tau = 0; tau < t; ++tau)
+            base[(size_t)k1 * t + tau] = unit_root((long long)k1 * tau, inner);
     }
+    if (upload(&p->tw4row, row) || upload(&p->tw4base, base)) return 1;
+    if (p->outer > 1) {
+        std::vector<cf> o((size_t)p->outer * t), uu((size_t)p->outer * p->n1 * 16);
+        for (int k1o = 0; k1o < p->outer; ++k1o) {
+            for (int tau = 0; tau < t; ++tau) o[(size_t)k1o * t + tau] = unit_root((long long)k1o * tau, n_fft);
+            for (int k1 = 0; k1 < p->n1; ++k1)
+                for (int j = 0; j < 16; ++j) {
+                    // W_{16 n1}^{k1 j} W_65536^{k1o j} as one angle over 65536 * 16 n1 / gcd ...: in double
+                    const double a = -2.0 * M_PI * ((double)((long long)k1 * j % (16ll * p->n1)) / (16.0 * p->n1) +
+                                                    (double)((long long)k1o * j % 65536) / 65536.0);
+                    uu[((size_t)k1o * p->n1 + k1) * 16 + j] = make_float2((float)cos(a), (float)sin(a));
+                }
+        }
+        if (upload(&p->tw4o, o) || upload(&p->tw4u, uu)) return 1;
+    }
+    // twiddles in the column passes: only with 256- / 512-point columns (T1 = n1 / 16 threads
+    // per column, thread tau holds rows tau + T1 j: factors a g^j, a = W_N^{tau n2}, g = W_N^{T1 n2})
+    if (p->n1 >= 256 && p->outer == 1) {
+        const int t1 = p->n1 / 16;
+        std::vector<cf> a((size_t)t1 * p->n2), g((size_t)4 * p->n2);
+        for (int n2 = 0; n2 < p->n2; ++n2) {
+            for (int i = 0; i < 4; ++i) g[(size_t)i * p->n2 + n2] = unit_root(((long long)t1 << i) * n2, n_fft);
+            for (int tau = 0; tau < t1; ++tau) a[(size_t)tau * p->n2 + n2] = unit_root((long long)tau * n2, n_fft);
+        }
+        if (upload(&p->twa, a) || upload(&p->twg, g)) return 1;
+        p->tw_col = true;
+    }
+    return 0;
+}
 
-    // response: upload (if needed), permute to [C][N1][N2], scale by 1/N
-    const size_t rbytes = (size_t)n_resp * n_fft * sizeof(cf);
+// response: upload (if needed), permute to [C][N1][N2], scale by 1/N; then the streams' indices
+static int osm_put_response(bbt_osm_plan* p, const void* resp, int resp_on_device, const std::vector<int>& idx) {
+    const int64_t n_fft = p->n;
+    const size_t rbytes = (size_t)p->C * n_fft * sizeof(cf);
     cf* nat = nullptr;
     if (resp_on_device) {
         nat = (cf*)resp;
     } else {
         if (hipMalloc((void**)&nat, rbytes) != hipSuccess ||
             hipMemcpy(nat, resp, rbytes, hipMemcpyHostToDevice) != hipSuccess)
-            return bail(fail("bbt_osm_plan_create: uploading the response failed"));
+            return fail("bbt_osm_plan_create: uploading the response failed");
     }
     if (hipMalloc((void**)&p->resp, rbytes) != hipSuccess)
-        return bail(fail("bbt_osm_plan_create: hipMalloc(response) failed"));
+        return fail("bbt_osm_plan_create: hipMalloc(response) failed");
     // a device-resident response may still be being written on the caller's
     // (non-blocking) stream, which the null stream used below does not wait for
     if (resp_on_device && hipDeviceSynchronize() != hipSuccess)
-        return bail(fail("bbt_osm_plan_create: hipDeviceSynchronize failed"));
-    hipLaunchKernelGGL(k_permute_resp, dim3((unsigned)((n_fft + 255) / 256), n_resp), dim3(256), 0, 0,
+        return fail("bbt_osm_plan_create: hipDeviceSynchronize failed");
+    hipLaunchKernelGGL(k_permute_resp, dim3((unsigned)((n_fft + 255) / 256), p->C), dim3(256), 0, 0,
                        nat, p->resp, p->outer, p->n1, (long long)p->n2, 1.0f / (float)n_fft);
     hipError_t e = hipDeviceSynchronize();
     if (!resp_on_device) hipFree(nat);
     if (e != hipSuccess)
-        return bail(fail("bbt_osm_plan_create: response permutation failed: %s",
-                         hipGetErrorString(e)));
+        return fail("bbt_osm_plan_create: response permutation failed: %s", hipGetErrorString(e));
     if (hipMalloc((void**)&p->resp_index, idx.size() * sizeof(int)) != hipSuccess ||
         hipMemcpy(p->resp_index, idx.data(), idx.size() * sizeof(int), hipMemcpyHostToDevice) !=
             hipSuccess)
-        return bail(fail("bbt_osm_plan_create: resp_index upload failed"));
+        return fail("bbt_osm_plan_create: resp_index upload failed");
+    return 0;
+}
 
-    // workspace: `lanes` work buffers of `chunk` blocks each, 192 MiB in total.
-    // Measured on MI355X (2-pol 2^20 blocks): 2 x 6 blocks is best; a launch of
-    // 6 blocks is 1536 row-pass workgroups = exactly two rounds of the 768
-    // resident ones, while 2 x 12 (384 MiB) falls out of the 256 MiB Infinity
-    // Cache and loses 6 % although every pass alone is faster.
-    int lanes = 2;
-    if (const char* env = getenv("BBT_OSM_LANES")) lanes = atoi(env);
-    lanes = lanes < 1 ? 1 : (lanes > BBT_MAX_LANES ? BBT_MAX_LANES : lanes);
-    if (const char* env = getenv("BBT_OSM_TIMING_STRIDE")) p->timing_stride = std::max(1, atoi(env));
-    // (plans on the specialised generic kernels pad the rows of the work buffer to whole lines)
-    p->n2p = p->rtc ? (p->n2 + 7) / 8 * 8 : p->n2;
-    const size_t per_block = p->rtc ? (size_t)p->npair * p->n1 * p->n2p * 16 : (size_t)p->npair * n_fft * 16;
-    int chunk = (int)((192u << 20) / per_block / lanes);
-    if (const char* env = getenv("BBT_OSM_CHUNK")) chunk = atoi(env);
-    if (chunk < 1) chunk = 1;
-    if (chunk > BBT_MAX_CHUNK) chunk = BBT_MAX_CHUNK;
-    if (p->outer > 1) {                       // grid.y = blocks * pairs * 256 must fit
-        while (chunk > 1 && (long long)chunk * p->npair * p->outer > 65535) --chunk;
-    }
-    while (chunk > 1 && (long long)chunk * p->npair > 65535) --chunk;      // grid.y of the row pass
-    if ((double)chunk * per_block * lanes > 16.0 * (1u << 30)) lanes = 1;   // (config 4: 2 x 2 GiB)
-    // Short blocks: sixteen descriptors are a small launch (16 x 8192 samples: 32 workgroups per
-    // pass), so runs of REGULAR blocks -- equal steps of input and output, the same kept range:
-    // every block of a padded task but a re-aligned last one -- go as one descriptor and a hop
-    // (OsmChunk::reg_count), as many blocks as the work buffer (the same 192 MiB) holds.
-    int cap = (int)std::min<size_t>((192u << 20) / per_block / lanes, 4096);
-    while (cap > 1 && (long long)cap * p->npair * p->outer > 65535) --cap;
-    if (cap < chunk || getenv("BBT_OSM_CHUNK")) cap = chunk;
-    if (single) {
-        // `chunk` pairs of blocks fit the work buffer: a chunk of descriptors holds twice as many blocks
-        const int pairs = chunk > BBT_MAX_CHUNK / 2 ? BBT_MAX_CHUNK / 2 : chunk;
-        cap = std::max(cap, pairs);
-        p->work_bytes = per_block * cap;
-        chunk = 2 * pairs;
-        cap = 2 * cap;
-    } else {
-        p->work_bytes = per_block * cap;
-    }
-    if (p->n1 == 1 && !getenv("BBT_OSM_CHUNK")) {
-        // one kernel, no work buffer: nothing bounds a launch but the descriptor array
-        chunk = BBT_MAX_CHUNK;
-        while (chunk > 1 && (long long)chunk * p->npair >= (1ll << 31)) --chunk;
-    }
-    if (p->n1 == 1) cap = (int)std::min<long long>(1 << 20, ((1ll << 31) - 1) / p->npair);   // nothing to hold
-    p->chunk = chunk;
-    p->cap = cap;
-    p->lanes = lanes;
-    if (p->n1 == 1) p->work_bytes = 0;        // one kernel, no work buffer
+// the lanes' work buffers and streams, the tail stream and the events that order them
+static int osm_make_lanes(bbt_osm_plan* p) {
     if (p->n1 > 1) {
         for (int l = 0; l < p->lanes; ++l) {
             if (hipMalloc((void**)&p->lane_work[l], p->work_bytes) != hipSuccess)
-                return bail(fail("bbt_osm_plan_create: hipMalloc(workspace %zu bytes) failed",
-                                 p->work_bytes));
+                return fail("bbt_osm_plan_create: hipMalloc(workspace %zu bytes) failed", p->work_bytes);
             if (p->lanes > 1 &&
                 (hipStreamCreateWithFlags(&p->lane_stream[l], hipStreamNonBlocking) != hipSuccess ||
                  hipEventCreateWithFlags(&p->ev_join[l], BBT_EV_ORDER) != hipSuccess))
-                return bail(fail("bbt_osm_plan_create: creating the lane streams failed"));
+                return fail("bbt_osm_plan_create: creating the lane streams failed");
         }
         p->work = p->lane_work[0];
         if (p->lanes > 1 &&
             hipEventCreateWithFlags(&p->ev_fork, BBT_EV_ORDER) != hipSuccess)
-            return bail(fail("bbt_osm_plan_create: creating the fork event failed"));
+            return fail("bbt_osm_plan_create: creating the fork event failed");
         if (p->lanes > 1) {
             if (hipStreamCreateWithFlags(&p->tail_stream, hipStreamNonBlocking) != hipSuccess ||
                 hipEventCreateWithFlags(&p->ev_tail[0], BBT_EV_ORDER) != hipSuccess ||
                 hipEventCreateWithFlags(&p->ev_tail[1], BBT_EV_ORDER) != hipSuccess)
-                return bail(fail("bbt_osm_plan_create: creating the tail stream failed"));
+                return fail("bbt_osm_plan_create: creating the tail stream failed");
         }
-    } else {
-        p->lanes = 1;
     }
     // (BBT_ASIDE=0, a development switch: one-kernel plans have no stream of their own and run
     // every call on the caller's)
@@ -1663,10 +1495,65 @@ int bbt_osm_plan_create(bbt_osm_plan** plan, int64_t n_fft, int n_stream, int n_
             (!p->ev_fork && hipEventCreateWithFlags(&p->ev_fork, BBT_EV_ORDER) != hipSuccess) ||
             hipEventCreateWithFlags(&p->ev_tail[0], BBT_EV_ORDER) != hipSuccess ||
             hipEventCreateWithFlags(&p->ev_tail[1], BBT_EV_ORDER) != hipSuccess)
-            return bail(fail("bbt_osm_plan_create: creating the tail stream failed"));
+            return fail("bbt_osm_plan_create: creating the tail stream failed");
     }
     if (hipEventCreateWithFlags(&p->ev_done, BBT_EV_ORDER) != hipSuccess)
-        return bail(fail("bbt_osm_plan_create: creating the completion event failed"));
+        return fail("bbt_osm_plan_create: creating the completion event failed");
+    return 0;
+}
+
+extern "C" {
+
+int bbt_osm_plan_create(bbt_osm_plan** plan, int64_t n_fft, int n_stream, int n_resp,
+                        const void* resp, int resp_on_device, const int32_t* resp_index) {
+    ARG_TRY(plan && resp, "bbt_osm_plan_create: null argument");
+    *plan = nullptr;
+    // block length and stream count: checked, and the levels planned (osm_geo.hpp)
+    const OsmKnobs knobs = osm_knobs_from_env();
+    OsmGeo geo;
+    std::string text;           // why osm_levels refuses, or why there is nothing to compile
+    ARG_TRY(osm_levels(n_fft, n_stream, knobs, &geo, &text), "%s", text.c_str());
+    ARG_TRY(n_resp >= 1, "bbt_osm_plan_create: n_resp=%d must be >= 1", n_resp);
+    std::vector<int> idx(geo.single ? 2 : n_stream, 0);
+    if (resp_index)
+        for (int s = 0; s < n_stream; ++s) {
+            ARG_TRY(resp_index[s] >= 0 && resp_index[s] < n_resp,
+                    "bbt_osm_plan_create: resp_index[%d]=%d out of range", s, resp_index[s]);
+            idx[s] = resp_index[s];
+        }
+    if (geo.single) idx[1] = idx[0];        // both halves of a pair of blocks are the one stream
+    bbt_osm_plan* p = new bbt_osm_plan;
+    auto bail = [&](int) {
+        bbt_osm_plan_destroy(p);
+        return 1;
+    };
+    if (hipGetDevice(&p->device) != hipSuccess) return bail(fail("hipGetDevice failed"));
+    p->n = n_fft;
+    p->S = n_stream;
+    p->npair = geo.npair;
+    p->single = geo.single;
+    p->C = n_resp;
+    p->generic = geo.generic;
+    p->outer = geo.outer;
+    p->n1 = geo.n1;
+    p->n2 = geo.n2;
+    p->g1 = geo.g1;
+    p->g2 = geo.g2;
+    p->gen_ct = geo.gen_ct;
+    p->q1 = geo.q1;
+    p->q2 = geo.q2;
+    p->q2r = geo.q2r;
+    // tables; generic lengths: the kernels compiled for the length, which the buffers depend on
+    if (p->generic ? osm_generic_tables(p, geo, knobs, text) : osm_pow2_tables(p)) return bail(1);
+    if (osm_put_response(p, resp, resp_on_device, idx)) return bail(1);
+    osm_buffers(&geo, p->rtc, knobs);
+    p->n2p = geo.n2p;
+    p->chunk = geo.chunk;
+    p->cap = geo.cap;
+    p->lanes = geo.lanes;
+    p->work_bytes = geo.work_bytes;
+    p->timing_stride = knobs.timing_stride;
+    if (osm_make_lanes(p)) return bail(1);
     *plan = p;
     return 0;
 }
@@ -1731,15 +1618,7 @@ int bbt_osm_plan_defer(bbt_osm_plan* p, bbt_event done) {
 }
 
 int bbt_osm_plan_fusable(const bbt_osm_plan* p, int n_chan) {
-    // can bbt_osm_execute_channelized take Channelize(n_chan) into the row pass?
-    if (!p || p->generic || (p->n1 == 1 && p->outer == 1)) return 0;
-    if (p->single)              // one stream: blocks side by side; 256 channels and up, no detection
-        return fft_len_ok(n_chan) && n_chan <= p->n2 && p->n2 % n_chan == 0;
-    if (n_chan == 16 || n_chan == 32 || n_chan == 64 || n_chan == 128)       // few channels: after an
-        return p->n1 >= 256 || p->outer == 256;                             // exchange in the row pass
-    if (n_chan == 2 || n_chan == 4 || n_chan == 8)       // very few: lane butterflies in the row pass,
-        return p->outer == 1 && (p->n1 == 16 || p->n1 == 256);           // two-level plans (2^13 ... 2^20 samples)
-    return fft_len_ok(n_chan) && n_chan <= p->n2 && p->n2 % n_chan == 0;
+    return p && osm_fusable(p->generic, p->single, p->outer, p->n1, p->n2, n_chan);
 }
 
 int bbt_osm_execute(bbt_osm_plan* p, const void* in_dev, void* out_dev, int64_t n_blocks,
@@ -1937,11 +1816,7 @@ int bbt_osm_execute_channelized(bbt_osm_plan* p, const void* in_dev, void* out_d
 }
 
 int bbt_osm_detect_bins_max(const bbt_osm_plan* p, int n_chan, int step) {
-    // integration bins one column-pass workgroup touches: its 256 rows hold
-    // every (n2 / n_chan)-th of 256 * n2 / n_chan consecutive spectra
-    if (!p || n_chan <= 0 || step <= 0) return -1;
-    const int64_t span = 255ll * (p->n2 / n_chan);
-    return (int)(span / step) + 2;
+    return p ? osm_detect_bins_max(p->n2, n_chan, step) : -1;
 }
 
 int bbt_osm_execute_channelized_detect(bbt_osm_plan* p, const void* in_dev, void* out_dev,

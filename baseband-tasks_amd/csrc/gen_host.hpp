@@ -1,7 +1,8 @@
 // Host rules of the general LDS Stockham kernels (fft_generic.hpp, gen_kernels.hpp) and of the
 // two-level overlap-save plans built on them: stage lists, workgroup size, how a block length
-// splits into N1 x N2 and how many columns a column tile takes.  Plain C++ (no device code), so
-// that tests/gen2_plan_dump.cpp can print, without a device, what bbt_osm_plan_create decides.
+// splits into N1 x N2 and how many columns a column tile takes.  Plain C++ (no device code): the
+// plan's geometry (osm_geo.hpp) is built on these rules, and tests/gen2_plan_dump.cpp prints them
+// without a device.
 #pragma once
 #include <algorithm>
 #include <cstdint>
@@ -119,7 +120,7 @@ static inline bool g2_fit_col_plan(int n1, int* ct, G2Plan* q1) {
         *ct /= 2;
     return ok && q1->threads() <= 1024 && q1->lds_elems * 8 <= 64 * 1024;
 }
-// What bbt_osm_plan_create leaves in gen_ct in each mode.  With compilation on the column plan of
+// What osm_levels (osm_geo.hpp) leaves in gen_ct in each mode.  With compilation on the column plan of
 // the compiled kernels may have narrowed the tile, and after a failed compilation k_gen_col runs
 // with that: n1 * ct <= BBT_GEN_MAX_LEN holds in every mode.
 static inline int gen_col_ct(int64_t n_fft, int n1, int mode) {

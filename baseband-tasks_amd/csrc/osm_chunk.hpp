@@ -5,6 +5,7 @@
 #if !defined(__HIPCC_RTC__)          // (hipRTC provides the runtime's declarations itself)
 #include <hip/hip_runtime.h>
 #endif
+#include "osm_limits.hpp"
 
 namespace bbt {
 
@@ -20,7 +21,6 @@ __device__ __forceinline__ unsigned xcd_remap(unsigned bid, unsigned nblocks) {
 
 // ---------------------------------------------------------------------------
 // Overlap-save block descriptors (one launch handles <= BBT_MAX_CHUNK blocks).
-#define BBT_MAX_CHUNK 16
 struct OsmBlock {
     long long in_off;   // first input complete sample of the block
     long long out_off;  // output complete sample that receives n == valid_start

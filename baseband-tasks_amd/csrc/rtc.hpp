@@ -130,7 +130,7 @@ static inline int rtc_compile(const std::string& source, std::vector<char>* code
             struct stat st;
             std::string stamp;
             for (const char* h : {"fft_gen2.hpp", "gen2_kernels.hpp", "gen_functors.hpp", "fft_generic.hpp", "fft_core.hpp",
-                                  "osm_chunk.hpp", "gen_geo.hpp"})
+                                  "osm_chunk.hpp", "osm_limits.hpp", "gen_geo.hpp"})
                 if (stat((inc + "/" + h).c_str(), &st) == 0)
                     stamp += std::to_string((long long)st.st_mtime) + ":" + std::to_string((long long)st.st_size) + ";";
             const size_t key = std::hash<std::string>()(source + "|" + arch + "|" + defines + "|" + stamp);

@@ -1,12 +1,16 @@
-// Prints what the host planner of the generic-length engine (csrc/gen2_host.hpp) decides, as
-// JSON lines, for tests/test_gen2_planner.py:   gen2_plan_dump plan <pmax> <n> <ct> ... | split <N> ...
-// and, per block length, what bbt_osm_plan_create runs a two-level block of the general LDS
-// Stockham kernels with (csrc/gen_host.hpp):      gen2_plan_dump route off|on|failed <N> ...
+// Prints what the host rules decide without a device, as JSON lines, for tests/test_gen2_planner.py
+// and tests/test_osm_geo.py:
+//   plan <pmax> <n> <ct> ...     a plan of the generic-length engine (csrc/gen2_host.hpp)
+//   split <N> ...                the measured split of a block and the plans of both kernels (csrc/osm_geo.hpp: osm_levels)
+//   route off|on|failed <N> ...  what a two-level block runs with on the general LDS Stockham kernels (csrc/gen_host.hpp)
+//   source <N> | source2 <N>     the translation unit an overlap-save plan compiles for a block (osm_g2_source)
+//   osm 0|1|failed <n_fft> <n_stream> ...   levels and buffers of a plan: BBT_RTC=0, compiled, compilation failed
+//   parts <run> <chunk> <cap> <lanes> <fork> ...   how a regular run is cut into launches (osm_run_parts)
+// No environment variable decides anything here: the knobs are the defaults.
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
-#include "gen2_host.hpp"
-#include "gen_host.hpp"
+#include "osm_geo.hpp"
 using namespace bbt;
 
 static void dump(const G2Plan& g) {
@@ -35,17 +39,13 @@ int main(int argc, char** argv) {
         }
     } else if (!strcmp(argv[1], "split")) {
         for (int i = 2; i < argc; ++i) {
-            int n1 = 0, n2 = 0;
-            if (!g2_choose_split(atoll(argv[i]), 8, 1024, 8192, &n1, &n2)) { printf("null\n"); continue; }
-            G2Plan c, r;
-            // (as bbt_osm_plan_create plans them: short blocks with wider column tiles, short rows several to a workgroup)
-            const bool small = atoll(argv[i]) <= (1 << 17);
-            g2_plan(n1, small ? g2_col_ct(n1, g2_pmax(BBT_G2_KIND_COL)) : 8, &c, g2_pmax(BBT_G2_KIND_COL));
-            g2_plan(n2, g2_row_ct(n2, g2_pmax(BBT_G2_KIND_ROW)), &r, g2_pmax(BBT_G2_KIND_ROW));
-            printf("{\"n1\": %d, \"n2\": %d, \"col\": ", n1, n2);
-            dump(c);
+            OsmGeo g;
+            std::string text;
+            if (!osm_levels(atoll(argv[i]), 2, OsmKnobs(), &g, &text) || !g.measured || !g.compiled) { printf("null\n"); continue; }
+            printf("{\"n1\": %d, \"n2\": %d, \"col\": ", g.n1, g.n2);
+            dump(g.q1);
             printf(", \"row\": ");
-            dump(r);
+            dump(g.q2);
             printf("}\n");
         }
     } else if (!strcmp(argv[1], "route")) {
@@ -75,29 +75,47 @@ int main(int argc, char** argv) {
             for (int s = 0; s < f2.nfac; ++s) printf("%s%d", s ? ", " : "", f2.fac[s]);
             printf("]}\n");
         }
-    } else if (!strcmp(argv[1], "source")) {
-        G2Plan g;
-        if (!g2_plan(atoi(argv[2]), 1, &g, g2_pmax(BBT_G2_KIND_ROW))) return 1;
-        const G2Plan gr = g2_reversed(g);
-        printf("#include \"gen2_kernels.hpp\"\n%s%sBBT_G2_KERNEL_OSM_SMALL(k_small, GA, GB, 0)\nBBT_G2_KERNEL_FFT_ROWS(k_rows, GA, -1, 0)\n",
-               g2_trait_source("GA", g).c_str(), g2_trait_source("GB", gr).c_str());
-    } else if (!strcmp(argv[1], "source2")) {
-        // the translation unit bbt_osm_plan_create writes for a two-level block (row kernel + both column passes)
-        int n1 = 0, n2 = 0;
-        const long long n = atoll(argv[2]);
-        if (!g2_choose_split(n, 8, 1024, 8192, &n1, &n2)) return 1;
-        G2Plan q1, q2;
-        const int ct = n <= (1 << 17) ? g2_col_ct(n1, g2_pmax(BBT_G2_KIND_COL)) : 8;
-        if (!g2_plan(n2, g2_row_ct(n2, g2_pmax(BBT_G2_KIND_ROW)), &q2, g2_pmax(BBT_G2_KIND_ROW)) ||
-            !g2_plan(n1, ct, &q1, g2_pmax(BBT_G2_KIND_COL)))
+    } else if (!strcmp(argv[1], "source") || !strcmp(argv[1], "source2")) {
+        // what bbt_osm_plan_create compiles for a block of one kernel (source) or of two levels (source2)
+        OsmGeo g;
+        std::string text;
+        const bool two = !strcmp(argv[1], "source2");
+        if (!osm_levels(atoll(argv[2]), 2, OsmKnobs(), &g, &text)) return 1;
+        if (!g.generic && !two) {
+            // (a power of two: its plan compiles nothing; the same text on the traits of the length, for
+            // tests/test_conversion_host.py, which puts another plan's kernel on them)
+            g.n1 = 1;
+            if (!g2_plan(atoi(argv[2]), 1, &g.q2, g2_pmax(BBT_G2_KIND_ROW))) return 1;
+            g.q2r = g2_reversed(g.q2);
+        } else if (!g.compiled || (g.n1 > 1) != two) {
             return 1;
-        const G2Plan q2r = g2_reversed(q2);
-        const char* w2 = q2.threads() >= 448 ? "4" : "0";
-        const char* w1 = q1.threads() >= 448 ? "4" : "0";
-        printf("#include \"gen2_kernels.hpp\"\n%s%s%sBBT_G2_KERNEL_ROW(k_row, GA, GB, %s)\n"
-               "BBT_G2_KERNEL_COL(k_first, GC, true, %s)\nBBT_G2_KERNEL_COL(k_last, GC, false, %s)\n",
-               g2_trait_source("GA", q2).c_str(), g2_trait_source("GB", q2r).c_str(), g2_trait_source("GC", q1).c_str(),
-               w2, w1, w1);
+        }
+        // (source: with the channelizer's kernel on the same traits -- chan_pick of bbt_hip.hip -- as a second entry point)
+        printf("%s%s", osm_g2_source(g).text.c_str(), two ? "" : "BBT_G2_KERNEL_FFT_ROWS(k_rows, GA, -1, 0)\n");
+    } else if (!strcmp(argv[1], "osm")) {
+        OsmKnobs knobs;
+        knobs.rtc = !strcmp(argv[2], "0") ? 0 : 1;
+        const bool rtc_ok = !strcmp(argv[2], "1");
+        for (int i = 3; i + 1 < argc; i += 2) {
+            OsmGeo g;
+            std::string text;
+            const long long n = atoll(argv[i]);
+            if (!osm_levels(n, atoi(argv[i + 1]), knobs, &g, &text)) {
+                printf("{\"n_fft\": %lld, \"n_stream\": %d, \"error\": \"%s\"}\n", n, atoi(argv[i + 1]), text.c_str());
+                continue;
+            }
+            osm_buffers(&g, g.generic && g.compiled && rtc_ok, knobs);
+            printf("{\"n_fft\": %lld, \"n_stream\": %d, \"outer\": %d, \"n1\": %d, \"n2\": %d, \"n2p\": %d, \"gen_ct\": %d, "
+                   "\"lanes\": %d, \"chunk\": %d, \"cap\": %d, \"work_bytes\": %lld, \"workspace_bytes\": %lld}\n",
+                   n, g.S, g.outer, g.n1, g.n2, g.n2p, g.gen_ct, g.lanes, g.chunk, g.cap, (long long)g.work_bytes,
+                   (long long)g.work_bytes * g.lanes);
+        }
+    } else if (!strcmp(argv[1], "parts")) {
+        for (int i = 2; i + 4 < argc; i += 5) {
+            int64_t parts, per;
+            osm_run_parts(atoll(argv[i]), atoi(argv[i + 1]), atoi(argv[i + 2]), atoi(argv[i + 3]), atoi(argv[i + 4]) != 0, &parts, &per);
+            printf("{\"parts\": %lld, \"per\": %lld}\n", (long long)parts, (long long)per);
+        }
     }
     return 0;
 }
