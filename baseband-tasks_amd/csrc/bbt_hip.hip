@@ -24,6 +24,9 @@
 #include "gen2_host.hpp"
 #include "gen_host.hpp"
 #include "osm_geo.hpp"
+#include "chan_geo.hpp"
+#include "pfb_geo.hpp"
+#include "tune.hpp"
 #include "rtc.hpp"
 #include "fold_kernels.hpp"
 #include "phase_kernels.hpp"
@@ -2043,63 +2046,7 @@ static int chan_dispatch(const bbt_chan_plan* p, const float2* in, float2* out, 
     return 0;
 }
 
-extern "C" {
-
-}  // extern "C"
-
-// Scratch device memory of the plans that time their candidates (chan_pick, pfb_pick): ONE buffer
-// per device, allocated when the first such plan is made, grown when a plan needs more, and kept
-// -- mapping and unmapping a GiB per plan preempts every queue of the process and took 0.3-2 s
-// each after a few dozen plans.  1 GiB each way when the card has it to spare (well past the 256
-// MiB memory-side cache: at 256 MiB each way 1536 channels ranked wrongly), at most an eighth of
-// what is free; BBT_TUNE_KEEP=0 frees it after every plan.
-struct TuneScratch {
-    std::mutex mu;
-    std::map<int, std::pair<void*, size_t>> buf;         // device -> (pointer, bytes)
-};
-static TuneScratch& tune_scratch() {
-    static TuneScratch* t = new TuneScratch;              // (never destroyed: the runtime may be gone by then)
-    return *t;
-}
-// A buffer of at least `least` bytes (as much as `want` if the card has it to spare); null if not to be had.
-// The caller holds it until tune_release(): plans are made one at a time (the mutex is held).
-static void* tune_acquire(size_t least, size_t want, size_t* got) {
-    TuneScratch& t = tune_scratch();
-    t.mu.lock();
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess) {
-        t.mu.unlock();
-        return nullptr;
-    }
-    auto& slot = t.buf[dev];
-    if (slot.second < least) {
-        if (slot.first) hipFree(slot.first);
-        slot = {nullptr, 0};
-        size_t free_b = 0, total_b = 0;
-        if (hipMemGetInfo(&free_b, &total_b) != hipSuccess) free_b = 0;
-        size_t bytes = std::max(least, std::min(want, free_b / 4));
-        void* ptr = nullptr;
-        if (bytes > free_b / 2 || hipMalloc(&ptr, bytes) != hipSuccess) {
-            hipGetLastError();
-            t.mu.unlock();
-            return nullptr;
-        }
-        slot = {ptr, bytes};
-    }
-    *got = slot.second;
-    return slot.first;
-}
-static void tune_release() {
-    TuneScratch& t = tune_scratch();
-    if (getenv("BBT_TUNE_KEEP") && !strcmp(getenv("BBT_TUNE_KEEP"), "0")) {
-        int dev = 0;
-        if (hipGetDevice(&dev) == hipSuccess && t.buf[dev].first) {
-            hipFree(t.buf[dev].first);
-            t.buf[dev] = {nullptr, 0};
-        }
-    }
-    t.mu.unlock();
-}
+// (the scratch memory and the harness of the plans that time their candidates: tune.hpp)
 extern "C" int bbt_tune_scratch(int release, int64_t* bytes) {
     TuneScratch& t = tune_scratch();
     std::lock_guard<std::mutex> lock(t.mu);
@@ -2114,142 +2061,90 @@ extern "C" int bbt_tune_scratch(int release, int64_t* bytes) {
     return 0;
 }
 
-// One candidate of a generic-length channelizer plan on the compiled kernels: columns of a
-// workgroup = cp neighbouring stream pairs (up to 8: 128-byte pieces of a complete sample, as
-// many as divide the pair count) x consecutive transforms while they still fit ONE wave (a
-// transform of 100 threads gains nothing from a neighbour: 1000 channels 160 G alone, 128 G in
-// twos).  0 = ok (k2 set), 1 = not available (g_err says why).
-// `wide` (many streams): as many pairs as fit a workgroup of 1024 threads and 144 KiB instead of 256
-// threads -- whole 128-byte lines at one workgroup per CU, as k_fft_rows_pp.
-static int chan_candidate(bbt_chan_plan* p, int n_chan, int direction, int pmax, bool wide = false) {
-    G2Plan probe;
-    if (!g2_plan(n_chan, 1, &probe, pmax)) return fail("no stage list for %d", n_chan);
-    int cp = 1;
-    while (cp < 8 && p->npair % (2 * cp) == 0 &&
-           (wide ? probe.tj * 2 * cp <= 1024 && (int64_t)n_chan * 2 * cp * 8 <= 144 * 1024 : probe.tj * 2 * cp <= 256))
-        cp *= 2;
-    int ct = cp;
-    const int ct_cap = getenv("BBT_G2_CHAN_CT") ? atoi(getenv("BBT_G2_CHAN_CT")) : 256;      // (dev)
-    while (2 * ct <= ct_cap && probe.tj * 2 * ct <= 64 && (int64_t)n_chan * 2 * ct * 8 <= 64 * 1024) ct *= 2;
-    G2Plan q;
-    if (!g2_plan(n_chan, ct, &q, pmax) || q.threads() > 1024) return fail("no plan for %d x %d columns", n_chan, ct);
-    const std::string src = "#include \"gen2_kernels.hpp\"\n" + g2_trait_source("GA", q) +
-                            "BBT_G2_KERNEL_FFT_ROWS(k_rows, GA, " + (direction < 0 ? "-1" : "+1") +
-                            (q.threads() >= 448 ? ", 4)\n" : ", 0)\n");
+// A candidate of a generic-length channelizer plan (chan_geo.hpp) with its kernel and its table,
+// and the one place where a plan takes one.
+struct ChanBuilt {
+    ChanCandidate c;
     hipFunction_t k = nullptr;
     cf* w = nullptr;
-    if (g2_build(src, {"k_rows"}, &k) || get_g2_table(q, &w)) return 1;
-    p->q = q;
-    p->cp = cp;
-    p->k2 = k;
-    p->qw = w;
+};
+// 0 = ok, 1 = not available (g_err says why).
+static int chan_build(const ChanCandidate& c, ChanBuilt* b) {
+    if (!c.ok()) return fail("%s", c.error.c_str());
+    b->c = c;
+    return g2_build(c.source, {"k_rows"}, &b->k) || get_g2_table(c.q, &b->w);
+}
+static void chan_apply(bbt_chan_plan* p, const ChanBuilt& b) {
+    p->q = b.c.q;
+    p->cp = b.c.cp;
+    p->k2 = b.k;
+    p->qw = b.w;
+}
+// The plan stays on the general kernel because the compiled ones are not to be had (g_err):
+// 0 with one warning, 1 = error in `require` mode.
+static int chan_stay_general(bbt_chan_plan* p) {
+    if (rtc_mode() == 2) return 1;
+    g2_warn_once("bbt_chan_plan_create");
+    p->k2 = nullptr;
+    return 0;
+}
+// The plan takes the candidate of `code`, untimed.
+static int chan_take(bbt_chan_plan* p, int code, const ChanKnobs& knobs) {
+    ChanBuilt b;
+    if (chan_build(chan_g2_candidate(p->n, p->npair, p->dir, code % 100, code >= 100, knobs), &b)) return chan_stay_general(p);
+    chan_apply(p, b);
     return 0;
 }
 // Choose among the candidates (and the general kernel) by timing them; 0 = ok (p->k2 null: the
 // general kernel stays), 1 = error (only in `require` mode).
-static int chan_pick(bbt_chan_plan* p, int n_chan, int direction) {
-    static std::mutex mu;
-    static std::map<std::tuple<int, int, int, int>, int> chosen;       // (device, n, streams, direction) -> points (+ 100: wide), 0 = general
+static int chan_pick(bbt_chan_plan* p, const ChanKnobs& knobs) {
+    static TuneMemo<std::tuple<int, int, int, int>, int> chosen;       // (device, n, streams, direction) -> ChanCandidate::code, 0 = general
     int dev = 0;
     HIP_TRY(hipGetDevice(&dev));
-    const auto key = std::make_tuple(dev, n_chan, p->S, direction);
-    const bool tune = !(getenv("BBT_G2_TUNE") && !strcmp(getenv("BBT_G2_TUNE"), "0"));
-    int pick = -1;
-    {
-        std::lock_guard<std::mutex> lock(mu);
-        auto it = chosen.find(key);
-        if (it != chosen.end()) pick = it->second;
-    }
-    if (pick < 0 && !tune) pick = g2_pmax(BBT_G2_KIND_CHAN) + (getenv("BBT_G2_CHAN_WIDE") ? 100 : 0);      // (wide: tests)
+    const auto key = std::make_tuple(dev, p->n, p->S, p->dir);
+    int remembered = -1;
+    chosen.find(key, &remembered);
+    const int pick = chan_untimed_code(remembered, knobs);
     if (pick == 0) return 0;                                           // (the general kernel won before)
-    if (pick > 0) {
-        if (!chan_candidate(p, n_chan, direction, pick % 100, pick >= 100)) return 0;
-        if (rtc_mode() == 2) return 1;
-        g2_warn_once("bbt_chan_plan_create");
-        p->k2 = nullptr;
-        return 0;
-    }
-    // time the candidates on scratch memory (tune_acquire), from HBM as in use, on the null stream (a
-    // stream of its own would be one more hardware queue made and destroyed per plan)
-    const size_t per = (size_t)n_chan * p->S * sizeof(cf);
-    size_t got = 0;
-    char* base = (char*)tune_acquire(16 * per, (size_t)2 << 30, &got);
-    const int64_t ns = (int64_t)(got / (2 * per));
-    void *a = base, *b = base ? base + ns * per : nullptr;
-    hipStream_t st = nullptr;
-    hipEvent_t e0 = nullptr, e1 = nullptr;
-    bool ready = base && hipMemsetAsync(a, 0, ns * per, nullptr) == hipSuccess &&
-                 hipEventCreate(&e0) == hipSuccess && hipEventCreate(&e1) == hipSuccess &&
-                 hipDeviceSynchronize() == hipSuccess;
-    auto time_current = [&]() -> float {
-        float best = 1e30f;
-        if (bbt_chan_execute(p, a, b, ns, st)) return best;           // (warm-up: code object upload, tables)
-        for (int r = 0; r < 2; ++r) {
-            float ms = 0.f;
-            if (hipEventRecord(e0, st) != hipSuccess || bbt_chan_execute(p, a, b, ns, st) ||
-                hipEventRecord(e1, st) != hipSuccess || hipEventSynchronize(e1) != hipSuccess ||
-                hipEventElapsedTime(&ms, e0, e1) != hipSuccess)
-                return 1e30f;
-            best = std::min(best, ms);
-        }
-        return best;
-    };
-    float best_ms = 1e30f;
+    if (pick > 0) return chan_take(p, pick, knobs);
+    const size_t per = (size_t)p->n * p->S * sizeof(cf);
+    bool ready;
     int any = 0;
-    if (ready) {
-        p->k2 = nullptr;
-        best_ms = time_current();                                       // the general kernel
-        pick = 0;
-        bbt_chan_plan best_plan = *p;
-        std::vector<G2Plan> seen;                                       // (plans already timed: stages, threads, columns)
-        for (int code : {10, 16, 20, 110, 116, 120}) {
-            const int pmax = code % 100;
-            const bool wide = code >= 100;
-            if (wide && p->npair < 4) continue;
-            if (chan_candidate(p, n_chan, direction, pmax, wide)) continue;
-            ++any;
-            bool same = false;
-            for (const G2Plan& o : seen) {
-                bool eq = o.nfac == p->q.nfac && o.tj == p->q.tj && o.ct == p->q.ct;
-                for (int i = 0; eq && i < o.nfac; ++i) eq = o.fac[i] == p->q.fac[i];
-                same = same || eq;
-            }
-            if (same) continue;
-            seen.push_back(p->q);
-            const float ms = time_current();
-            if (getenv("BBT_RTC_VERBOSE"))
-                fprintf(stderr, "bbt: Channelize(%d) x %d streams, %d points per thread, %d pairs x %d transforms per workgroup: "
-                                "%.3f ms (general %.3f)\n", n_chan, p->S, pmax, p->cp, p->q.ct / p->cp, ms,
-                        best_plan.k2 ? -1.f : best_ms);
-            if (ms < best_ms) {
-                best_ms = ms;
-                pick = code;
-                best_plan = *p;
-            }
-        }
-        *p = best_plan;
-    }
-    if (e0) hipEventDestroy(e0);
-    if (e1) hipEventDestroy(e1);
-    if (base) tune_release();
-    if (!ready) {                                                       // (no scratch memory: the rule, untimed)
-        hipGetLastError();
-        if (chan_candidate(p, n_chan, direction, g2_pmax(BBT_G2_KIND_CHAN))) {
-            if (rtc_mode() == 2) return 1;
-            g2_warn_once("bbt_chan_plan_create");
+    {
+        TuneBench bench(16 * per, (size_t)2 << 30, [&](size_t got) { return got / (2 * per) * per; });
+        ready = bench.ready();
+        if (ready) {
+            const int64_t ns = (int64_t)(bench.size() / (2 * per));
+            void *in = bench.base(), *out = bench.base() + ns * per;
+            auto run = [&](hipStream_t st) { return bbt_chan_execute(p, in, out, ns, st); };
             p->k2 = nullptr;
+            const float general_ms = bench.best_of(run);
+            float best_ms = general_ms;
+            ChanBuilt best;                                             // (k null: the general kernel)
+            std::string why;
+            const std::vector<ChanCandidate> list = chan_candidates(p->n, p->npair, p->dir, knobs, &why);
+            if (list.empty()) fail("%s", why.c_str());
+            for (const ChanCandidate& c : list) {
+                ChanBuilt b;
+                if (chan_build(c, &b)) continue;
+                ++any;
+                chan_apply(p, b);
+                const float ms = bench.best_of(run);
+                if (getenv("BBT_RTC_VERBOSE"))
+                    fprintf(stderr, "bbt: Channelize(%d) x %d streams, %d points per thread, %d pairs x %d transforms per workgroup: "
+                                    "%.3f ms (general %.3f)\n", p->n, p->S, c.code % 100, c.cp, c.q.ct / c.cp, ms,
+                            best.k ? -1.f : general_ms);
+                if (ms < best_ms) {
+                    best_ms = ms;
+                    best = b;
+                }
+            }
+            chan_apply(p, best);
+            if (any) chosen.remember(key, best.k ? best.c.code : 0);
         }
-        return 0;
     }
-    if (!any) {
-        if (rtc_mode() == 2) return 1;
-        g2_warn_once("bbt_chan_plan_create");
-        p->k2 = nullptr;
-        return 0;
-    }
-    std::lock_guard<std::mutex> lock(mu);
-    chosen[key] = pick;
-    return 0;
+    if (!ready) return chan_take(p, g2_pmax(BBT_G2_KIND_CHAN), knobs);      // (no scratch memory: the rule, untimed, and nothing remembered)
+    return any ? 0 : chan_stay_general(p);
 }
 
 extern "C" {
@@ -2257,24 +2152,11 @@ extern "C" {
 int bbt_chan_plan_create(bbt_chan_plan** plan, int n_chan, int n_stream, int direction) {
     ARG_TRY(plan, "bbt_chan_plan_create: null argument");
     *plan = nullptr;
-    const bool fast = is_pow2(n_chan) && n_chan >= 2 && n_chan <= 4096;
-    // (8192 and 16384 channels: one workgroup of 512 / 1024 threads per transform, stream pairs, plain directions)
-    const bool big = (n_chan == 8192 || n_chan == 16384) && n_stream % 2 == 0 && (direction == -1 || direction == 1);
-    ARG_TRY(fast || big || (n_chan >= 2 && n_chan <= BBT_GEN_MAX_LEN && is_7smooth(n_chan)),
-            "bbt_chan_plan_create: n_chan=%d must be a power of two in [2, 16384] (above 4096: stream "
-            "pairs, directions -1 / +1) or a product of 2, 3, 5, 7 up to 8192", n_chan);
-    const bool single = n_stream == 1 && fast && n_chan >= 256;
-    ARG_TRY(single || (n_stream >= 2 && n_stream % 2 == 0 && n_stream <= 65535 * 2),
-            "bbt_chan_plan_create: n_stream=%d must be even and >= 2 (or 1 for a power-of-two n_chan "
-            "in [256, 4096])", n_stream);
-    // direction -2: forward transform of ONE stream z = a + i b made of two real streams, writing their
-    // half spectra (n_spectra, n_chan / 2 + 1, 2) instead of Z (Channelize of float32 streams in one pass)
-    // (+2: the inverse -- half spectra of two real streams in, z = a + i b out)
-    const bool split_real = direction == -2 || direction == 2;
-    ARG_TRY(!split_real || (fast && n_chan >= 256),
-            "bbt_chan_plan_create: direction -2 / +2 needs a power-of-two n_chan in [256, 4096]");
-    if (split_real) direction /= 2;
-    ARG_TRY(direction == -1 || direction == 1, "bbt_chan_plan_create: direction must be -1, +1, -2 or +2");
+    ChanShape shape;
+    std::string refusal;
+    if (!chan_check(n_chan, n_stream, direction, &shape, &refusal)) return fail("%s", refusal.c_str());
+    direction = shape.direction;
+    const bool split_real = shape.split_real, big = shape.kind == CHAN_BIG, fast = shape.kind != CHAN_GENERIC && !big;
     bbt_chan_plan* p = new bbt_chan_plan;
     p->n = n_chan;
     p->S = n_stream;
@@ -2310,8 +2192,8 @@ int bbt_chan_plan_create(bbt_chan_plan** plan, int n_chan, int n_stream, int dir
         // On four stream pairs and more each is also tried `wide`: as many pairs as fit a workgroup of
         // 1024 threads (whole lines: Channelize(3000) on 16 / 128 / 2048 streams 127 / 107 / 110 -> 200 / 201 / 203 G
         // stream-samples/s).  BBT_G2_TUNE=0: no timing, 10 points; BBT_G2_CHAN=none: the general kernels.
-        const char* chan_env = getenv("BBT_G2_CHAN");
-        if (rtc_mode() && !(chan_env && !strcmp(chan_env, "none")) && chan_pick(p, n_chan, direction)) {
+        const ChanKnobs knobs = chan_knobs_from_env();
+        if (rtc_mode() && !knobs.general && chan_pick(p, knobs)) {
             delete p;
             return 1;
         }
@@ -2422,10 +2304,6 @@ struct bbt_pfb_plan {
     bbt_chan_plan* two_pass = nullptr;
 };
 
-// geometry of one pair in the several-pairs form of the window kernel: 128 threads and 2048 / N
-// spectra per workgroup up to 1024 channels, 256 threads and two spectra for 2048
-static constexpr int pfb_pp_geometry(int n) { return n <= 1024 ? 2048 : 4096; }
-
 template <int N, int NTAP>
 static void launch_pfb_window(const bbt_pfb_plan* p, const float2* in, float2* out, int64_t n_spec,
                               hipStream_t st) {
@@ -2440,7 +2318,7 @@ static void launch_pfb_window(const bbt_pfb_plan* p, const float2* in, float2* o
                                (long long)n_spec, 1, p->taps_quads, p->tab4096.tw0, p->tab4096.tw1);
         return;
     }
-    if (p->pp > 1) {            // several pairs per workgroup (many streams): pfb_pick
+    if (p->pp > 1) {            // several pairs per workgroup (many streams): pfb_route
         constexpr int GN = pfb_pp_geometry(N);
         const unsigned gy = (unsigned)((n_spec + GN / N - 1) / (GN / N));
         if (p->pp == 4)
@@ -2464,20 +2342,16 @@ static void launch_pfb_window(const bbt_pfb_plan* p, const float2* in, float2* o
                            (long long)n_spec, p->S, p->taps_quads, p->tab4096.tw0, p->tab4096.tw1);
 }
 
-// sliding-window variants exist for these (n_chan, n_tap)
-static bool pfb_window_dispatch(const bbt_pfb_plan* p, const float2* in, float2* out,
-                                int64_t n_spec, hipStream_t st, bool probe) {
-#define BBT_PW(N_, T_)                                                  \
-    if (p->n == N_ && p->n_tap == T_) {                                 \
-        if (!probe) launch_pfb_window<N_, T_>(p, in, out, n_spec, st);  \
-        return true;                                                    \
-    }
+// the sliding-window variants: those of pfb_has_window (pfb_geo.hpp)
+static void pfb_window_dispatch(const bbt_pfb_plan* p, const float2* in, float2* out, int64_t n_spec, hipStream_t st) {
+#define BBT_PW(N_, T_)                                                                   \
+    static_assert(pfb_has_window(N_, T_), "pfb_has_window must name every window kernel"); \
+    if (p->n == N_ && p->n_tap == T_) return launch_pfb_window<N_, T_>(p, in, out, n_spec, st);
     BBT_PW(256, 4) BBT_PW(512, 4) BBT_PW(1024, 4) BBT_PW(2048, 4)
     BBT_PW(256, 8) BBT_PW(512, 8) BBT_PW(1024, 8) BBT_PW(2048, 8)
     BBT_PW(256, 12) BBT_PW(512, 12) BBT_PW(1024, 12) BBT_PW(2048, 12)
     BBT_PW(256, 16) BBT_PW(512, 16) BBT_PW(1024, 16) BBT_PW(2048, 16)
 #undef BBT_PW
-    return false;
 }
 
 template <int N>
@@ -2489,139 +2363,75 @@ static void launch_pfb(const bbt_pfb_plan* p, const float2* in, float2* out, int
                        (long long)n_spec, p->S, p->n_tap, p->taps, p->tab.tw0, p->tab.tw1);
 }
 
-// Which route a filter-bank plan takes.  Measured on MI355X (round 5, 1024 channels, G
-// stream-samples/s at 16 / 128 / 2048 streams): one pair per workgroup (16 bytes of every complete
-// sample per lane) 4 taps 140 / 99 / 82, 12 taps 107 / 54 / 54; two passes (window over whole rows,
-// transform in place: 33 bytes per stream-sample instead of 16) 150 / 159 / 146 and 144 / 154 / 133;
-// several pairs per workgroup, lanes over the pairs first (64- or 128-byte runs): 4 taps
-// 223 / 228 / 186, 12 taps 148 / 131 / 130 -- with 128 registers and at most two workgroups per CU
-// its NTAP + NG - 1 row loads for NG spectra weigh more the more taps there are.  Which of them
-// and which order of workgroups wins depends on taps, channels and streams, so the candidates
-// are timed once on scratch memory (as chan_pick) and the choice is remembered for the process.
-// BBT_PFB_TUNE=0: the round-4 rule (two passes from 16 streams on); BBT_PFB_TWO_PASS=0 / 1,
-// BBT_PFB_PP=4 / 8 (+ BBT_PFB_GL) force a route (dev).
 #ifndef BBT_PFB_NI
 #define BBT_PFB_NI 192                // spectra per sweep of the window pass (k_pfb_fir_rows): 96 -> 192 +2-5 %, 384 no better
 #endif
-static int pfb_pick(bbt_pfb_plan* p, bool pp_ok) {
-    const int n_tap = p->n_tap, n_stream = p->S;
-    const bool two_ok = !p->split_real && n_stream >= 2 && (n_tap == 4 || n_tap == 8 || n_tap == 12 || n_tap == 16);
-    const char* env2 = getenv("BBT_PFB_TWO_PASS");
-    const char* envp = getenv("BBT_PFB_PP");
-    auto set_pp = [&](int pp, int gl) {
-        p->pp = pp;
-        p->gl = (gl > 0 && (p->npair / pp) % gl == 0) ? gl : 0;
-    };
-    auto need_two_pass = [&]() -> int {
-        return p->two_pass ? 0 : bbt_chan_plan_create(&p->two_pass, p->n, n_stream, -1);
-    };
-    if (envp && pp_ok) {
-        const int pp = atoi(envp);
-        if ((pp == 4 || (pp == 8 && p->gn == 2048)) && p->npair % pp == 0) {
-            set_pp(pp, getenv("BBT_PFB_GL") ? atoi(getenv("BBT_PFB_GL")) : 0);
-            return 0;
-        }
+// The one place where a plan takes a route (pfb_geo.hpp: PfbCandidate).  `two_pass`: the channelizer
+// plan of the second pass, which the plan owns from here on if the route is two passes.
+static void pfb_apply(bbt_pfb_plan* p, const PfbCandidate& c, bbt_chan_plan* two_pass) {
+    p->two_pass = c.pp == 0 ? two_pass : nullptr;
+    p->pp = c.pp > 1 ? c.pp : 1;
+    p->gl = c.pp > 1 ? c.gl : 0;
+}
+// Which route the plan takes (pfb_geo.hpp: pfb_route): fixed, or the fastest of the candidates,
+// timed once on scratch memory (tune.hpp) and remembered for the process.  0 = ok.
+static int pfb_pick(bbt_pfb_plan* p, const PfbShape& shape, const PfbKnobs& knobs) {
+    const PfbRoute route = pfb_route(knobs, shape);
+    PfbCandidate best = route.fixed;
+    static TuneMemo<std::tuple<int, int, int, int>, PfbCandidate> chosen;   // (device, channels, taps, streams) -> route
+    std::tuple<int, int, int, int> key;
+    bool timed = route.timed;
+    if (timed) {
+        int dev = 0;
+        HIP_TRY(hipGetDevice(&dev));
+        key = std::make_tuple(dev, p->n, p->n_tap, p->S);
+        timed = !chosen.find(key, &best);
     }
-    // (two passes also where no sliding-window kernel exists and every spectrum would re-read its rows:
-    // 16 x 4096 on two streams 64.4 -> 84.2 G complete samples/s, 0.26 -> 0.34; with a window kernel one
-    // pass wins on few streams: 8 x 2048 125 against 91, 4 x 1024 164 against 88)
-    const bool rule_two = two_ok && (n_stream >= 16 || (!p->window && n_tap >= 8));
-    if (env2) return (two_ok && atoi(env2) != 0) ? need_two_pass() : 0;
-    const bool tune = !(getenv("BBT_PFB_TUNE") && !strcmp(getenv("BBT_PFB_TUNE"), "0"));
-    if (!pp_ok || !tune || n_stream < 8) return rule_two ? need_two_pass() : 0;
-
-    static std::mutex mu;
-    static std::map<std::tuple<int, int, int, int>, std::pair<int, int>> chosen;   // -> (pp: 0 two passes, 1 one pair; gl)
-    int dev = 0;
-    HIP_TRY(hipGetDevice(&dev));
-    const auto key = std::make_tuple(dev, p->n, n_tap, n_stream);
-    {
-        std::lock_guard<std::mutex> lock(mu);
-        auto it = chosen.find(key);
-        if (it != chosen.end()) {
-            if (it->second.first == 0) return need_two_pass();
-            if (it->second.first > 1) set_pp(it->second.first, it->second.second);
-            return 0;
-        }
-    }
-    if (two_ok && need_two_pass()) return 1;
-    bbt_chan_plan* const tp = p->two_pass;
-    const size_t per = (size_t)p->n * p->S * sizeof(cf);
-    const auto t_start = std::chrono::steady_clock::now();
-    auto trace = [&](const char* what, int x = 0, int y = 0) {
-        if (!getenv("BBT_PFB_TRACE")) return;
-        fprintf(stderr, "bbt: pfb_pick %d x %d on %d streams, %8.3f ms: %s %d %d\n", n_tap, p->n, n_stream,
-                std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_start).count(), what, x, y);
-        fflush(stderr);
-    };
-    trace("allocating");
-    // (scratch memory: tune_acquire; on the null stream, as chan_pick)
-    size_t got = 0;
-    char* base = (char*)tune_acquire((2 * 16 + n_tap) * per, (size_t)2 << 30, &got);
-    const int64_t ns = base ? (int64_t)((got - (n_tap - 1) * per) / (2 * per)) : 0;
-    void *a = base, *b = base ? base + (ns + n_tap - 1) * per : nullptr;
-    hipStream_t st = nullptr;
-    hipEvent_t e0 = nullptr, e1 = nullptr;
-    const bool ready = base && hipMemsetAsync(a, 0, (ns + n_tap - 1) * per, nullptr) == hipSuccess &&
-                       hipEventCreate(&e0) == hipSuccess &&
-                       hipEventCreate(&e1) == hipSuccess && hipDeviceSynchronize() == hipSuccess;
-    trace("allocated");
-    struct Cand { int pp, gl; };
-    std::vector<Cand> cands;
-    if (two_ok) cands.push_back({0, 0});
-    if (n_stream < 16) cands.push_back({1, 0});
-    cands.push_back({4, 0});
-    if ((p->npair / 4) % 4 == 0) cands.push_back({4, 4});
-    if (p->gn == 2048 && p->npair % 8 == 0) {
-        cands.push_back({8, 0});
-        if (p->npair / 8 > 1) cands.push_back({8, 1});
-    }
-    Cand best = rule_two ? Cand{0, 0} : Cand{1, 0};
-    float best_ms = 1e30f;
-    for (const Cand& c : cands) {
-        if (!ready) break;
-        p->two_pass = c.pp == 0 ? tp : nullptr;
-        p->pp = 1;
-        p->gl = 0;
-        if (c.pp > 1) set_pp(c.pp, c.gl);
-        float ms = 1e30f;
-        trace("candidate", c.pp, c.gl);
-        if (!bbt_pfb_execute(p, a, b, ns, st)) {
-            for (int r = 0; r < 2; ++r) {
-                float t = 0.f;
-                if (hipEventRecord(e0, st) != hipSuccess || bbt_pfb_execute(p, a, b, ns, st) ||
-                    hipEventRecord(e1, st) != hipSuccess || hipEventSynchronize(e1) != hipSuccess ||
-                    hipEventElapsedTime(&t, e0, e1) != hipSuccess) {
-                    ms = 1e30f;
-                    break;
+    // (a timed plan makes the channelizer plan of the second pass before the comparison)
+    bbt_chan_plan* tp = nullptr;
+    if ((timed ? shape.two_ok : best.pp == 0) && bbt_chan_plan_create(&tp, p->n, p->S, -1)) return 1;
+    if (timed) {
+        const int n_tap = p->n_tap;
+        const size_t per = (size_t)p->n * p->S * sizeof(cf);
+        const auto t_start = std::chrono::steady_clock::now();
+        auto trace = [&](const char* what, int x = 0, int y = 0) {
+            if (!getenv("BBT_PFB_TRACE")) return;
+            fprintf(stderr, "bbt: pfb_pick %d x %d on %d streams, %8.3f ms: %s %d %d\n", n_tap, p->n, p->S,
+                    std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_start).count(), what, x, y);
+            fflush(stderr);
+        };
+        trace("allocating");
+        bool ready;
+        {
+            // (input: ns + n_tap - 1 spectra, zeroed; output: ns spectra)
+            auto spectra = [&](size_t got) { return (int64_t)((got - (n_tap - 1) * per) / (2 * per)); };
+            TuneBench bench((2 * 16 + n_tap) * per, (size_t)2 << 30, [&](size_t got) { return (spectra(got) + n_tap - 1) * per; });
+            ready = bench.ready();
+            trace("allocated");
+            if (ready) {
+                const int64_t ns = spectra(bench.size());
+                void *in = bench.base(), *out = bench.base() + (ns + n_tap - 1) * per;
+                float best_ms = 1e30f;
+                for (const PfbCandidate& c : route.candidates) {
+                    pfb_apply(p, c, tp);
+                    trace("candidate", c.pp, c.gl);
+                    const float ms = bench.best_of([&](hipStream_t st) { return bbt_pfb_execute(p, in, out, ns, st); });
+                    if (getenv("BBT_RTC_VERBOSE"))
+                        fprintf(stderr, "bbt: PolyphaseFilterBank %d x %d on %d streams, %s (pairs %d, order %d): %.3f ms\n", n_tap,
+                                p->n, p->S, c.pp == 0 ? "two passes" : "one pass", c.pp, c.gl, ms);
+                    if (ms < best_ms) {
+                        best_ms = ms;
+                        best = c;
+                    }
                 }
-                ms = std::min(ms, t);
             }
+            trace("timed");
         }
-        if (getenv("BBT_RTC_VERBOSE"))
-            fprintf(stderr, "bbt: PolyphaseFilterBank %d x %d on %d streams, %s (pairs %d, order %d): %.3f ms\n", n_tap, p->n,
-                    n_stream, c.pp == 0 ? "two passes" : "one pass", c.pp, c.gl, ms);
-        if (ms < best_ms) {
-            best_ms = ms;
-            best = c;
-        }
+        trace("freed");
+        if (ready) chosen.remember(key, best);           // (no scratch memory: the rule, and nothing remembered)
     }
-    trace("timed");
-    if (e0) hipEventDestroy(e0);
-    if (e1) hipEventDestroy(e1);
-    if (base) tune_release();
-    if (!ready) hipGetLastError();
-    trace("freed");
-    p->two_pass = nullptr;
-    p->pp = 1;
-    p->gl = 0;
-    if (best.pp == 0) p->two_pass = tp;
-    else if (tp) bbt_chan_plan_destroy(tp);
-    if (best.pp > 1) set_pp(best.pp, best.gl);
-    if (ready) {
-        std::lock_guard<std::mutex> lock(mu);
-        chosen[key] = std::make_pair(best.pp, p->gl);
-    }
+    pfb_apply(p, best, tp);
+    if (tp && !p->two_pass) bbt_chan_plan_destroy(tp);
     return 0;
 }
 
@@ -2631,32 +2441,19 @@ int bbt_pfb_plan_create(bbt_pfb_plan** plan, int n_tap, int n_chan, int n_stream
                         const float* taps_host) {
     ARG_TRY(plan && taps_host, "bbt_pfb_plan_create: null argument");
     *plan = nullptr;
-    ARG_TRY(fft_len_ok(n_chan),
-            "bbt_pfb_plan_create: n_chan=%d must be a power of two in [256, 4096]", n_chan);
-    ARG_TRY(n_tap >= 1 && n_tap <= 64, "bbt_pfb_plan_create: n_tap=%d must be in [1, 64]", n_tap);
-    // n_stream -1: as 1, the stream being z = a + i b of two real streams; out receives their half
-    // spectra (n_spectra, n_chan / 2 + 1, 2) -- the filter bank of two float32 streams in one pass
-    // (a negative even n_stream -S: S such streams, in pairs)
-    const bool split_real = n_stream == -1 || (n_stream < 0 && n_stream % 2 == 0);
-    if (split_real) n_stream = -n_stream;
-    ARG_TRY(n_stream == 1 || (n_stream >= 2 && n_stream % 2 == 0 && n_stream <= 65535 * 2),
-            "bbt_pfb_plan_create: n_stream=%d must be even and >= 2", n_stream);
+    PfbShape shape;
+    std::string refusal;
+    if (!pfb_check(n_tap, n_chan, n_stream, &shape, &refusal)) return fail("%s", refusal.c_str());
     bbt_pfb_plan* p = new bbt_pfb_plan;
-    p->split_real = split_real;
+    p->split_real = shape.split_real;
     p->n = n_chan;
-    p->S = n_stream;
-    p->npair = n_stream / 2;
+    p->S = shape.S;
+    p->npair = shape.npair;
     p->n_tap = n_tap;
+    p->window = shape.window;
+    p->gn = shape.gn;
+    const bool pp_ok = shape.pp_ok;
     const size_t tb = (size_t)n_tap * n_chan * sizeof(float);
-    p->window = pfb_window_dispatch(p, nullptr, nullptr, 0, nullptr, true);
-    if ((n_stream == 1 || split_real) && !p->window) {   // only the sliding-window kernels take one stream / split
-        delete p;
-        return fail("bbt_pfb_plan_create: one stream needs n_chan in 256..2048 and 4, 8, 12 or 16 taps "
-                    "(got %d x %d); pad to two streams otherwise", n_tap, n_chan);
-    }
-    // several stream pairs per workgroup of the window kernel are possible for (pfb_pick chooses)
-    const bool pp_ok = p->window && !split_real && n_chan <= 2048 && p->npair % 4 == 0;
-    p->gn = pp_ok ? pfb_pp_geometry(n_chan) : 4096;
     if ((pp_ok && get_tables(p->gn, &p->tabg)) ||
         (p->window && get_tables(4096, &p->tab4096)) ||
         get_tables(n_chan, &p->tab) || hipMalloc((void**)&p->taps, tb) != hipSuccess ||
@@ -2666,17 +2463,9 @@ int bbt_pfb_plan_create(bbt_pfb_plan** plan, int n_tap, int n_chan, int n_stream
         return 1;
     }
     if (p->window) {
-        // taps of column tau + T c, four at a time: quads[((c * n_tap / 4) + q) * T + tau][k] = h[4 q + k]
-        // (T = 256 threads per pair; gn / 16 in the several-pairs form)
+        // (pfb_tap_quads: T = 256 threads per pair; gn / 16 in the several-pairs form)
         for (int form = 0; form < (pp_ok ? 2 : 1); ++form) {
-            const int T = form ? p->gn / 16 : 256, cols = n_chan / T, quads = n_tap / 4;
-            std::vector<float> perm((size_t)n_tap * n_chan);
-            for (int c = 0; c < cols; ++c)
-                for (int q = 0; q < quads; ++q)
-                    for (int tau = 0; tau < T; ++tau)
-                        for (int k = 0; k < 4; ++k)
-                            perm[(((size_t)c * quads + q) * T + tau) * 4 + k] =
-                                taps_host[(size_t)(4 * q + k) * n_chan + tau + T * c];
+            const std::vector<float> perm = pfb_tap_quads(taps_host, n_tap, n_chan, form ? p->gn / 16 : 256);
             float** dst = form ? &p->taps_quads_pp : &p->taps_quads;
             if (hipMalloc((void**)dst, tb) != hipSuccess ||
                 hipMemcpy(*dst, perm.data(), tb, hipMemcpyHostToDevice) != hipSuccess) {
@@ -2686,7 +2475,7 @@ int bbt_pfb_plan_create(bbt_pfb_plan** plan, int n_tap, int n_chan, int n_stream
             }
         }
     }
-    if (pfb_pick(p, pp_ok)) {
+    if (pfb_pick(p, shape, pfb_knobs_from_env())) {
         bbt_pfb_plan_destroy(p);
         return 1;
     }
@@ -2739,7 +2528,7 @@ int bbt_pfb_execute(bbt_pfb_plan* p, const void* in_dev, void* out_dev, int64_t 
             // input of slab s0 starts at spectrum s0 (same offset as the output, except
             // for half spectra of a real pair: n/2 + 1 channels x 2 streams per spectrum)
             const int64_t out_off = p->split_real ? s0 * (p->n / 2 + 1) * 2 * p->S : off;
-            pfb_window_dispatch(p, in + off, out + out_off, ns, st, false);
+            pfb_window_dispatch(p, in + off, out + out_off, ns, st);
             continue;
         }
         switch (p->n) {

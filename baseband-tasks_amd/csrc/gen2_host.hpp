@@ -43,7 +43,7 @@ struct G2Plan {
 // pipeline the six pairs (COL, ROW) in {10, 12, 16, 20} x {16, 20} all measured 34.1-35.5 G (800
 // MHz block) and 30.4-31.8 G (600 MHz): within the run-to-run spread, so both stay at 20.  The
 // streaming channelizer's optimum depends on the length: its plans time 10, 16 and 20 and keep
-// the fastest (bbt_hip.hip, chan_pick); CHAN is what is used untimed.  Environment variables of
+// the fastest (chan_geo.hpp, chan_pick); CHAN is what is used untimed.  Environment variables of
 // the same names override (dev).
 enum { BBT_G2_KIND_CHAN = 0, BBT_G2_KIND_COL = 1, BBT_G2_KIND_ROW = 2 };
 static inline int g2_pmax(int kind = BBT_G2_KIND_ROW) {

@@ -1,17 +1,37 @@
-// Prints what the host rules decide without a device, as JSON lines, for tests/test_gen2_planner.py
-// and tests/test_osm_geo.py:
+// Prints what the host rules decide without a device, as JSON lines, for tests/test_gen2_planner.py,
+// tests/test_osm_geo.py and tests/test_tune_geo.py:
 //   plan <pmax> <n> <ct> ...     a plan of the generic-length engine (csrc/gen2_host.hpp)
 //   split <N> ...                the measured split of a block and the plans of both kernels (csrc/osm_geo.hpp: osm_levels)
 //   route off|on|failed <N> ...  what a two-level block runs with on the general LDS Stockham kernels (csrc/gen_host.hpp)
 //   source <N> | source2 <N>     the translation unit an overlap-save plan compiles for a block (osm_g2_source)
 //   osm 0|1|failed <n_fft> <n_stream> ...   levels and buffers of a plan: BBT_RTC=0, compiled, compilation failed
 //   parts <run> <chunk> <cap> <lanes> <fork> ...   how a regular run is cut into launches (osm_run_parts)
-// No environment variable decides anything here: the knobs are the defaults.
+//   chan [dir=<d>] <n_chan> <n_stream> ...   a channelizer plan (csrc/chan_geo.hpp): its kind or the refusal, the candidates
+//                                a timed plan compares, and the untimed choice (-1: none) with the default knobs, with
+//                                BBT_G2_TUNE=0, with BBT_G2_CHAN_WIDE too, and with 116 remembered
+//   pfb <knobs> <n_tap> <n_chan> <n_stream> ...   a filter-bank plan (csrc/pfb_geo.hpp): the shape or the refusal, and the
+//                                route; knobs: - or a list of tune=0, two=0|1, pp=<n>, gl=<n> (the BBT_PFB_* switches)
+//   quads <n_tap> <n_chan> <T>   the taps h[i] = i as the window kernels read them (pfb_tap_quads)
+// No environment variable decides anything here: the knobs are the defaults, or the arguments.
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
-#include "osm_geo.hpp"
+#include "chan_geo.hpp"
+#include "pfb_geo.hpp"
 using namespace bbt;
+
+static const char* chan_kind_name(ChanKind k) {
+    return k == CHAN_SHORT ? "short" : k == CHAN_ROWS ? "rows" : k == CHAN_BIG ? "big" : "generic";
+}
+static void print_text(const std::string& text) {        // as a JSON string
+    putchar('"');
+    for (char c : text) {
+        if (c == '\n') printf("\\n");
+        else if (c == '"' || c == '\\') printf("\\%c", c);
+        else putchar(c);
+    }
+    putchar('"');
+}
 
 static void dump(const G2Plan& g) {
     printf("{\"n\": %d, \"tj\": %d, \"ct\": %d, \"threads\": %d, \"slots\": %d, \"lds_elems\": %d, \"table_len\": %d, \"fac\": [",
@@ -90,7 +110,7 @@ int main(int argc, char** argv) {
         } else if (!g.compiled || (g.n1 > 1) != two) {
             return 1;
         }
-        // (source: with the channelizer's kernel on the same traits -- chan_pick of bbt_hip.hip -- as a second entry point)
+        // (source: with the channelizer's kernel on the same traits -- chan_g2_candidate of csrc/chan_geo.hpp -- as a second entry point)
         printf("%s%s", osm_g2_source(g).text.c_str(), two ? "" : "BBT_G2_KERNEL_FFT_ROWS(k_rows, GA, -1, 0)\n");
     } else if (!strcmp(argv[1], "osm")) {
         OsmKnobs knobs;
@@ -116,6 +136,80 @@ int main(int argc, char** argv) {
             osm_run_parts(atoll(argv[i]), atoi(argv[i + 1]), atoi(argv[i + 2]), atoi(argv[i + 3]), atoi(argv[i + 4]) != 0, &parts, &per);
             printf("{\"parts\": %lld, \"per\": %lld}\n", (long long)parts, (long long)per);
         }
+    } else if (!strcmp(argv[1], "chan")) {
+        int direction = -1;
+        int i = 2;
+        if (!strncmp(argv[i], "dir=", 4)) direction = atoi(argv[i++] + 4);
+        for (; i + 1 < argc; i += 2) {
+            const int n_chan = atoi(argv[i]), n_stream = atoi(argv[i + 1]);
+            ChanShape shape;
+            std::string error;
+            printf("{\"n_chan\": %d, \"n_stream\": %d, ", n_chan, n_stream);
+            if (!chan_check(n_chan, n_stream, direction, &shape, &error)) {
+                printf("\"error\": ");
+                print_text(error);
+                printf("}\n");
+                continue;
+            }
+            ChanKnobs untimed, untimed_wide;
+            untimed.tune = untimed_wide.tune = false;
+            untimed_wide.wide = true;
+            printf("\"kind\": \"%s\", \"single\": %s, \"split_real\": %s, \"direction\": %d, \"untimed\": [%d, %d, %d, %d], "
+                   "\"candidates\": [", chan_kind_name(shape.kind), shape.single ? "true" : "false", shape.split_real ? "true" : "false",
+                   shape.direction, chan_untimed_code(-1, ChanKnobs()), chan_untimed_code(-1, untimed),
+                   chan_untimed_code(-1, untimed_wide), chan_untimed_code(116, untimed));
+            // (8192 channels: what the rule would list on its own -- the product runs them on the `big` kernels)
+            if (shape.kind == CHAN_GENERIC || n_chan == BBT_GEN_MAX_LEN) {
+                bool first = true;
+                for (const ChanCandidate& c : chan_candidates(n_chan, n_stream / 2, shape.direction, ChanKnobs(), &error)) {
+                    printf("%s{\"code\": %d, \"cp\": %d, \"plan\": ", first ? "" : ", ", c.code, c.cp);
+                    dump(c.q);
+                    printf(", \"source\": ");
+                    print_text(c.source);
+                    printf("}");
+                    first = false;
+                }
+            }
+            printf("]}\n");
+        }
+    } else if (!strcmp(argv[1], "pfb")) {
+        PfbKnobs knobs;
+        for (const char* a = argv[2]; a && *a && *a != '-'; a = strchr(a, ',') ? strchr(a, ',') + 1 : nullptr) {
+            if (!strncmp(a, "tune=", 5)) knobs.tune = atoi(a + 5) != 0;
+            else if (!strncmp(a, "two=", 4)) knobs.two_pass = atoi(a + 4) != 0;
+            else if (!strncmp(a, "pp=", 3)) knobs.pp = atoi(a + 3);
+            else if (!strncmp(a, "gl=", 3)) knobs.gl = atoi(a + 3);
+            else return 2;
+        }
+        for (int i = 3; i + 2 < argc; i += 3) {
+            const int n_tap = atoi(argv[i]), n_chan = atoi(argv[i + 1]), n_stream = atoi(argv[i + 2]);
+            PfbShape s;
+            std::string error;
+            printf("{\"n_tap\": %d, \"n_chan\": %d, \"n_stream\": %d, ", n_tap, n_chan, n_stream);
+            if (!pfb_check(n_tap, n_chan, n_stream, &s, &error)) {
+                printf("\"error\": ");
+                print_text(error);
+                printf("}\n");
+                continue;
+            }
+            const PfbRoute r = pfb_route(knobs, s);
+            printf("\"streams\": %d, \"split_real\": %s, \"window\": %s, \"pp_ok\": %s, \"gn\": %d, \"two_ok\": %s, "
+                   "\"rule_two\": %s, \"timed\": %s, \"fixed\": [%d, %d], \"candidates\": [", s.S, s.split_real ? "true" : "false",
+                   s.window ? "true" : "false", s.pp_ok ? "true" : "false", s.gn, s.two_ok ? "true" : "false",
+                   s.rule_two ? "true" : "false", r.timed ? "true" : "false", r.fixed.pp, r.fixed.gl);
+            for (size_t c = 0; c < r.candidates.size(); ++c)
+                printf("%s[%d, %d]", c ? ", " : "", r.candidates[c].pp, r.candidates[c].gl);
+            printf("]}\n");
+        }
+    } else if (!strcmp(argv[1], "quads")) {
+        if (argc < 5) return 2;
+        const int n_tap = atoi(argv[2]), n_chan = atoi(argv[3]), T = atoi(argv[4]);
+        std::vector<float> h((size_t)n_tap * n_chan);
+        for (size_t j = 0; j < h.size(); ++j) h[j] = (float)j;
+        const std::vector<float> q = pfb_tap_quads(h.data(), n_tap, n_chan, T);
+        printf("[");
+        for (size_t j = 0; j < q.size(); ++j) printf("%s%d", j ? ", " : "", (int)q[j]);
+        printf("]\n");
     }
     return 0;
 }

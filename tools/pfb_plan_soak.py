@@ -1,5 +1,6 @@
 """Create filter-bank plans over and over (dev tool): every plan on 8 streams and more times its
-routes (bbt_hip.hip pfb_pick); BBT_PFB_TRACE=1 prints each step."""
+routes (csrc/pfb_geo.hpp pfb_route, timed by pfb_pick of bbt_hip.hip through csrc/tune.hpp); BBT_PFB_TRACE=1 prints
+each step."""
 import os, sys, time, ctypes
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np, torch
