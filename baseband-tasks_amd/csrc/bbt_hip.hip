@@ -11,6 +11,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <initializer_list>
 #include <map>
 #include <mutex>
 #include <string>
@@ -32,6 +33,7 @@
 #include "phase_kernels.hpp"
 #include "modulate_kernels.hpp"
 #include "sk_kernels.hpp"
+#include "dmt_kernels.hpp"
 #include "r2c_kernels.hpp"
 #include "gather_kernels.hpp"
 #include "pack_kernels.hpp"
@@ -41,7 +43,7 @@
 
 using namespace bbt;
 
-#define BBT_VERSION 162
+#define BBT_VERSION 163
 
 // ---------------------------------------------------------------------------
 // errors
@@ -3625,6 +3627,106 @@ extern "C" int bbt_shift_execute(bbt_shift_plan* p, const void* in_dev, void* ou
     else
         hipLaunchKernelGGL((k_shift_samples<float, ITER>), grid, block, 0, st, (const float*)in_dev,
                            (float*)out_dev, (long long)n_out, n_elem, lg_le, offset);
+    HIP_TRY(hipGetLastError());
+    return 0;
+}
+
+// ---------------------------------------------------------------------------
+// incoherent dedispersion over many trial DMs (dmt_kernels.hpp; the tiling is dmt_geo.hpp's)
+struct bbt_dmt_plan {
+    int ndm = 0, nchan = 0, n_rest = 0, ndm_pad = 0, span = 0;
+    int* tab = nullptr;              // [nchan][ndm_pad], padding entries 0
+    float* scratch = nullptr;        // the transposed chunk, grown on demand
+    long long scratch_floats = 0;
+};
+
+// BBT_DMT_TILE: output times of a workgroup (64, 128, 256); BBT_DMT_TRIALS: trials a thread holds
+// (1, 2, 4, 8, 16).  For measuring and for the tests that walk the tilings; no value of the output
+// depends on either.  Anything else leaves the default.
+static int dmt_env(const char* name, std::initializer_list<int> allowed) {
+    const char* e = getenv(name);
+    if (e && *e) {
+        const int v = atoi(e);
+        for (int a : allowed)
+            if (v == a) return v;
+    }
+    return 0;
+}
+
+extern "C" int bbt_dmt_plan_destroy(bbt_dmt_plan* p) {
+    if (!p) return 0;
+    if (p->tab) hipFree(p->tab);
+    if (p->scratch) hipFree(p->scratch);
+    delete p;
+    return 0;
+}
+
+extern "C" int bbt_dmt_plan_create(bbt_dmt_plan** plan, const int32_t* offsets_host, int64_t ndm, int64_t nchan,
+                                   int64_t n_rest) {
+    ARG_TRY(plan && offsets_host, "bbt_dmt_plan_create: null argument");
+    *plan = nullptr;
+    const char* err = dmt_sizes(ndm, nchan, n_rest);
+    ARG_TRY(!err, "bbt_dmt_plan_create: %s", err ? err : "");
+    long long span = 0;
+    for (long long i = 0; i < (long long)ndm * nchan; ++i) span = std::max<long long>(span, offsets_host[i]);
+    err = dmt_check_table(offsets_host, (long long)ndm * nchan, span);
+    ARG_TRY(!err, "bbt_dmt_plan_create: %s", err ? err : "");
+    bbt_dmt_plan* p = new bbt_dmt_plan;
+    p->ndm = (int)ndm, p->nchan = (int)nchan, p->n_rest = (int)n_rest, p->span = (int)span;
+    p->ndm_pad = dmt_pad_ndm((int)ndm);
+    std::vector<int> tab((size_t)nchan * p->ndm_pad, 0);
+    for (long long d = 0; d < ndm; ++d)
+        for (long long c = 0; c < nchan; ++c) tab[(size_t)c * p->ndm_pad + d] = offsets_host[d * nchan + c];
+    if (hipMalloc((void**)&p->tab, tab.size() * sizeof(int)) != hipSuccess ||
+        hipMemcpy(p->tab, tab.data(), tab.size() * sizeof(int), hipMemcpyHostToDevice) != hipSuccess) {
+        fail("bbt_dmt_plan_create: uploading the table failed");
+        bbt_dmt_plan_destroy(p);
+        return 1;
+    }
+    *plan = p;
+    return 0;
+}
+
+extern "C" int bbt_dmt_plan_info(const bbt_dmt_plan* p, int64_t* span, int* tile_t, int* trials,
+                                 int64_t* scratch_bytes) {
+    ARG_TRY(p, "bbt_dmt_plan_info: null argument");
+    const int t = dmt_env("BBT_DMT_TILE", {64, 128, 256}), b = dmt_env("BBT_DMT_TRIALS", {1, 2, 4, 8, 16});
+    if (span) *span = p->span;
+    if (tile_t) *tile_t = t ? t : BBT_DMT_TILE;
+    if (trials) *trials = b ? b : BBT_DMT_DB;
+    if (scratch_bytes) *scratch_bytes = p->scratch_floats * (long long)sizeof(float);
+    return 0;
+}
+
+// out[i][d][r], i < n_out, from in[t][c][r], t < n_in.  One plan serves one stream at a time: the
+// scratch is the plan's.
+extern "C" int bbt_dmt_execute(bbt_dmt_plan* p, const float* in_dev, int64_t n_in, float* out_dev, int64_t n_out,
+                               bbt_stream stream) {
+    ARG_TRY(p && in_dev && out_dev, "bbt_dmt_execute: null argument");
+    ARG_TRY((((uintptr_t)in_dev | (uintptr_t)out_dev) & 3) == 0, "bbt_dmt_execute: arrays must be 4-byte aligned");
+    DmtGeo g = {};
+    const char* err = dmt_geo(n_in, n_out, p->nchan, p->n_rest, p->ndm, p->span,
+                              dmt_env("BBT_DMT_TILE", {64, 128, 256}), dmt_env("BBT_DMT_TRIALS", {1, 2, 4, 8, 16}), &g);
+    ARG_TRY(!err, "bbt_dmt_execute: %s (n_in=%lld, n_out=%lld, span=%d)", err ? err : "", (long long)n_in,
+            (long long)n_out, p->span);
+    if (g.scratch > p->scratch_floats) {
+        if (p->scratch) HIP_TRY(hipFree(p->scratch));          // (waits for the launches that use it)
+        p->scratch = nullptr, p->scratch_floats = 0;
+        HIP_TRY(hipMalloc((void**)&p->scratch, (size_t)g.scratch * sizeof(float)));
+        p->scratch_floats = g.scratch;
+    }
+    hipStream_t st = (hipStream_t)stream;
+    hipLaunchKernelGGL(k_dmt_transpose, dim3((unsigned)g.tr_t, (unsigned)g.tr_e), dim3(BBT_DMT_THREADS), 0, st, in_dev,
+                       p->scratch, (long long)n_in, p->nchan * p->n_rest, g.pitch);
+    HIP_TRY(hipGetLastError());
+    const dim3 grid((unsigned)g.n_wg), block(BBT_DMT_THREADS);
+    switch (g.db) {
+        case 1: hipLaunchKernelGGL((k_dmt_sweep<1>), grid, block, 0, st, p->scratch, p->tab, out_dev, g); break;
+        case 2: hipLaunchKernelGGL((k_dmt_sweep<2>), grid, block, 0, st, p->scratch, p->tab, out_dev, g); break;
+        case 4: hipLaunchKernelGGL((k_dmt_sweep<4>), grid, block, 0, st, p->scratch, p->tab, out_dev, g); break;
+        case 8: hipLaunchKernelGGL((k_dmt_sweep<8>), grid, block, 0, st, p->scratch, p->tab, out_dev, g); break;
+        default: hipLaunchKernelGGL((k_dmt_sweep<16>), grid, block, 0, st, p->scratch, p->tab, out_dev, g); break;
+    }
     HIP_TRY(hipGetLastError());
     return 0;
 }

@@ -171,6 +171,34 @@ class Dedisperse(Disperse):
         return -self._dm
 
 
+def with_band(ih, frequency=None, sideband=None):
+    """``ih``, under a `SetAttribute` where ``frequency`` or ``sideband`` override its own."""
+    if frequency is not None or sideband is not None:
+        from .base import SetAttribute
+        ih = SetAttribute(ih, frequency=frequency, sideband=sideband)
+    return ih
+
+
+def dispersion_sample_delays(ih, dms, reference_frequency=None):
+    """The dispersive delays of the streams of ``ih``, in samples (float64, not rounded), for each
+    of the `DispersionMeasure` ``dms``, and the reference frequency in Hz they are relative to:
+    ``(list of arrays shaped like ih.frequency, reference_frequency)``.
+
+    The arithmetic `DisperseSamples` and `search.DMTrials` share: the delay at ``ih.frequency`` --
+    plus ``sideband * sample_rate / 2``, the mid-channel frequency, where the stream is not complex
+    -- relative to ``reference_frequency`` (default: the mean of those frequencies)."""
+    frequency = ih.frequency
+    if np.dtype(ih.dtype).kind != 'c':
+        # mid-channel frequency of a real stream
+        frequency = frequency + ih.sideband * _stream_rate(ih) / 2.
+    if reference_frequency is None:
+        reference_frequency = np.mean(frequency)
+    else:
+        reference_frequency = u.to_hz(reference_frequency)
+    rate = _stream_rate(ih)
+    return [dm.time_delay(frequency, reference_frequency) * rate for dm in dms], reference_frequency
+
+
 class DisperseSamples(ShiftSamples):
     """Incoherent dispersion: shift every stream by the dispersive delay at its
     mid-channel frequency, rounded to whole samples (no in-channel smearing;
@@ -178,20 +206,10 @@ class DisperseSamples(ShiftSamples):
 
     def __init__(self, ih, dm, *, reference_frequency=None, samples_per_frame=None,
                  frequency=None, sideband=None):
-        if frequency is not None or sideband is not None:
-            from .base import SetAttribute
-            ih = SetAttribute(ih, frequency=frequency, sideband=sideband)
-        frequency = ih.frequency
-        if np.dtype(ih.dtype).kind != 'c':
-            # mid-channel frequency of a real stream
-            frequency = frequency + ih.sideband * _stream_rate(ih) / 2.
-        if reference_frequency is None:
-            reference_frequency = np.mean(frequency)
-        else:
-            reference_frequency = u.to_hz(reference_frequency)
+        ih = with_band(ih, frequency, sideband)
         dm = DispersionMeasure(dm)
-        delay = dm.time_delay(frequency, reference_frequency)          # seconds
-        super().__init__(ih, delay * _stream_rate(ih), samples_per_frame=samples_per_frame)
+        (delay,), reference_frequency = dispersion_sample_delays(ih, [dm], reference_frequency)
+        super().__init__(ih, delay, samples_per_frame=samples_per_frame)
         self.reference_frequency = reference_frequency
         self._dm = dm
 

@@ -108,6 +108,10 @@ SIGNATURES = {
     'bbt_shift_plan_create': [_pvp, _int, _int, _pi32],
     'bbt_shift_plan_destroy': [_vp],
     'bbt_shift_execute': [_vp, _vp, _vp, _i64, _vp],
+    'bbt_dmt_plan_create': [_pvp, _pi32, _i64, _i64, _i64],
+    'bbt_dmt_plan_destroy': [_vp],
+    'bbt_dmt_plan_info': [_vp, _pi64, C.POINTER(_int), C.POINTER(_int), _pi64],
+    'bbt_dmt_execute': [_vp, _vp, _i64, _vp, _i64, _vp],
     'bbt_fir_plan_create': [_pvp, _int, _int, _vp],
     'bbt_fir_plan_destroy': [_vp],
     'bbt_fir_execute': [_vp, _vp, _vp, _i64, _vp],
@@ -142,7 +146,7 @@ SIGNATURES = {
 }
 
 #: oldest libbbt_hip.so whose entry points and argument meanings this binding assumes
-MIN_LIB_VERSION = 162
+MIN_LIB_VERSION = 163
 
 _lib = None
 _lock = threading.Lock()
@@ -1623,6 +1627,50 @@ class ShiftPlan(_Plan):
 
     def execute(self, in_dev, out_dev, n_out):
         check(lib().bbt_shift_execute(self._h, in_dev.ptr_to_read(), out_dev.ptr, int(n_out), _stream))
+
+
+#: bounds of the trial-DM plan (csrc/dmt_geo.hpp)
+DMT_MAX_NCHAN, DMT_MAX_NDM, DMT_MAX_REST, DMT_MAX_SPAN = 16384, 4096, 64, 1 << 24
+
+
+class DmtPlan(_Plan):
+    """out[i, d, r] = sum over c, ascending, of in[i + offsets[d, c], c, r]: incoherent dedispersion
+    over ``ndm`` trial DMs, one float32 accumulator per output element (bbt_dmt_* in
+    include/bbt_hip.h; `search.dm_trials_samples` is the NumPy restatement).  ``offsets``: int
+    ``(ndm, nchan)``, all >= 0; the plan's ``span`` is the largest."""
+    _destroy = 'bbt_dmt_plan_destroy'
+
+    def __init__(self, offsets, n_rest=1):
+        super().__init__()
+        offsets = np.asarray(offsets)
+        if offsets.ndim != 2 or offsets.dtype.kind not in 'iu':
+            raise ValueError("DmtPlan: offsets must be an integer array (ndm, nchan)")
+        if offsets.size and (offsets.min() < -(1 << 31) or offsets.max() >= (1 << 31)):
+            raise ValueError("DmtPlan: offsets must fit 32 bits")
+        offsets = np.ascontiguousarray(offsets, dtype=np.int32)
+        self.ndm, self.nchan = offsets.shape
+        self.n_rest = int(n_rest)
+        check(lib().bbt_dmt_plan_create(C.byref(self._h), offsets.ctypes.data_as(_pi32), self.ndm, self.nchan,
+                                        self.n_rest))
+        self.span = self.info()['span']
+
+    def info(self):
+        """span of the table, the tiling the next call will use (BBT_DMT_TILE, BBT_DMT_TRIALS) and
+        the bytes of scratch the plan holds."""
+        span, scratch, tile, trials = _i64(0), _i64(0), _int(0), _int(0)
+        check(lib().bbt_dmt_plan_info(self._h, C.byref(span), C.byref(tile), C.byref(trials), C.byref(scratch)))
+        return dict(span=span.value, tile=tile.value, trials=trials.value, scratch_bytes=scratch.value)
+
+    def execute(self, in_dev, n_in, out_dev, n_out):
+        """``in_dev``: float32, at least ``n_in * nchan * n_rest`` values; ``out_dev``: float32, at
+        least ``n_out * ndm * n_rest``; ``n_in >= n_out + span``."""
+        n_in, n_out = int(n_in), int(n_out)
+        row_in, row_out = self.nchan * self.n_rest, self.ndm * self.n_rest
+        if (in_dev.dtype != np.float32 or out_dev.dtype != np.float32 or n_in < 0 or n_out < 0
+                or in_dev.size < n_in * row_in or out_dev.size < n_out * row_out):
+            raise ValueError("DmtPlan.execute: float32 DeviceArrays of n_in * nchan * n_rest and "
+                             "n_out * ndm * n_rest values are needed")
+        check(lib().bbt_dmt_execute(self._h, in_dev.ptr_to_read(), n_in, out_dev.ptr, n_out, _stream))
 
 
 COMM_ID_BYTES = 128

@@ -46,6 +46,7 @@ typedef struct bbt_osm_plan bbt_osm_plan;
 typedef struct bbt_chan_plan bbt_chan_plan;
 typedef struct bbt_pfb_plan bbt_pfb_plan;
 typedef struct bbt_shift_plan bbt_shift_plan;
+typedef struct bbt_dmt_plan bbt_dmt_plan;
 typedef struct bbt_fir_plan bbt_fir_plan;
 typedef struct bbt_r2c_plan bbt_r2c_plan;
 typedef struct bbt_gather_plan bbt_gather_plan;
@@ -531,6 +532,29 @@ int bbt_shift_plan_create(bbt_shift_plan** plan, int n_elem, int elem_bytes,
 int bbt_shift_plan_destroy(bbt_shift_plan* plan);
 int bbt_shift_execute(bbt_shift_plan* plan, const void* in_dev, void* out_dev, int64_t n_out,
                       bbt_stream stream);
+
+/* ---- incoherent dedispersion over many trial DMs: DMTrials --------------------
+ * in holds n_in samples of nchan channels of n_rest elements, float32, in[t][c][r]; the table is
+ * offsets[d][c], d < ndm, every entry in [0, span] with span its largest entry.  For i < n_out,
+ *   out[i][d][r] = sum over c of in[i + offsets[d][c]][c][r]        (float32 [n_out][ndm][n_rest])
+ * with ONE float32 accumulator per output element, started at +0, the channels added in ascending c,
+ * one rounded add per channel.  That order is the contract: results do not depend on the launch or the
+ * tiling (BBT_DMT_TILE = 64, 128 or 256 output times per workgroup and BBT_DMT_TRIALS = 1, 2, 4, 8 or 16
+ * trials per thread, read from the environment at every call, only change the speed), and a NaN or Inf
+ * reaches exactly the outputs whose sweep crosses it.
+ * The plan owns the device copy of the table and a scratch of the chunk's size (the chunk transposed to
+ * time-fastest), which grows to the largest n_in it has seen; it serves one stream at a time.
+ * Limits: ndm <= 4096, nchan <= 16384, n_rest <= 64, span <= 2^24, n_in <= 2^40; indices are 64-bit.
+ * create refuses a null pointer, sizes beyond the limits, a negative offset and a span above 2^24;
+ * execute refuses a null pointer, n_out < 1 and n_in < n_out + span -- all before anything is launched.
+ * Asynchronous on `stream`. */
+int bbt_dmt_plan_create(bbt_dmt_plan** plan, const int32_t* offsets_host, int64_t ndm, int64_t nchan,
+                        int64_t n_rest);
+int bbt_dmt_plan_destroy(bbt_dmt_plan* plan);
+int bbt_dmt_plan_info(const bbt_dmt_plan* plan, int64_t* span, int* tile_t, int* trials,
+                      int64_t* scratch_bytes);
+int bbt_dmt_execute(bbt_dmt_plan* plan, const float* in_dev, int64_t n_in, float* out_dev, int64_t n_out,
+                    bbt_stream stream);
 
 /* ---- real-valued streams ------------------------------------------------------
  * float32 streams run through the complex kernels (the reference's rfft/irfft
