@@ -23,7 +23,9 @@ from .functions import Square, Power
 from .integration import Integrate, Fold, PulseStack
 from .modulation import Modulate, modulate_samples
 from .rfi import SpectralKurtosis, Excise, sk_limits, spectral_kurtosis, excise_flags, excise_samples
-from .search import DMTrials, dm_trial_shifts, dm_trials_samples
+from .search import (DMTrials, dm_trial_shifts, dm_trials_samples, Standardize, standardize_samples,
+                     BoxcarSearch, boxcar_search_samples, boxcar_candidates)
+from . import search
 from .conversion import Real2Complex
 from .shaping import (ChangeSampleShapeBase, ChangeSampleShape, Reshape, Transpose, ReshapeAndTranspose,
                       GetItem, GetSlice)

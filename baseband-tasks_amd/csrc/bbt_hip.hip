@@ -34,6 +34,7 @@
 #include "modulate_kernels.hpp"
 #include "sk_kernels.hpp"
 #include "dmt_kernels.hpp"
+#include "sps_kernels.hpp"
 #include "r2c_kernels.hpp"
 #include "gather_kernels.hpp"
 #include "pack_kernels.hpp"
@@ -43,7 +44,7 @@
 
 using namespace bbt;
 
-#define BBT_VERSION 163
+#define BBT_VERSION 164
 
 // ---------------------------------------------------------------------------
 // errors
@@ -3726,6 +3727,112 @@ extern "C" int bbt_dmt_execute(bbt_dmt_plan* p, const float* in_dev, int64_t n_i
         case 4: hipLaunchKernelGGL((k_dmt_sweep<4>), grid, block, 0, st, p->scratch, p->tab, out_dev, g); break;
         case 8: hipLaunchKernelGGL((k_dmt_sweep<8>), grid, block, 0, st, p->scratch, p->tab, out_dev, g); break;
         default: hipLaunchKernelGGL((k_dmt_sweep<16>), grid, block, 0, st, p->scratch, p->tab, out_dev, g); break;
+    }
+    HIP_TRY(hipGetLastError());
+    return 0;
+}
+
+// ---------------------------------------------------------------------------
+// single-pulse search on the (time, DM) plane (sps_kernels.hpp; the tiling is sps_geo.hpp's)
+struct bbt_sps_plan {
+    long long n = 0, n_elem = 0;
+    int K = 0;
+    float* scratch = nullptr;        // the partial sums between passes, grown on demand
+    long long scratch_floats = 0;
+};
+
+// BBT_SPS_WIDTH: elements of a boxcar workgroup (16, 32, 64); BBT_SPS_FUSE: levels per pass (1, 2, 3);
+// BBT_SPS_SPLIT: threads that share a (block, element) at most (1, 2, 4, 8, 16); BBT_SPS_STD_ROWS: threads
+// along the segments in Standardize (1, 2, 4, 8, 16).  For measuring and for the tests that walk the
+// tilings; no value of the output depends on any.  Anything else leaves the default.
+static int sps_env_width() { return dmt_env("BBT_SPS_WIDTH", {16, 32, 64}); }
+static int sps_env_fuse() { return dmt_env("BBT_SPS_FUSE", {1, 2, 3}); }
+static int sps_env_split() { return dmt_env("BBT_SPS_SPLIT", {1, 2, 4, 8, 16}); }
+static int sps_env_rows() { return dmt_env("BBT_SPS_STD_ROWS", {1, 2, 4, 8, 16}); }
+
+// out[b * n + t][e] = (x[b * n + t][e] - mean) * (1 / sd) of block b < n_block, element e < n_elem
+extern "C" int bbt_sps_standardize(const float* x_dev, float* out_dev, int64_t n_block, int64_t n, int64_t n_elem,
+                                   bbt_stream stream) {
+    ARG_TRY(x_dev && out_dev, "bbt_sps_standardize: null argument");
+    ARG_TRY((((uintptr_t)x_dev | (uintptr_t)out_dev) & 3) == 0, "bbt_sps_standardize: arrays must be 4-byte aligned");
+    StdGeo g = {};
+    const char* err = sps_std_geo(n_block, n, n_elem, sps_env_rows(), &g);
+    ARG_TRY(!err, "bbt_sps_standardize: %s (n_block=%lld, n=%lld, n_elem=%lld)", err ? err : "", (long long)n_block,
+            (long long)n, (long long)n_elem);
+    hipLaunchKernelGGL(k_sps_standardize, dim3((unsigned)g.n_wg), dim3(BBT_SPS_THREADS), 0, (hipStream_t)stream, x_dev,
+                       out_dev, g);
+    HIP_TRY(hipGetLastError());
+    return 0;
+}
+
+extern "C" int bbt_sps_plan_destroy(bbt_sps_plan* p) {
+    if (!p) return 0;
+    if (p->scratch) hipFree(p->scratch);
+    delete p;
+    return 0;
+}
+
+extern "C" int bbt_sps_plan_create(bbt_sps_plan** plan, int64_t n, int64_t n_widths, int64_t n_elem) {
+    ARG_TRY(plan, "bbt_sps_plan_create: null argument");
+    *plan = nullptr;
+    const char* err = sps_sizes(n, n_widths, n_elem);
+    ARG_TRY(!err, "bbt_sps_plan_create: %s", err ? err : "");
+    bbt_sps_plan* p = new bbt_sps_plan;
+    p->n = n, p->K = (int)n_widths, p->n_elem = n_elem;
+    *plan = p;
+    return 0;
+}
+
+// the tiling the next call will use and the bytes of scratch the plan holds (plan may be null: the
+// tiling only); scales: 13 floats, c_k
+extern "C" int bbt_sps_plan_info(const bbt_sps_plan* p, int* width, int* fuse, int* split, int* std_rows,
+                                 int64_t* scratch_bytes, float* scales) {
+    const int w = sps_env_width(), f = sps_env_fuse(), s = sps_env_split(), r = sps_env_rows();
+    if (width) *width = w ? w : BBT_SPS_WIDTH;
+    if (fuse) *fuse = f ? f : BBT_SPS_FUSE;
+    if (split) *split = s ? s : BBT_SPS_SPLIT;
+    if (std_rows) *std_rows = r ? r : BBT_SPS_STD_ROWS;
+    if (scratch_bytes) *scratch_bytes = p ? p->scratch_floats * (long long)sizeof(float) : 0;
+    if (scales)
+        for (int k = 0; k < BBT_SPS_MAX_WIDTHS; ++k) scales[k] = sps_scale(k);
+    return 0;
+}
+
+template <int F>
+static void sps_launch(const bbt_sps_plan* p, const SpsGeo& g, const float* in_dev, float* out_dev, hipStream_t st) {
+    float* buf[2] = {p->scratch, p->scratch + (g.n_pass > 2 ? g.n_in * g.n_elem : 0)};
+    const float* src = in_dev;
+    for (int q = 0; q < g.n_pass; ++q) {
+        const SpsPass ps = sps_pass(g, q);
+        float* dst = ps.store ? buf[q & 1] : nullptr;
+        const float c0 = g.c[ps.k0], c1 = ps.levels > 1 ? g.c[ps.k0 + 1] : 0.f, c2 = ps.levels > 2 ? g.c[ps.k0 + 2] : 0.f;
+        hipLaunchKernelGGL((k_sps_pass<F>), dim3((unsigned)ps.n_wg), dim3(BBT_SPS_THREADS), 0, st, src, dst, out_dev, g,
+                           ps.k0, ps.blocks, (int)ps.store, (int)(q == 0), (int)(q == g.n_pass - 1), c0, c1, c2);
+        src = dst;
+    }
+}
+
+// best[b][3][e], b < n_blocks, from in[t][e], t < n_in, n_in >= n_blocks * n: windows may run on into
+// in[n_blocks * n ...] as far as n_in goes.  One plan serves one stream at a time: the scratch is the plan's.
+extern "C" int bbt_sps_execute(bbt_sps_plan* p, const float* in_dev, int64_t n_in, float* out_dev, int64_t n_blocks,
+                               bbt_stream stream) {
+    ARG_TRY(p && in_dev && out_dev, "bbt_sps_execute: null argument");
+    ARG_TRY((((uintptr_t)in_dev | (uintptr_t)out_dev) & 3) == 0, "bbt_sps_execute: arrays must be 4-byte aligned");
+    SpsGeo g = {};
+    const char* err = sps_geo(n_in, n_blocks, p->n, p->K, p->n_elem, sps_env_width(), sps_env_fuse(), sps_env_split(), &g);
+    ARG_TRY(!err, "bbt_sps_execute: %s (n_in=%lld, n_blocks=%lld, n=%lld)", err ? err : "", (long long)n_in,
+            (long long)n_blocks, p->n);
+    if (g.scratch > p->scratch_floats) {
+        if (p->scratch) HIP_TRY(hipFree(p->scratch));          // (waits for the launches that use it)
+        p->scratch = nullptr, p->scratch_floats = 0;
+        HIP_TRY(hipMalloc((void**)&p->scratch, (size_t)g.scratch * sizeof(float)));
+        p->scratch_floats = g.scratch;
+    }
+    hipStream_t st = (hipStream_t)stream;
+    switch (g.fuse) {
+        case 1: sps_launch<1>(p, g, in_dev, out_dev, st); break;
+        case 2: sps_launch<2>(p, g, in_dev, out_dev, st); break;
+        default: sps_launch<3>(p, g, in_dev, out_dev, st); break;
     }
     HIP_TRY(hipGetLastError());
     return 0;

@@ -112,6 +112,12 @@ SIGNATURES = {
     'bbt_dmt_plan_destroy': [_vp],
     'bbt_dmt_plan_info': [_vp, _pi64, C.POINTER(_int), C.POINTER(_int), _pi64],
     'bbt_dmt_execute': [_vp, _vp, _i64, _vp, _i64, _vp],
+    'bbt_sps_standardize': [_vp, _vp, _i64, _i64, _i64, _vp],
+    'bbt_sps_plan_create': [_pvp, _i64, _i64, _i64],
+    'bbt_sps_plan_destroy': [_vp],
+    'bbt_sps_plan_info': [_vp, C.POINTER(_int), C.POINTER(_int), C.POINTER(_int), C.POINTER(_int), _pi64,
+                          C.POINTER(C.c_float)],
+    'bbt_sps_execute': [_vp, _vp, _i64, _vp, _i64, _vp],
     'bbt_fir_plan_create': [_pvp, _int, _int, _vp],
     'bbt_fir_plan_destroy': [_vp],
     'bbt_fir_execute': [_vp, _vp, _vp, _i64, _vp],
@@ -146,7 +152,7 @@ SIGNATURES = {
 }
 
 #: oldest libbbt_hip.so whose entry points and argument meanings this binding assumes
-MIN_LIB_VERSION = 163
+MIN_LIB_VERSION = 164
 
 _lib = None
 _lock = threading.Lock()
@@ -1671,6 +1677,68 @@ class DmtPlan(_Plan):
             raise ValueError("DmtPlan.execute: float32 DeviceArrays of n_in * nchan * n_rest and "
                              "n_out * ndm * n_rest values are needed")
         check(lib().bbt_dmt_execute(self._h, in_dev.ptr_to_read(), n_in, out_dev.ptr, n_out, _stream))
+
+
+#: bounds of the single-pulse search (csrc/sps_geo.hpp)
+SPS_MAX_N, SPS_MAX_WIDTHS = 65536, 13
+
+
+def sps_info(plan=None):
+    """The tiling the next call will use (BBT_SPS_WIDTH, BBT_SPS_FUSE, BBT_SPS_SPLIT, BBT_SPS_STD_ROWS),
+    the library's 13 scales c_k and, for a plan, the bytes of scratch it holds."""
+    width, fuse, split, rows, scratch = _int(0), _int(0), _int(0), _int(0), _i64(0)
+    scales = (C.c_float * SPS_MAX_WIDTHS)()
+    check(lib().bbt_sps_plan_info(plan._h if plan is not None else None, C.byref(width), C.byref(fuse),
+                                  C.byref(split), C.byref(rows), C.byref(scratch), scales))
+    return dict(width=width.value, fuse=fuse.value, split=split.value, std_rows=rows.value,
+                scratch_bytes=scratch.value, scales=np.array(scales[:], dtype=np.float32))
+
+
+def sps_standardize(x, n, n_elem, out=None):
+    """Every whole block of ``n`` samples of float32 ``x`` (samples of ``n_elem`` elements) brought to
+    zero mean and unit variance per element (bbt_sps_standardize in include/bbt_hip.h;
+    `search.standardize_samples` is the NumPy restatement).  Returns ``out``, float32 of ``(x.size //
+    n_elem // n) * n * n_elem`` values."""
+    n, n_elem = int(n), int(n_elem)
+    if x.dtype != np.float32:
+        raise TypeError(f"sps_standardize: x must be float32, not {x.dtype}")
+    if n_elem < 1 or x.size % n_elem:
+        raise ValueError(f"sps_standardize: {x.size} values are not samples of {n_elem} elements")
+    if not 2 <= n <= SPS_MAX_N:
+        raise ValueError(f"sps_standardize: n must be 2 ... {SPS_MAX_N}, not {n}")
+    n_block = x.size // n_elem // n
+    if out is None:
+        out = DeviceArray((n_block * n, n_elem), np.float32)
+    elif out.dtype != np.float32 or out.size != n_block * n * n_elem:
+        raise ValueError(f"sps_standardize: out must be a float32 DeviceArray of {n_block * n * n_elem} values")
+    check(lib().bbt_sps_standardize(x.ptr_to_read(), out.ptr, n_block, n, n_elem, _stream))
+    return out
+
+
+class SpsPlan(_Plan):
+    """best[b, :, e] = (snr, offset, level) of the best boxcar of widths 1, 2, ... 2^(n_widths - 1) that
+    starts in block ``b`` of ``n`` samples (bbt_sps_* in include/bbt_hip.h; `search.boxcar_search_samples`
+    is the NumPy restatement).  The plan owns the scratch of the partial sums."""
+    _destroy = 'bbt_sps_plan_destroy'
+
+    def __init__(self, n, n_widths, n_elem=1):
+        super().__init__()
+        self.n, self.n_widths, self.n_elem = int(n), int(n_widths), int(n_elem)
+        check(lib().bbt_sps_plan_create(C.byref(self._h), self.n, self.n_widths, self.n_elem))
+
+    def info(self):
+        """The tiling the next call will use and the bytes of scratch the plan holds (`sps_info`)."""
+        return sps_info(self)
+
+    def execute(self, in_dev, n_in, out_dev, n_blocks):
+        """``in_dev``: float32, at least ``n_in * n_elem`` values, ``n_in >= n_blocks * n``; ``out_dev``:
+        float32, at least ``n_blocks * 3 * n_elem``."""
+        n_in, n_blocks = int(n_in), int(n_blocks)
+        if (in_dev.dtype != np.float32 or out_dev.dtype != np.float32 or n_in < 0 or n_blocks < 0
+                or in_dev.size < n_in * self.n_elem or out_dev.size < n_blocks * 3 * self.n_elem):
+            raise ValueError("SpsPlan.execute: float32 DeviceArrays of n_in * n_elem and n_blocks * 3 * n_elem "
+                             "values are needed")
+        check(lib().bbt_sps_execute(self._h, in_dev.ptr_to_read(), n_in, out_dev.ptr, n_blocks, _stream))
 
 
 COMM_ID_BYTES = 128

@@ -1,11 +1,17 @@
 """Incoherent dedispersion over many trial DMs on the GPU: a detected filterbank swept along the
 dispersion curve of every trial and summed over frequency, giving the (time, DM) plane in which a
-pulse of unknown DM stands out (`DMTrials`).
+pulse of unknown DM stands out (`DMTrials`); and the single-pulse search on that plane: every
+column brought to zero mean and unit variance per block (`Standardize`), matched-filtered with
+boxcars of widths 1, 2, ... 4096 and the best S/N kept per block of start times (`BoxcarSearch`),
+the local maxima of which are the candidates (`boxcar_candidates`, on the host).
 
-The reference has no such task, so the rule is this package's, restated in NumPy here
-(`dm_trial_shifts`, `dm_trials_samples`) and computed by csrc/dmt_kernels.hpp.  The shifts are those
-of `DedisperseSamples`, to the bit; the sum is one float32 accumulator per output element, the
-channels added in ascending index."""
+The reference has no such tasks, so the rules are this package's, restated in NumPy here
+(`dm_trial_shifts`, `dm_trials_samples`, `standardize_samples`, `boxcar_search_samples`) and
+computed by csrc/dmt_kernels.hpp and csrc/sps_kernels.hpp.  The shifts are those of
+`DedisperseSamples`, to the bit; the trial sum is one float32 accumulator per output element, the
+channels added in ascending index; a boxcar sum is a fixed binary tree over its own samples."""
+import operator
+
 import numpy as np
 
 from . import hip
@@ -14,7 +20,8 @@ from .device_task import DeviceTaskMixin, fetch_device
 from .dispersion import dispersion_sample_delays, with_band
 from .dm import DispersionMeasure
 
-__all__ = ['DMTrials', 'dm_trial_shifts', 'dm_trials_samples']
+__all__ = ['DMTrials', 'dm_trial_shifts', 'dm_trials_samples', 'Standardize', 'standardize_samples',
+           'BoxcarSearch', 'boxcar_search_samples', 'boxcar_candidates', 'SNR', 'OFFSET', 'WIDTH']
 
 MAX_NCHAN, MAX_NDM = hip.DMT_MAX_NCHAN, hip.DMT_MAX_NDM
 MAX_REST, MAX_SPAN = hip.DMT_MAX_REST, hip.DMT_MAX_SPAN
@@ -221,6 +228,328 @@ class DMTrials(DeviceTaskMixin, BaseTaskBase):
             given = self._band_given[key]
             return None if given is None else f"{key}={given}".replace('\n', ',')
         return super()._repr_item(key, default, value)
+
+    def close(self):
+        super().close()
+        self._drop_cache()
+        if self._plan is not None:
+            self._plan.close()
+            self._plan = None
+
+
+# -- the single-pulse search on the plane ------------------------------------------------------------------
+#: rows of `BoxcarSearch`'s output: the best S/N of a block, its start relative to the block, its level k
+SNR, OFFSET, WIDTH = 0, 1, 2
+
+SEGMENT = 32          # samples of a segment of Standardize's two-level sums (BBT_SPS_SEG)
+MAX_N, MAX_WIDTHS = hip.SPS_MAX_N, hip.SPS_MAX_WIDTHS
+#: c_k = float32(2 ** (-k / 2)): what a sum over 2^k samples of unit variance is scaled by
+BOXCAR_SCALES = np.array([2.0 ** (-k / 2) for k in range(MAX_WIDTHS)]).astype(np.float32)
+BOXCAR_SCALES.setflags(write=False)
+
+CANDIDATE_DTYPE = np.dtype([('sample', np.int64), ('trial', np.int64), ('width', np.int64), ('snr', np.float32)])
+
+
+def _check_block(n, least):
+    n = operator.index(n)
+    if not least <= n <= MAX_N:
+        raise ValueError(f"a block must have {least} ... {MAX_N} samples, not {n}.")
+    return n
+
+
+def _check_widths(n_widths):
+    n_widths = operator.index(n_widths)
+    if not 1 <= n_widths <= MAX_WIDTHS:
+        raise ValueError(f"n_widths must be 1 ... {MAX_WIDTHS} (widths up to {1 << (MAX_WIDTHS - 1)}), not {n_widths}.")
+    return n_widths
+
+
+def _check_plane(data, who):
+    data = np.asarray(data)
+    if data.dtype != np.float32 or data.ndim < 1:
+        raise TypeError(f"{who}: samples must be float32 (N, ...), not {data.dtype} {data.shape}.")
+    return data
+
+
+def standardize_samples(data, n):
+    """NumPy restatement of the `Standardize` kernel.
+
+    ``data``: float32 ``(N,) + s``; a tail shorter than ``n`` is dropped.  Per block of ``n`` samples and
+    element, in float64 with every step rounded once: ``S1 = sum x`` and ``S2 = sum x * x`` (the product of
+    two float32 is exact) in the two-level order of `rfi.spectral_kurtosis` -- segments of 32 samples
+    summed in sample order from 0, the segment sums added in segment order from 0 -- then ::
+
+        mean = S1 / n;  q = S2 / n;  t = mean * mean;  var = q - t;  sd = sqrt(var);  r = 1 / sd
+        z[i] = (x[i] - float32(mean)) * float32(r)          (float32: one subtract, one multiply)
+
+    A block whose ``var`` is not finite or not ``> 0`` -- constant, all zero, holding a NaN or an Inf -- is
+    ``+0`` throughout.  Returns float32 ``((N // n) * n,) + s``."""
+    data, n = _check_plane(data, 'standardize_samples'), _check_block(n, 2)
+    nb = data.shape[0] // n
+    x = data[:nb * n].reshape((nb, n) + data.shape[1:])
+    s1 = np.zeros((nb,) + data.shape[1:], np.float64)
+    s2 = np.zeros_like(s1)
+    with np.errstate(all='ignore'):
+        for t0 in range(0, n, SEGMENT):
+            a1 = np.zeros_like(s1)
+            a2 = np.zeros_like(s1)
+            for t in range(t0, min(t0 + SEGMENT, n)):
+                q = x[:, t].astype(np.float64)
+                a1 = a1 + q
+                a2 = a2 + q * q
+            s1 = s1 + a1
+            s2 = s2 + a2
+        m = np.float64(n)
+        mean = s1 / m
+        q = s2 / m
+        t = mean * mean
+        var = q - t
+        sd = np.sqrt(var)
+        r = 1. / sd
+        ok = np.isfinite(var) & (var > 0.)
+        m32, r32 = mean.astype(np.float32), r.astype(np.float32)
+        z = x - m32[:, np.newaxis]
+        z = z * r32[:, np.newaxis]
+    assert z.dtype == np.float32
+    z[np.broadcast_to(~ok[:, np.newaxis], z.shape)] = 0.
+    return z.reshape((nb * n,) + data.shape[1:])
+
+
+def boxcar_search_samples(data, n, n_widths=MAX_WIDTHS):
+    """NumPy restatement of the `BoxcarSearch` kernels.
+
+    ``data``: float32 ``(N,) + s``, ``N >= n``.  With ``S_0 = x`` and, level by level, ``S_{k+1}[i] = S_k[i]
+    + S_k[i + 2^k]`` (one rounded float32 add; defined where ``i + 2^(k+1) <= N``), ``snr_k[i] = S_k[i] *
+    BOXCAR_SCALES[k]`` (one rounded multiply).  For block ``b`` of ``n`` start times the winner over all ``(k,
+    i)`` with ``k < n_widths``, ``b n <= i < (b + 1) n`` and ``i + 2^k <= N`` is the largest S/N, among equals
+    the smaller ``k``, then the smaller ``i``; a NaN never wins.  Returns float32 ``(N // n, 3) + s``: row
+    `SNR` the winner's S/N, row `OFFSET` its ``i - b n``, row `WIDTH` its ``k``; ``(-inf, 0, 0)`` where a
+    block has nothing but NaN."""
+    data = _check_plane(data, 'boxcar_search_samples')
+    n, n_widths = _check_block(n, 1), _check_widths(n_widths)
+    if data.shape[0] < n:
+        raise ValueError(f"{data.shape[0]} samples are less than one block of {n}.")
+    rest = data.shape[1:]
+    nb = data.shape[0] // n
+    best = np.full((nb,) + rest, -np.inf, np.float32)
+    offset = np.zeros((nb,) + rest, np.int64)
+    level = np.zeros((nb,) + rest, np.int64)
+    have = np.zeros((nb,) + rest, bool)
+    s = data
+    with np.errstate(all='ignore'):
+        for k in range(n_widths):
+            w = 1 << k
+            snr = s[:nb * n] * BOXCAR_SCALES[k]
+            if snr.shape[0] < nb * n:              # (start times whose window runs past the stream: absent)
+                snr = np.concatenate([snr, np.full((nb * n - snr.shape[0],) + rest, np.nan, np.float32)])
+            snr = snr.reshape((nb, n) + rest)
+            valid = ~np.isnan(snr)
+            filled = np.where(valid, snr, np.float32(-np.inf))
+            top = filled.max(axis=1)
+            first = (valid & (filled == top[:, np.newaxis])).argmax(axis=1)       # the smallest i among equals
+            value = np.take_along_axis(snr, first[:, np.newaxis], axis=1)[:, 0]
+            better = valid.any(axis=1) & (~have | (value > best))                # (not >=: the smaller k stays)
+            best = np.where(better, value, best)
+            offset = np.where(better, first, offset)
+            level = np.where(better, k, level)
+            have |= better
+            if k + 1 == n_widths or s.shape[0] <= w:
+                break
+            s = s[:-w] + s[w:]
+    out = np.empty((nb, 3) + rest, np.float32)
+    out[:, SNR], out[:, OFFSET], out[:, WIDTH] = best, offset, level
+    return out
+
+
+def boxcar_candidates(best, n, threshold):
+    """The local maxima of a `BoxcarSearch` result above a threshold (host, NumPy).
+
+    ``best``: ``(blocks, 3, ndm)`` as read from ``BoxcarSearch(plane, n, ...)``.  A cell ``(b, d)`` is a
+    candidate if its S/N is ``>= threshold``, none of its up to 8 neighbours in (block, trial) has a larger
+    S/N, and no neighbour with an equal S/N comes before it in ``(b, d)`` raster order (so a plateau yields
+    its first cell, and cells that touch only diagonally-later equals still count).  Returns a structured
+    array with fields ``sample`` (int64: ``b n + offset``, on the sample grid of the searched plane),
+    ``trial``, ``width`` (``2^k``) and ``snr``, sorted by descending ``snr``, then ``sample``, then ``trial``.
+    Nothing is merged across widths or trials."""
+    best = np.asarray(best)
+    n = _check_block(n, 1)
+    if best.ndim != 3 or best.shape[1] != 3:
+        raise ValueError(f"best must be (blocks, 3, ndm) as BoxcarSearch makes it, not {best.shape}.")
+    snr = best[:, SNR].astype(np.float32)
+    nb, nd = snr.shape
+    padded = np.full((nb + 2, nd + 2), np.nan, np.float32)             # (a NaN compares False: no neighbour)
+    padded[1:-1, 1:-1] = snr
+    with np.errstate(invalid='ignore'):
+        keep = snr >= np.float32(threshold)
+        for db in (-1, 0, 1):
+            for dd in (-1, 0, 1):
+                if db == 0 and dd == 0:
+                    continue
+                other = padded[1 + db:1 + db + nb, 1 + dd:1 + dd + nd]
+                keep &= ~(other > snr)
+                if (db, dd) < (0, 0):
+                    keep &= ~(other == snr)
+    b, d = np.nonzero(keep)
+    out = np.empty(b.shape[0], CANDIDATE_DTYPE)
+    out['sample'] = b * n + best[b, OFFSET, d].astype(np.int64)
+    out['trial'] = d
+    out['width'] = np.int64(1) << best[b, WIDTH, d].astype(np.int64)
+    out['snr'] = snr[b, d]
+    return out[np.lexsort((out['trial'], out['sample'], -out['snr'].astype(np.float64)))]
+
+
+def _check_plane_stream(ih, who):
+    in_dtype = np.dtype(ih.dtype)
+    if in_dtype.kind == 'c':
+        raise TypeError(f"{who} works on detected power; make a complex stream float32 with Square or Power first.")
+    if in_dtype != np.dtype(np.float32):
+        raise TypeError(f"{who} handles float32 streams; got {in_dtype}.")
+
+
+def _lone_frequency(ih):
+    """Does ``ih`` have a frequency but no sideband, as the plane of `DMTrials` has?  The base classes
+    take the two together; a task that passes such metadata on hands them a placeholder sideband and
+    takes it out again."""
+    return getattr(ih, 'frequency', None) is not None and getattr(ih, 'sideband', None) is None
+
+
+class Standardize(DeviceTaskMixin, BaseTaskBase):
+    """Bring every block of ``n`` samples to zero mean and unit variance, per element of a sample.
+
+    Parameters
+    ----------
+    ih : stream
+        float32, any sample shape -- usually the (time, DM) plane of `DMTrials`.
+    n : int
+        Samples of a block, 2 ... 65536, counted from sample 0 of ``ih``; a tail shorter than ``n`` is
+        dropped.
+    samples_per_frame : int, optional
+        A multiple of ``n``.  Default: the smallest one that is at least ``ih.samples_per_frame``, at
+        most the length of the output.
+
+    Sample rate, start time and metadata are those of ``ih``; the length is ``(len // n) * n``.  The
+    statistics are the plain mean and variance of the block, summed in float64 in a fixed order, and
+    the values equal `standardize_samples` bit for bit.  A block that is constant, all zero (what
+    `Excise` leaves) or holds a NaN or an Inf comes out as +0.  There is no median / MAD, no running
+    baseline, and a pulse's own power is not clipped from the estimate: a bright pulse in a short
+    block lowers its own S/N.  Choose blocks much longer than the widest boxcar."""
+
+    #: input bytes fetched at most per `fetch_device` call and launch (assignable); a chunk is a
+    #: whole number of blocks
+    standardize_budget = 1 << 29
+
+    def __init__(self, ih, n, *, samples_per_frame=None):
+        _check_plane_stream(ih, 'Standardize')
+        self.n = n = _check_block(n, 2)
+        if ih.shape[0] < n:
+            raise ValueError(f"the stream has {ih.shape[0]} samples: less than one block of {n}.")
+        self._n_elem = _prod(ih.shape[1:])
+        length = ih.shape[0] // n * n
+        if samples_per_frame is None:
+            samples_per_frame = min(-(-operator.index(ih.samples_per_frame) // n) * n, length)
+        samples_per_frame = operator.index(samples_per_frame)
+        if samples_per_frame < n or samples_per_frame % n:
+            raise ValueError(f"samples_per_frame must be a multiple of the block, {n}; got {samples_per_frame}.")
+        lone = _lone_frequency(ih)
+        super().__init__(ih, shape=(length,) + tuple(ih.shape[1:]), samples_per_frame=samples_per_frame,
+                         dtype=np.float32, **(dict(sideband=1) if lone else {}))
+        if lone:
+            del self.meta['__attributes__']['sideband']
+
+    def _chunk_samples(self):
+        block_bytes = self.n * self._n_elem * 4
+        return max(1, int(self.standardize_budget) // block_bytes) * self.n
+
+    def _input_span(self, first, last):
+        a, b = self._frame_span(first, last)
+        return (self.ih, a, b - a) if b - a <= self._chunk_samples() else None      # (one fetch only)
+
+    def _compute_frames(self, first, last, out):
+        a, b = self._frame_span(first, last)          # (frames and the stream are whole blocks)
+        per = self._chunk_samples()
+        for c0 in range(a, b, per):
+            c1 = min(b, c0 + per)
+            x = fetch_device(self.ih, c0, c1 - c0)
+            hip.sps_standardize(x, self.n, self._n_elem, out=out[c0 - a:c1 - a])
+
+    def _repr_item(self, key, default, value=None):
+        if key == 'samples_per_frame' and default is None:
+            default = min(-(-self._ih_samples_per_frame // self.n) * self.n, self.shape[0])
+        return super()._repr_item(key, default, value)
+
+
+class BoxcarSearch(DeviceTaskMixin, BaseTaskBase):
+    """The best boxcar S/N in every block of ``n`` start times, per element of a sample: a pulse of
+    unknown width is matched-filtered with boxcars of widths 1, 2, 4, ... and the best one kept.
+
+    Parameters
+    ----------
+    ih : stream
+        float32, any sample shape, of zero mean and unit variance -- usually
+        ``Standardize(DMTrials(...), m)``.
+    n : int
+        Start times folded into one output sample, 1 ... 65536, counted from sample 0 of ``ih``; the
+        stream must hold one block at least.
+    n_widths : int, optional
+        ``K``, 1 ... 13: widths ``2^k`` for ``k < K``, up to 4096.  Default 13.
+    samples_per_frame : int, optional
+        Of the output (blocks).  Default 1.
+
+    The output is float32 ``(len // n, 3) + sample_shape`` at ``sample_rate / n`` from ``ih``'s start
+    time: for block ``b`` row `SNR` is the largest ``snr_k[i] = S_k[i] * float32(2^(-k/2))`` over all
+    widths and all start times ``b n <= i < (b + 1) n`` whose window fits the stream (``i + 2^k <= len``; it may
+    run into later blocks and into the dropped tail), row `OFFSET` is ``i - b n`` and row `WIDTH` is ``k`` of
+    that winner, as floats.  Among equal S/N the smaller ``k`` wins, then the smaller ``i``; a NaN never
+    wins; a block of nothing else gives ``(-inf, 0, 0)``.  ``S_k[i]`` is the sum of ``ih[i] ... ih[i + 2^k -
+    1]`` added up as a fixed binary tree (``S_{k+1}[i] = S_k[i] + S_k[i + 2^k]``, one rounded float32 add),
+    so values equal `boxcar_search_samples` bit for bit whatever the tiling or the chunking.  Metadata are
+    those of ``ih``, broadcast over the new axis.  `boxcar_candidates` turns a read of this task into a
+    candidate list.  Nothing leaves HBM: the levels are made pass by pass through a scratch the plan owns,
+    the running winner living in the output."""
+
+    #: bytes of input, partial sums (twice the input at most) and output per `fetch_device` call and
+    #: launch (assignable)
+    sps_budget = 1 << 29
+
+    def __init__(self, ih, n, n_widths=MAX_WIDTHS, *, samples_per_frame=1):
+        _check_plane_stream(ih, 'BoxcarSearch')
+        self.n = n = _check_block(n, 1)
+        self.n_widths = _check_widths(n_widths)
+        if ih.shape[0] < n:
+            raise ValueError(f"the stream has {ih.shape[0]} samples: less than one block of {n}.")
+        self._n_elem = _prod(ih.shape[1:])
+        self._halo = (1 << (self.n_widths - 1)) - 1
+        self._plan = None
+        lone = _lone_frequency(ih)
+        super().__init__(ih, shape=(ih.shape[0] // n, 3) + tuple(ih.shape[1:]), sample_rate=_stream_rate(ih) / n,
+                         samples_per_frame=samples_per_frame, dtype=np.float32,
+                         **(dict(sideband=1) if lone else {}))
+        if lone:
+            del self.meta['__attributes__']['sideband']
+
+    def _chunk_blocks(self):
+        row = self._n_elem * 4
+        return max(1, (int(self.sps_budget) - 3 * self._halo * row) // (3 * self.n * row + 3 * row))
+
+    def _chunk_input(self, b0, b1):
+        """The input samples blocks [b0, b1) need: (first, count)."""
+        start = b0 * self.n
+        return start, min(self.ih.shape[0], b1 * self.n + self._halo) - start
+
+    def _input_span(self, first, last):
+        a, b = self._frame_span(first, last)
+        return (self.ih,) + self._chunk_input(a, b) if b - a <= self._chunk_blocks() else None    # (one fetch only)
+
+    def _compute_frames(self, first, last, out):
+        if self._plan is None:
+            self._plan = hip.SpsPlan(self.n, self.n_widths, self._n_elem)
+        a, b = self._frame_span(first, last)
+        per = self._chunk_blocks()
+        for c0 in range(a, b, per):
+            c1 = min(b, c0 + per)
+            start, n_in = self._chunk_input(c0, c1)
+            x = fetch_device(self.ih, start, n_in)
+            self._plan.execute(x, n_in, out[c0 - a:c1 - a], c1 - c0)
 
     def close(self):
         super().close()

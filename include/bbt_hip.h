@@ -47,6 +47,7 @@ typedef struct bbt_chan_plan bbt_chan_plan;
 typedef struct bbt_pfb_plan bbt_pfb_plan;
 typedef struct bbt_shift_plan bbt_shift_plan;
 typedef struct bbt_dmt_plan bbt_dmt_plan;
+typedef struct bbt_sps_plan bbt_sps_plan;
 typedef struct bbt_fir_plan bbt_fir_plan;
 typedef struct bbt_r2c_plan bbt_r2c_plan;
 typedef struct bbt_gather_plan bbt_gather_plan;
@@ -554,6 +555,40 @@ int bbt_dmt_plan_destroy(bbt_dmt_plan* plan);
 int bbt_dmt_plan_info(const bbt_dmt_plan* plan, int64_t* span, int* tile_t, int* trials,
                       int64_t* scratch_bytes);
 int bbt_dmt_execute(bbt_dmt_plan* plan, const float* in_dev, int64_t n_in, float* out_dev, int64_t n_out,
+                    bbt_stream stream);
+
+/* ---- single-pulse search on the (time, DM) plane: Standardize, BoxcarSearch -----
+ * A chunk is x[t][e], float32, element fastest; every e is an independent column.
+ *
+ * bbt_sps_standardize: per block b < n_block of n samples (2 ... 65536) and element, in float64 with
+ * every step rounded once: S1 = sum x and S2 = sum x * x in the two-level order of bbt_sk_estimate
+ * (segments of 32 samples summed in sample order, the segment sums added in segment order), mean = S1 /
+ * n, q = S2 / n, t = mean * mean, var = q - t, sd = sqrt(var), r = 1 / sd; then in float32 out = (x -
+ * (float)mean) * (float)r, one rounded subtract and one rounded multiply.  A block whose var is not
+ * finite or not > 0 comes out as +0.  out may not overlap x.
+ *
+ * bbt_sps_execute: S_0 = x, S_{k+1}[i] = S_k[i] + S_k[i + 2^k] (one rounded float32 add), snr_k[i] =
+ * S_k[i] * c_k with c_k = float32(2^(-k/2)), k < n_widths <= 13.  For block b < n_blocks of n start
+ * times (1 ... 65536) the winner over all (k, i), b n <= i < (b + 1) n, i + 2^k <= n_in, is written as
+ * out[b][0][e] = its snr, out[b][1][e] = (float)(i - b n), out[b][2][e] = (float)k: the largest snr,
+ * then the smaller k, then the smaller i; a NaN never wins, and a block with nothing else gives (-inf,
+ * 0, 0).  A window sum is a fixed binary tree over its own samples and the winner is the maximum of a
+ * total order, so results do not depend on the launch or the tiling (BBT_SPS_WIDTH = 16, 32 or 64
+ * elements per workgroup, BBT_SPS_FUSE = 1, 2 or 3 levels per pass, BBT_SPS_SPLIT = 1 ... 16 threads per
+ * block and element, BBT_SPS_STD_ROWS = 1 ... 16 for standardize, read from the environment at every
+ * call, only change the speed).  n_in >= n_blocks * n; samples beyond n_blocks * n + 2^(n_widths - 1) - 1
+ * are not read.  The plan owns a scratch of up to twice the chunk's size for the partial sums, which
+ * grows to the largest chunk it has seen; it serves one stream at a time.  plan_info takes a null plan
+ * (the tiling and the 13 scales only).
+ * Every refusal -- a null pointer, n or n_widths out of range, no blocks, a short input -- comes before
+ * anything is launched.  Asynchronous on `stream`. */
+int bbt_sps_standardize(const float* x_dev, float* out_dev, int64_t n_block, int64_t n, int64_t n_elem,
+                        bbt_stream stream);
+int bbt_sps_plan_create(bbt_sps_plan** plan, int64_t n, int64_t n_widths, int64_t n_elem);
+int bbt_sps_plan_destroy(bbt_sps_plan* plan);
+int bbt_sps_plan_info(const bbt_sps_plan* plan, int* width, int* fuse, int* split, int* std_rows,
+                      int64_t* scratch_bytes, float* scales);
+int bbt_sps_execute(bbt_sps_plan* plan, const float* in_dev, int64_t n_in, float* out_dev, int64_t n_blocks,
                     bbt_stream stream);
 
 /* ---- real-valued streams ------------------------------------------------------
