@@ -26,6 +26,9 @@ from .rfi import SpectralKurtosis, Excise, sk_limits, spectral_kurtosis, excise_
 from .search import (DMTrials, dm_trial_shifts, dm_trials_samples, Standardize, standardize_samples,
                      BoxcarSearch, boxcar_search_samples, boxcar_candidates)
 from . import search
+from .periodicity import (fluctuation_spectra, Whiten, whiten_samples, HarmonicSearch, harmonic_search_samples,
+                          harmonic_scales, harmonic_candidates)
+from . import periodicity
 from .conversion import Real2Complex
 from .shaping import (ChangeSampleShapeBase, ChangeSampleShape, Reshape, Transpose, ReshapeAndTranspose,
                       GetItem, GetSlice)

@@ -35,6 +35,7 @@
 #include "sk_kernels.hpp"
 #include "dmt_kernels.hpp"
 #include "sps_kernels.hpp"
+#include "hsum_kernels.hpp"
 #include "r2c_kernels.hpp"
 #include "gather_kernels.hpp"
 #include "pack_kernels.hpp"
@@ -44,7 +45,7 @@
 
 using namespace bbt;
 
-#define BBT_VERSION 164
+#define BBT_VERSION 165
 
 // ---------------------------------------------------------------------------
 // errors
@@ -3833,6 +3834,95 @@ extern "C" int bbt_sps_execute(bbt_sps_plan* p, const float* in_dev, int64_t n_i
         case 1: sps_launch<1>(p, g, in_dev, out_dev, st); break;
         case 2: sps_launch<2>(p, g, in_dev, out_dev, st); break;
         default: sps_launch<3>(p, g, in_dev, out_dev, st); break;
+    }
+    HIP_TRY(hipGetLastError());
+    return 0;
+}
+
+// ---------------------------------------------------------------------------
+// periodicity search on stacked fluctuation spectra (hsum_kernels.hpp; the tiling is hsum_geo.hpp's)
+struct bbt_hsum_plan {
+    long long nbin = 0, n = 0, lo = 0, n_elem = 0;
+    int K = 0;
+    float c[BBT_HSUM_MAX_LEVELS] = {};
+};
+
+// BBT_HSUM_WIDTH: elements of a search workgroup (16, 32, 64); BBT_HSUM_SPLIT: threads that share a
+// (spectrum, block, element) at most (1, 2, 4, 8, 16); BBT_HSUM_ROWS: threads along the segments in Whiten
+// (1, 2, 4, 8, 16).  Read at every call, for measuring and for the tests that walk the tilings; no value
+// of the output depends on any.  Anything else leaves the default.
+static int hsum_env_width() { return dmt_env("BBT_HSUM_WIDTH", {16, 32, 64}); }
+static int hsum_env_split() { return dmt_env("BBT_HSUM_SPLIT", {1, 2, 4, 8, 16}); }
+static int hsum_env_rows() { return dmt_env("BBT_HSUM_ROWS", {1, 2, 4, 8, 16}); }
+
+// out[s][j][e] = x[s][j][e] * (1 / mean of the block of m bins that holds j), +0 for j < skip
+extern "C" int bbt_hsum_whiten(const float* x_dev, float* out_dev, int64_t n_spec, int64_t nbin, int64_t n_elem,
+                               int64_t m, int64_t skip, bbt_stream stream) {
+    ARG_TRY(x_dev && out_dev, "bbt_hsum_whiten: null argument");
+    ARG_TRY((((uintptr_t)x_dev | (uintptr_t)out_dev) & 3) == 0, "bbt_hsum_whiten: arrays must be 4-byte aligned");
+    WhitenGeo g = {};
+    const char* err = hsum_whiten_geo(n_spec, nbin, n_elem, m, skip, hsum_env_rows(), &g);
+    ARG_TRY(!err, "bbt_hsum_whiten: %s (n_spec=%lld, nbin=%lld, n_elem=%lld, m=%lld, skip=%lld)", err ? err : "",
+            (long long)n_spec, (long long)nbin, (long long)n_elem, (long long)m, (long long)skip);
+    hipLaunchKernelGGL(k_hsum_whiten, dim3((unsigned)g.n_wg), dim3(BBT_HSUM_THREADS), 0, (hipStream_t)stream, x_dev,
+                       out_dev, g);
+    HIP_TRY(hipGetLastError());
+    return 0;
+}
+
+extern "C" int bbt_hsum_plan_destroy(bbt_hsum_plan* p) {
+    delete p;
+    return 0;
+}
+
+// scales_host: n_levels floats, c_L = float32(sqrt(averaged / 2^L)) as the caller rounded them
+extern "C" int bbt_hsum_plan_create(bbt_hsum_plan** plan, int64_t nbin, int64_t n, int64_t n_levels, int64_t lo,
+                                    int64_t n_elem, const float* scales_host) {
+    ARG_TRY(plan && scales_host, "bbt_hsum_plan_create: null argument");
+    *plan = nullptr;
+    const char* err = hsum_sizes(nbin, n, n_levels, lo, n_elem);
+    ARG_TRY(!err, "bbt_hsum_plan_create: %s", err ? err : "");
+    for (int L = 0; L < (int)n_levels; ++L)
+        ARG_TRY(scales_host[L] > 0.f && scales_host[L] < __builtin_inff(),
+                "bbt_hsum_plan_create: the scales must be finite and > 0");
+    bbt_hsum_plan* p = new bbt_hsum_plan;
+    p->nbin = nbin, p->n = n, p->K = (int)n_levels, p->lo = lo, p->n_elem = n_elem;
+    for (int L = 0; L < p->K; ++L) p->c[L] = scales_host[L];
+    *plan = p;
+    return 0;
+}
+
+// the tiling the next call will use (plan may be null: the tiling only); scales: 6 floats, the plan's c_L
+// (0 beyond its levels, and for a null plan)
+extern "C" int bbt_hsum_plan_info(const bbt_hsum_plan* p, int* width, int* split, int* rows, float* scales) {
+    const int w = hsum_env_width(), s = hsum_env_split(), r = hsum_env_rows();
+    if (width) *width = w ? w : BBT_HSUM_WIDTH;
+    if (split) *split = s ? s : BBT_HSUM_SPLIT;
+    if (rows) *rows = r ? r : BBT_HSUM_ROWS;
+    if (scales)
+        for (int L = 0; L < BBT_HSUM_MAX_LEVELS; ++L) scales[L] = p ? p->c[L] : 0.f;
+    return 0;
+}
+
+// best[s][b][3][e], s < n_spec, b < ceil(nbin / n), from in[s][j][e], j < nbin
+extern "C" int bbt_hsum_execute(bbt_hsum_plan* p, const float* in_dev, int64_t n_spec, float* out_dev,
+                                bbt_stream stream) {
+    ARG_TRY(p && in_dev && out_dev, "bbt_hsum_execute: null argument");
+    ARG_TRY((((uintptr_t)in_dev | (uintptr_t)out_dev) & 3) == 0, "bbt_hsum_execute: arrays must be 4-byte aligned");
+    HsumGeo g = {};
+    const char* err = hsum_geo(n_spec, p->nbin, p->n, p->K, p->lo, p->n_elem, hsum_env_width(), hsum_env_split(), &g);
+    ARG_TRY(!err, "bbt_hsum_execute: %s (n_spec=%lld, nbin=%lld, n=%lld)", err ? err : "", (long long)n_spec, p->nbin,
+            p->n);
+    for (int L = 0; L < BBT_HSUM_MAX_LEVELS; ++L) g.c[L] = p->c[L];
+    const dim3 grid((unsigned)g.n_wg), block(BBT_HSUM_THREADS);
+    hipStream_t st = (hipStream_t)stream;
+    switch (g.K) {
+        case 1: hipLaunchKernelGGL((k_hsum_search<1>), grid, block, 0, st, in_dev, out_dev, g); break;
+        case 2: hipLaunchKernelGGL((k_hsum_search<2>), grid, block, 0, st, in_dev, out_dev, g); break;
+        case 3: hipLaunchKernelGGL((k_hsum_search<3>), grid, block, 0, st, in_dev, out_dev, g); break;
+        case 4: hipLaunchKernelGGL((k_hsum_search<4>), grid, block, 0, st, in_dev, out_dev, g); break;
+        case 5: hipLaunchKernelGGL((k_hsum_search<5>), grid, block, 0, st, in_dev, out_dev, g); break;
+        default: hipLaunchKernelGGL((k_hsum_search<6>), grid, block, 0, st, in_dev, out_dev, g); break;
     }
     HIP_TRY(hipGetLastError());
     return 0;

@@ -118,6 +118,11 @@ SIGNATURES = {
     'bbt_sps_plan_info': [_vp, C.POINTER(_int), C.POINTER(_int), C.POINTER(_int), C.POINTER(_int), _pi64,
                           C.POINTER(C.c_float)],
     'bbt_sps_execute': [_vp, _vp, _i64, _vp, _i64, _vp],
+    'bbt_hsum_whiten': [_vp, _vp, _i64, _i64, _i64, _i64, _i64, _vp],
+    'bbt_hsum_plan_create': [_pvp, _i64, _i64, _i64, _i64, _i64, C.POINTER(C.c_float)],
+    'bbt_hsum_plan_destroy': [_vp],
+    'bbt_hsum_plan_info': [_vp, C.POINTER(_int), C.POINTER(_int), C.POINTER(_int), C.POINTER(C.c_float)],
+    'bbt_hsum_execute': [_vp, _vp, _i64, _vp, _vp],
     'bbt_fir_plan_create': [_pvp, _int, _int, _vp],
     'bbt_fir_plan_destroy': [_vp],
     'bbt_fir_execute': [_vp, _vp, _vp, _i64, _vp],
@@ -152,7 +157,7 @@ SIGNATURES = {
 }
 
 #: oldest libbbt_hip.so whose entry points and argument meanings this binding assumes
-MIN_LIB_VERSION = 164
+MIN_LIB_VERSION = 165
 
 _lib = None
 _lock = threading.Lock()
@@ -1739,6 +1744,77 @@ class SpsPlan(_Plan):
             raise ValueError("SpsPlan.execute: float32 DeviceArrays of n_in * n_elem and n_blocks * 3 * n_elem "
                              "values are needed")
         check(lib().bbt_sps_execute(self._h, in_dev.ptr_to_read(), n_in, out_dev.ptr, n_blocks, _stream))
+
+
+#: bounds of the periodicity search (csrc/hsum_geo.hpp)
+HSUM_MIN_M, HSUM_MAX_M, HSUM_MAX_N, HSUM_MAX_LEVELS, HSUM_MAX_NBIN = 2, 65536, 65536, 6, 1 << 24
+
+
+def hsum_info(plan=None):
+    """The tiling the next call will use (BBT_HSUM_WIDTH, BBT_HSUM_SPLIT, BBT_HSUM_ROWS) and, for a
+    plan, the 6 scales c_L it holds (0 beyond its levels)."""
+    width, split, rows = _int(0), _int(0), _int(0)
+    scales = (C.c_float * HSUM_MAX_LEVELS)()
+    check(lib().bbt_hsum_plan_info(plan._h if plan is not None else None, C.byref(width), C.byref(split),
+                                   C.byref(rows), scales))
+    return dict(width=width.value, split=split.value, rows=rows.value,
+                scales=np.array(scales[:], dtype=np.float32))
+
+
+def hsum_whiten(x, nbin, n_elem, m, skip=1, out=None):
+    """Every block of ``m`` bins, counted from bin ``skip``, of every spectrum of float32 ``x`` (spectra of
+    ``nbin`` bins of ``n_elem`` elements) divided by its own mean, the bins below ``skip`` +0
+    (bbt_hsum_whiten in include/bbt_hip.h; `periodicity.whiten_samples` is the NumPy restatement).
+    Returns ``out``, float32 of the size of ``x``."""
+    nbin, n_elem, m, skip = int(nbin), int(n_elem), int(m), int(skip)
+    if x.dtype != np.float32:
+        raise TypeError(f"hsum_whiten: x must be float32, not {x.dtype}")
+    if n_elem < 1 or nbin < 1 or x.size % (nbin * n_elem) or x.size == 0:
+        raise ValueError(f"hsum_whiten: {x.size} values are not spectra of {nbin} bins of {n_elem} elements")
+    if not HSUM_MIN_M <= m <= HSUM_MAX_M:
+        raise ValueError(f"hsum_whiten: m must be {HSUM_MIN_M} ... {HSUM_MAX_M}, not {m}")
+    if not 0 <= skip < nbin:
+        raise ValueError(f"hsum_whiten: skip must be 0 ... {nbin - 1}, not {skip}")
+    n_spec = x.size // (nbin * n_elem)
+    if out is None:
+        out = DeviceArray((n_spec, nbin, n_elem), np.float32)
+    elif out.dtype != np.float32 or out.size != x.size:
+        raise ValueError(f"hsum_whiten: out must be a float32 DeviceArray of {x.size} values")
+    check(lib().bbt_hsum_whiten(x.ptr_to_read(), out.ptr, n_spec, nbin, n_elem, m, skip, _stream))
+    return out
+
+
+class HsumPlan(_Plan):
+    """best[s, b, :, e] = (snr, offset, level) of the best sum of 1, 2, ... 2^(n_levels - 1) harmonics whose
+    top harmonic lies in block ``b`` of ``n`` bins of spectrum ``s`` (bbt_hsum_* in include/bbt_hip.h;
+    `periodicity.harmonic_search_samples` is the NumPy restatement).  ``scales``: the ``n_levels`` float32
+    ``c_L`` the S/N is formed with."""
+    _destroy = 'bbt_hsum_plan_destroy'
+
+    def __init__(self, nbin, n, n_levels, lo, n_elem, scales):
+        super().__init__()
+        self.nbin, self.n, self.n_levels, self.lo, self.n_elem = int(nbin), int(n), int(n_levels), int(lo), int(n_elem)
+        scales = np.ascontiguousarray(scales, dtype=np.float32).ravel()
+        if scales.shape[0] < min(max(self.n_levels, 0), HSUM_MAX_LEVELS):
+            raise ValueError(f"HsumPlan: {self.n_levels} levels need as many scales, not {scales.shape[0]}")
+        self.n_blocks = -(-self.nbin // self.n) if self.n > 0 else 0
+        check(lib().bbt_hsum_plan_create(C.byref(self._h), self.nbin, self.n, self.n_levels, self.lo, self.n_elem,
+                                         scales.ctypes.data_as(C.POINTER(C.c_float))))
+
+    def info(self):
+        """The tiling the next call will use and the plan's scales (`hsum_info`)."""
+        return hsum_info(self)
+
+    def execute(self, in_dev, n_spec, out_dev):
+        """``in_dev``: float32, at least ``n_spec * nbin * n_elem`` values; ``out_dev``: float32, at least
+        ``n_spec * n_blocks * 3 * n_elem``."""
+        n_spec = int(n_spec)
+        if (in_dev.dtype != np.float32 or out_dev.dtype != np.float32 or n_spec < 0
+                or in_dev.size < n_spec * self.nbin * self.n_elem
+                or out_dev.size < n_spec * self.n_blocks * 3 * self.n_elem):
+            raise ValueError("HsumPlan.execute: float32 DeviceArrays of n_spec * nbin * n_elem and n_spec * "
+                             "n_blocks * 3 * n_elem values are needed")
+        check(lib().bbt_hsum_execute(self._h, in_dev.ptr_to_read(), n_spec, out_dev.ptr, _stream))
 
 
 COMM_ID_BYTES = 128

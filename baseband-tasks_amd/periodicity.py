@@ -1,0 +1,403 @@
+"""Periodicity search on the (time, DM) plane: the fluctuation spectrum of every trial, made in
+stacks of short transforms by tasks the package has already (`fluctuation_spectra`), whitened block
+by block (`Whiten`), the sums of 1, 2, 4, ... 32 harmonics formed and the best S/N kept per block of
+frequency bins (`HarmonicSearch`), the local maxima of which are the candidates
+(`harmonic_candidates`, on the host).
+
+The reference has no such tasks, so the rules are this package's, restated in NumPy here
+(`whiten_samples`, `harmonic_search_samples`) and computed by csrc/hsum_kernels.hpp.  A block's mean
+is one float64 sum in a fixed two-level order; a harmonic sum is ONE float32 accumulator per top
+harmonic, the gathered bins added in a fixed order; the winner of a block is the maximum of a total
+order.  So every value has one correct bit pattern, whatever the tiling or the chunking."""
+import operator
+
+import numpy as np
+
+from . import hip
+from .base import META_ATTRIBUTES, BaseTaskBase, SetAttribute, _stream_rate, check_broadcast_to, simplify_shape
+from .channelize import Channelize
+from .device_task import DeviceTaskMixin, fetch_device
+from .functions import Square
+from .integration import Integrate
+from .search import _check_plane_stream, _local_maxima, _lone_frequency, _prod
+
+__all__ = ['fluctuation_spectra', 'Whiten', 'whiten_samples', 'HarmonicSearch', 'harmonic_search_samples',
+           'harmonic_scales', 'harmonic_candidates', 'SNR', 'OFFSET', 'LEVEL']
+
+#: rows of `HarmonicSearch`'s output: the best S/N of a block, its top harmonic's bin relative to the
+#: block, its level L (2^L harmonics)
+SNR, OFFSET, LEVEL = 0, 1, 2
+
+SEGMENT = 32          # bins of a segment of Whiten's two-level sums (BBT_HSUM_SEG)
+MIN_M, MAX_M = hip.HSUM_MIN_M, hip.HSUM_MAX_M
+MAX_N, MAX_LEVELS, MAX_NBIN = hip.HSUM_MAX_N, hip.HSUM_MAX_LEVELS, hip.HSUM_MAX_NBIN
+
+
+# -- the spectra ----------------------------------------------------------------------------------------
+def fluctuation_spectra(plane, n, stack=1):
+    """Stacked power spectra of every column of a float32 stream: ``Integrate(Square(Channelize(plane,
+    n)), stack)``, nothing else -- the transform of a real stream is an ``rfft`` per element, so the
+    result is float32 ``(nspec, n // 2 + 1) + plane.sample_shape`` at ``plane.sample_rate / (n * stack)``,
+    every value the average of ``stack`` consecutive power spectra of ``n`` samples, and it never leaves
+    the device.
+
+    ``plane`` is usually the (time, DM) plane of `DMTrials`, which has a frequency and no sideband; such
+    a stream is relabelled with ``sideband=1`` first, as the base classes take the two together.  ``n``
+    is what `Channelize` takes: up to 16384.  Bin ``j`` is fluctuation frequency ``j * bin_width`` with
+    ``bin_width = plane.sample_rate / n`` in Hz, an attribute of the task returned.  The ``frequency``
+    `Channelize` attaches to the bins -- the plane's own plus the bin's -- is meaningless here:
+    `HarmonicSearch` drops it."""
+    if np.dtype(plane.dtype) != np.dtype(np.float32):
+        raise TypeError(f"fluctuation_spectra works on a float32 stream; got {plane.dtype}.")
+    n, stack = operator.index(n), operator.index(stack)
+    if stack < 1:
+        raise ValueError(f"stack must be at least 1, not {stack}.")
+    if _lone_frequency(plane):
+        plane = SetAttribute(plane, frequency=plane.frequency, sideband=1)
+    spectra = Integrate(Square(Channelize(plane, n)), stack)
+    spectra.bin_width = _stream_rate(plane) / n
+    return spectra
+
+
+# -- the NumPy twins ------------------------------------------------------------------------------------
+def _check_spectra(data, who):
+    data = np.asarray(data)
+    if data.dtype != np.float32 or data.ndim < 2:
+        raise TypeError(f"{who}: spectra must be float32 (N, nbin, ...), not {data.dtype} {data.shape}.")
+    return data
+
+
+def _check_m(m):
+    m = operator.index(m)
+    if not MIN_M <= m <= MAX_M:
+        raise ValueError(f"a whitening block must have {MIN_M} ... {MAX_M} bins, not {m}.")
+    return m
+
+
+def _check_skip(skip, nbin, what='skip'):
+    skip = operator.index(skip)
+    if not 0 <= skip < nbin:
+        raise ValueError(f"{what} must be 0 ... {nbin - 1} for spectra of {nbin} bins, not {skip}.")
+    return skip
+
+
+def _whiten_blocks(x):
+    """``x``: float32 ``(N, blocks, len) + s``, every ``x[:, b]`` one block."""
+    ln = x.shape[2]
+    s1 = np.zeros(x.shape[:2] + x.shape[3:], np.float64)
+    with np.errstate(all='ignore'):
+        for t0 in range(0, ln, SEGMENT):
+            a = np.zeros_like(s1)
+            for t in range(t0, min(t0 + SEGMENT, ln)):
+                a = a + x[:, :, t].astype(np.float64)
+            s1 = s1 + a
+        mean = s1 / np.float64(ln)
+        r = 1. / mean
+        r32 = r.astype(np.float32)
+        ok = np.isfinite(mean) & (mean > 0.) & np.isfinite(r32)
+        z = x * r32[:, :, np.newaxis]
+    assert z.dtype == np.float32
+    z[np.broadcast_to(~ok[:, :, np.newaxis], z.shape)] = 0.
+    return z
+
+
+def whiten_samples(data, m, skip=1):
+    """NumPy restatement of the `Whiten` kernel.
+
+    ``data``: float32 ``(N, nbin) + s``.  Bins below ``skip`` come out ``+0``; from ``skip`` on the bins are
+    cut into blocks of ``m``, the last one whatever is left.  Per spectrum, block and element, in float64
+    with every step rounded once: ``S1 = sum x`` in the two-level order of `search.standardize_samples`
+    -- segments of 32 bins summed in bin order from the block's first bin, the segment sums added in
+    segment order -- then ::
+
+        mean = S1 / len;  r = 1 / mean;  z = x * float32(r)          (float32: one multiply)
+
+    A block whose ``mean`` is not finite or not ``> 0``, or whose ``float32(r)`` is not finite -- all zero,
+    holding a NaN or an Inf, of negative mean, of a denormal mean -- is ``+0`` throughout."""
+    data, m = _check_spectra(data, 'whiten_samples'), _check_m(m)
+    nbin = data.shape[1]
+    skip = _check_skip(skip, nbin)
+    out = np.zeros(data.shape, np.float32)
+    n_full = (nbin - skip) // m
+    if n_full:
+        x = data[:, skip:skip + n_full * m].reshape((data.shape[0], n_full, m) + data.shape[2:])
+        out[:, skip:skip + n_full * m] = _whiten_blocks(x).reshape((data.shape[0], n_full * m) + data.shape[2:])
+    if skip + n_full * m < nbin:
+        out[:, skip + n_full * m:] = _whiten_blocks(data[:, np.newaxis, skip + n_full * m:])[:, 0]
+    return out
+
+
+def _check_search(n, n_levels):
+    n, n_levels = operator.index(n), operator.index(n_levels)
+    if not 1 <= n <= MAX_N:
+        raise ValueError(f"a search block must have 1 ... {MAX_N} bins, not {n}.")
+    if not 1 <= n_levels <= MAX_LEVELS:
+        raise ValueError(f"n_levels must be 1 ... {MAX_LEVELS} (up to {1 << (MAX_LEVELS - 1)} harmonics), not "
+                         f"{n_levels}.")
+    return n, n_levels
+
+
+def harmonic_scales(averaged=1.):
+    """``c_L = float32(sqrt(averaged / 2^L))`` for ``L < 6``: the square root in float64, rounded once.
+    The sum of ``2^L`` values that are each the average of ``averaged`` exponential powers of unit mean
+    has mean ``2^L`` and standard deviation ``sqrt(2^L / averaged)``."""
+    averaged = float(averaged)
+    with np.errstate(all='ignore'):
+        c = np.sqrt(np.float64(averaged) / 2. ** np.arange(MAX_LEVELS)).astype(np.float32)
+    if not (averaged > 0. and np.all(np.isfinite(c)) and np.all(c > 0.)):
+        raise ValueError(f"averaged must be > 0 (and its scales finite float32), not {averaged}.")
+    return c
+
+
+def harmonic_search_samples(data, n, n_levels, averaged=1., lo=1):
+    """NumPy restatement of the `HarmonicSearch` kernel.
+
+    ``data``: float32 ``(N, nbin) + s``.  Per spectrum and element there is one float32 accumulator per
+    ``j``: ``T_0[j] = p[j]`` and, level by level, ``T_L[j] = T_{L-1}[j] + p[(j i + 2^(L-1)) >> L]`` for ``i =
+    1, 3, ... 2^L - 1`` in ascending order, one rounded add each; ``snr_L[j] = (T_L[j] - float32(2^L)) *
+    c_L`` with ``c = harmonic_scales(averaged)``, one rounded subtract and one rounded multiply.  ``(L, j)``
+    is present iff its fundamental's bin -- ``j`` for ``L = 0``, ``(j + 2^(L-1)) >> L`` otherwise -- is at least
+    ``lo``.  For block ``b`` of ``n`` bins (the last may be short) the winner over the present ``(L, j)`` with
+    ``L < n_levels`` and ``j`` in the block is the largest S/N, among equals the smaller ``L``, then the smaller
+    ``j``; a NaN never wins.  Returns float32 ``(N, ceil(nbin / n), 3) + s``: row `SNR` the winner's S/N, row
+    `OFFSET` its ``j - b n``, row `LEVEL` its ``L``; ``(-inf, 0, 0)`` where a block has nothing present that
+    is not NaN."""
+    data = _check_spectra(data, 'harmonic_search_samples')
+    n, n_levels = _check_search(n, n_levels)
+    N, nbin = data.shape[:2]
+    if not 1 <= nbin <= MAX_NBIN:
+        raise ValueError(f"a spectrum must have 1 ... {MAX_NBIN} bins, not {nbin}.")
+    lo = _check_skip(lo, nbin, 'lo')
+    c = harmonic_scales(averaged)
+    rest = data.shape[2:]
+    nb = -(-nbin // n)
+    j = np.arange(nbin)
+    best = np.full((N, nb) + rest, -np.inf, np.float32)
+    offset = np.zeros((N, nb) + rest, np.int64)
+    level = np.zeros((N, nb) + rest, np.int64)
+    have = np.zeros((N, nb) + rest, bool)
+    acc = data.copy()
+    absent = np.full((N, nb * n - nbin) + rest, np.nan, np.float32)
+    with np.errstate(all='ignore'):
+        for L in range(n_levels):
+            half = (1 << L) >> 1
+            for i in range(1, 1 << L, 2):
+                acc = acc + data[:, (j * i + half) >> L]
+            snr = (acc - np.float32(1 << L)) * c[L]
+            assert snr.dtype == np.float32
+            present = ((j + half) >> L) >= lo
+            snr[:, ~present] = np.nan                      # (absent: never a winner)
+            snr = np.concatenate([snr, absent], axis=1).reshape((N, nb, n) + rest)
+            valid = ~np.isnan(snr)
+            filled = np.where(valid, snr, np.float32(-np.inf))
+            top = filled.max(axis=2)
+            first = (valid & (filled == top[:, :, np.newaxis])).argmax(axis=2)    # the smallest j among equals
+            value = np.take_along_axis(snr, first[:, :, np.newaxis], axis=2)[:, :, 0]
+            better = valid.any(axis=2) & (~have | (value > best))                # (not >=: the smaller L stays)
+            best = np.where(better, value, best)
+            offset = np.where(better, first, offset)
+            level = np.where(better, L, level)
+            have |= better
+    out = np.empty((N, nb, 3) + rest, np.float32)
+    out[:, :, SNR], out[:, :, OFFSET], out[:, :, LEVEL] = best, offset, level
+    return out
+
+
+def harmonic_candidates(best, n, threshold, bin_width=None):
+    """The local maxima of one spectrum's `HarmonicSearch` result above a threshold (host, NumPy).
+
+    ``best``: ``(blocks, 3, ndm)``, one sample as read from ``HarmonicSearch(spectra, n, ...)``.  A cell ``(b,
+    d)`` is a candidate if its S/N is ``>= threshold``, none of its up to 8 neighbours in (block, trial) has
+    a larger S/N, and no neighbour with an equal S/N comes before it in ``(b, d)`` raster order: the rule
+    of `search.boxcar_candidates`.  Returns a structured array with fields ``bin`` (float64: ``(b n +
+    offset) / 2^L``, the fundamental in bins of the spectrum), ``trial``, ``harmonics`` (``2^L``), ``snr`` and,
+    if ``bin_width`` (Hz) is given, ``frequency = bin * bin_width``; sorted by descending ``snr``, then ``bin``,
+    then ``trial``.  Nothing is merged across trials or harmonics."""
+    best = np.asarray(best)
+    n = _check_search(n, 1)[0]
+    if best.ndim != 3 or best.shape[1] != 3:
+        raise ValueError(f"best must be (blocks, 3, ndm), one sample of HarmonicSearch, not {best.shape}.")
+    snr = best[:, SNR].astype(np.float32)
+    b, d = _local_maxima(snr, threshold)
+    fields = [('bin', np.float64), ('trial', np.int64), ('harmonics', np.int64), ('snr', np.float32)]
+    if bin_width is not None:
+        fields.append(('frequency', np.float64))
+    out = np.empty(b.shape[0], np.dtype(fields))
+    harmonics = np.int64(1) << best[b, LEVEL, d].astype(np.int64)
+    out['bin'] = (b * n + best[b, OFFSET, d].astype(np.int64)) / harmonics
+    out['trial'] = d
+    out['harmonics'] = harmonics
+    out['snr'] = snr[b, d]
+    if bin_width is not None:
+        out['frequency'] = out['bin'] * float(bin_width)
+    return out[np.lexsort((out['trial'], out['bin'], -out['snr'].astype(np.float64)))]
+
+
+# -- the tasks ------------------------------------------------------------------------------------------
+def _check_spectra_stream(ih, who):
+    _check_plane_stream(ih, who)
+    if len(ih.shape) < 2:
+        raise ValueError(f"{who} needs a bin axis: samples of shape (nbin, ...).")
+
+
+class Whiten(DeviceTaskMixin, BaseTaskBase):
+    """Divide every block of ``m`` frequency bins of every spectrum by its own mean, per element.
+
+    Parameters
+    ----------
+    ih : stream
+        float32 spectra of shape ``(N, nbin) + s``: the bin axis is the first sample axis -- usually
+        `fluctuation_spectra` of the (time, DM) plane.
+    m : int
+        Bins of a block, 2 ... 65536, counted from bin ``skip``; the last block is whatever is left.
+    skip : int, optional
+        Bins below it come out ``+0``: the DC bin by default.  ``0 <= skip < nbin``.
+    samples_per_frame : int, optional
+        Spectra per frame.  Default: that of ``ih``.
+
+    Shape, sample rate, start time and metadata are those of ``ih``.  The mean is the plain mean of
+    the block, summed in float64 in a fixed order, and the values equal `whiten_samples` bit for
+    bit.  A block that is all zero, holds a NaN or an Inf, or has a negative or a denormal mean comes
+    out as +0.  There is no median and no running fit: a bright line raises the mean of its own block,
+    and red noise steeper than a block is not flattened inside it."""
+
+    #: input bytes fetched at most per `fetch_device` call and launch (assignable); a chunk is a
+    #: whole number of spectra, one at least
+    whiten_budget = 1 << 29
+
+    def __init__(self, ih, m, skip=1, *, samples_per_frame=None):
+        _check_spectra_stream(ih, 'Whiten')
+        self.m = _check_m(m)
+        self._nbin = ih.shape[1]
+        self.skip = _check_skip(skip, self._nbin)
+        self._n_elem = _prod(ih.shape[2:])
+        if samples_per_frame is None:
+            samples_per_frame = max(min(operator.index(ih.samples_per_frame), ih.shape[0]), 1)
+        lone = _lone_frequency(ih)
+        super().__init__(ih, samples_per_frame=operator.index(samples_per_frame), dtype=np.float32,
+                         **(dict(sideband=1) if lone else {}))
+        if lone:
+            del self.meta['__attributes__']['sideband']
+
+    def _chunk_spectra(self):
+        return max(1, int(self.whiten_budget) // (self._nbin * self._n_elem * 4))
+
+    def _input_span(self, first, last):
+        a, b = self._frame_span(first, last)
+        return (self.ih, a, b - a) if b - a <= self._chunk_spectra() else None      # (one fetch only)
+
+    def _compute_frames(self, first, last, out):
+        a, b = self._frame_span(first, last)
+        per = self._chunk_spectra()
+        for c0 in range(a, b, per):
+            c1 = min(b, c0 + per)
+            x = fetch_device(self.ih, c0, c1 - c0)
+            hip.hsum_whiten(x, self._nbin, self._n_elem, self.m, self.skip, out=out[c0 - a:c1 - a])
+
+
+class HarmonicSearch(DeviceTaskMixin, BaseTaskBase):
+    """The best harmonic-sum S/N in every block of ``n`` frequency bins, per spectrum and element: a
+    pulsar's narrow pulse spreads its power over many harmonics, so sums of 1, 2, 4, ... harmonics are
+    formed and the best one kept.
+
+    Parameters
+    ----------
+    ih : stream
+        float32 spectra of shape ``(N, nbin) + s``, ideally of unit mean -- usually ``Whiten(
+        fluctuation_spectra(plane, ...), m)``.  ``nbin`` is 1 ... 2^24.
+    n : int
+        Bins folded into one output block, 1 ... 65536; the last block of a spectrum may be short.
+    n_levels : int, optional
+        ``K``, 1 ... 6: sums of ``2^L`` harmonics for ``L < K``, up to 32.  Default 5.
+    averaged : float, optional
+        ``Nd > 0``: the independent powers averaged into each value (``stack`` of `fluctuation_spectra`).
+    lo : int, optional
+        Lowest bin a fundamental may lie in, ``0 <= lo < nbin``.  Default 1: not the DC bin.
+    samples_per_frame : int, optional
+        Spectra per frame.  Default: that of ``ih``.
+
+    The output is float32 ``(N, ceil(nbin / n), 3) + s`` with the rate, start time and framing of
+    ``ih``.  With ``j`` the bin of the highest harmonic, ``T_0[j] = ih[j]`` and ``T_L[j] = T_{L-1}[j] + ih[(j i +
+    2^(L-1)) >> L]`` for ``i = 1, 3, ... 2^L - 1`` -- the bins ``round_half_up(j i / 2^L)``, ``i = 1 ... 2^L``, of the
+    harmonics of a fundamental at ``j / 2^L`` bins, all at most ``j`` -- and ``snr_L[j] = (T_L[j] - 2^L) * c_L``
+    with ``c_L = float32(sqrt(averaged / 2^L))`` (`harmonic_scales`).  For block ``b`` row `SNR` is the largest
+    ``snr_L[j]`` over the levels and the bins ``b n <= j < (b + 1) n`` whose fundamental's bin (``j`` for ``L = 0``,
+    ``(j + 2^(L-1)) >> L`` otherwise) is at least ``lo``, row `OFFSET` is ``j - b n`` and row `LEVEL` is ``L`` of that
+    winner, as floats.  Among equal S/N the smaller ``L`` wins, then the smaller ``j``; a NaN never wins; a
+    block with nothing else gives ``(-inf, 0, 0)``.  Every sum is one float32 accumulator, the bins added in
+    ascending ``i`` level by level, so values equal `harmonic_search_samples` bit for bit whatever the
+    tiling or the chunking.
+
+    The S/N is ``(sum - mean) / sd`` of the sum for noise of unit mean, NOT a Gaussian significance: for
+    unstacked exponential noise a single bin exceeds ``x`` with probability ``exp(-(x + 1))``, far more
+    often than a normal deviate, and only sums of many powers approach the normal tail.
+
+    Metadata that vary along the bin axis are dropped -- the per-bin ``frequency`` and with it the
+    ``sideband``, a per-bin ``polarization`` -- and those that do not are kept.  `harmonic_candidates` turns
+    one sample of this task into a candidate list.  Nothing leaves HBM: one kernel gathers the harmonics
+    of each ``j`` straight from the spectrum, with no scratch."""
+
+    #: bytes of input and output at most per `fetch_device` call and launch (assignable); a chunk is a
+    #: whole number of spectra, one at least
+    hsum_budget = 1 << 29
+
+    def __init__(self, ih, n, n_levels=5, averaged=1., lo=1, *, samples_per_frame=None):
+        _check_spectra_stream(ih, 'HarmonicSearch')
+        self.n, self.n_levels = _check_search(n, n_levels)
+        self._nbin = nbin = ih.shape[1]
+        if not 1 <= nbin <= MAX_NBIN:
+            raise ValueError(f"a spectrum must have 1 ... {MAX_NBIN} bins, not {nbin}.")
+        self.lo = _check_skip(lo, nbin, 'lo')
+        self.averaged = float(averaged)
+        self.scales = harmonic_scales(self.averaged)
+        rest = tuple(ih.shape[2:])
+        self._n_elem = _prod(rest)
+        self._nb = -(-nbin // self.n)
+        if samples_per_frame is None:
+            samples_per_frame = max(min(operator.index(ih.samples_per_frame), ih.shape[0]), 1)
+        kept = {}
+        for attr in META_ATTRIBUTES:
+            value = getattr(ih, attr, None)
+            if value is not None:
+                full = check_broadcast_to(value, tuple(ih.shape[1:]))
+                if np.all(full == full[:1]):                      # (the same in every bin)
+                    kept[attr] = simplify_shape(np.asanyarray(full[0]))
+        if 'frequency' not in kept:
+            kept.pop('sideband', None)
+        self._plan = None
+        super().__init__(ih, shape=(ih.shape[0], self._nb, 3) + rest,
+                         samples_per_frame=operator.index(samples_per_frame), dtype=np.float32,
+                         **(dict(sideband=1) if _lone_frequency(ih) else {}))
+        if kept:
+            self.meta['__attributes__'] = kept
+        else:
+            self.meta.pop('__attributes__', None)
+
+    def _check_shape(self, value):
+        # (the inherited metadata describe the bins; they are replaced once the stream is set up)
+        return simplify_shape(np.asanyarray(value))
+
+    def _chunk_spectra(self):
+        row = self._n_elem * 4
+        return max(1, int(self.hsum_budget) // ((self._nbin + 3 * self._nb) * row))
+
+    def _input_span(self, first, last):
+        a, b = self._frame_span(first, last)
+        return (self.ih, a, b - a) if b - a <= self._chunk_spectra() else None      # (one fetch only)
+
+    def _compute_frames(self, first, last, out):
+        if self._plan is None:
+            self._plan = hip.HsumPlan(self._nbin, self.n, self.n_levels, self.lo, self._n_elem, self.scales)
+        a, b = self._frame_span(first, last)
+        per = self._chunk_spectra()
+        for c0 in range(a, b, per):
+            c1 = min(b, c0 + per)
+            x = fetch_device(self.ih, c0, c1 - c0)
+            self._plan.execute(x, c1 - c0, out[c0 - a:c1 - a])
+
+    def close(self):
+        super().close()
+        self._drop_cache()
+        if self._plan is not None:
+            self._plan.close()
+            self._plan = None

@@ -361,6 +361,25 @@ def boxcar_search_samples(data, n, n_widths=MAX_WIDTHS):
     return out
 
 
+def _local_maxima(snr, threshold):
+    """The cells ``(b, d)`` of a float32 plane ``snr`` that are ``>= threshold``, have no larger value among
+    their up to 8 neighbours and no equal one before them in raster order: two index arrays."""
+    nb, nd = snr.shape
+    padded = np.full((nb + 2, nd + 2), np.nan, np.float32)             # (a NaN compares False: no neighbour)
+    padded[1:-1, 1:-1] = snr
+    with np.errstate(invalid='ignore'):
+        keep = snr >= np.float32(threshold)
+        for db in (-1, 0, 1):
+            for dd in (-1, 0, 1):
+                if db == 0 and dd == 0:
+                    continue
+                other = padded[1 + db:1 + db + nb, 1 + dd:1 + dd + nd]
+                keep &= ~(other > snr)
+                if (db, dd) < (0, 0):
+                    keep &= ~(other == snr)
+    return np.nonzero(keep)
+
+
 def boxcar_candidates(best, n, threshold):
     """The local maxima of a `BoxcarSearch` result above a threshold (host, NumPy).
 
@@ -376,20 +395,7 @@ def boxcar_candidates(best, n, threshold):
     if best.ndim != 3 or best.shape[1] != 3:
         raise ValueError(f"best must be (blocks, 3, ndm) as BoxcarSearch makes it, not {best.shape}.")
     snr = best[:, SNR].astype(np.float32)
-    nb, nd = snr.shape
-    padded = np.full((nb + 2, nd + 2), np.nan, np.float32)             # (a NaN compares False: no neighbour)
-    padded[1:-1, 1:-1] = snr
-    with np.errstate(invalid='ignore'):
-        keep = snr >= np.float32(threshold)
-        for db in (-1, 0, 1):
-            for dd in (-1, 0, 1):
-                if db == 0 and dd == 0:
-                    continue
-                other = padded[1 + db:1 + db + nb, 1 + dd:1 + dd + nd]
-                keep &= ~(other > snr)
-                if (db, dd) < (0, 0):
-                    keep &= ~(other == snr)
-    b, d = np.nonzero(keep)
+    b, d = _local_maxima(snr, threshold)
     out = np.empty(b.shape[0], CANDIDATE_DTYPE)
     out['sample'] = b * n + best[b, OFFSET, d].astype(np.int64)
     out['trial'] = d

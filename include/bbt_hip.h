@@ -48,6 +48,7 @@ typedef struct bbt_pfb_plan bbt_pfb_plan;
 typedef struct bbt_shift_plan bbt_shift_plan;
 typedef struct bbt_dmt_plan bbt_dmt_plan;
 typedef struct bbt_sps_plan bbt_sps_plan;
+typedef struct bbt_hsum_plan bbt_hsum_plan;
 typedef struct bbt_fir_plan bbt_fir_plan;
 typedef struct bbt_r2c_plan bbt_r2c_plan;
 typedef struct bbt_gather_plan bbt_gather_plan;
@@ -590,6 +591,40 @@ int bbt_sps_plan_info(const bbt_sps_plan* plan, int* width, int* fuse, int* spli
                       int64_t* scratch_bytes, float* scales);
 int bbt_sps_execute(bbt_sps_plan* plan, const float* in_dev, int64_t n_in, float* out_dev, int64_t n_blocks,
                     bbt_stream stream);
+
+/* ---- periodicity search on stacked fluctuation spectra: Whiten, HarmonicSearch -----
+ * A chunk is p[s][j][e], s < n_spec spectra of nbin bins, float32, element fastest; every (s, e) is an
+ * independent spectrum.
+ *
+ * bbt_hsum_whiten: bins j < skip come out +0; from skip on the bins are cut into blocks of m (2 ...
+ * 65536), the last one whatever is left.  Per (spectrum, block, element), in float64 with every step
+ * rounded once: S1 = sum x in the two-level order of bbt_sps_standardize (segments of 32 bins summed in
+ * bin order from the block's first bin, the segment sums added in segment order), mean = S1 / len, r = 1 /
+ * mean; then in float32 out = x * (float)r, one rounded multiply.  A block whose mean is not finite or
+ * not > 0, or whose (float)r is not finite, comes out as +0.  0 <= skip < nbin.  out may not overlap x.
+ *
+ * bbt_hsum_execute: one float32 accumulator per top harmonic j: T_0[j] = p[j], T_L[j] = T_{L-1}[j] + p[(j i
+ * + 2^(L-1)) >> L] for i = 1, 3, ... 2^L - 1 in ascending order (one rounded add each), snr_L[j] = (T_L[j] -
+ * (float)2^L) * c_L (one rounded subtract, one rounded multiply), L < n_levels <= 6, with the n_levels
+ * scales c_L the plan was made with.  (L, j) is present iff its fundamental's bin, j for L = 0 and (j +
+ * 2^(L-1)) >> L otherwise, is >= lo.  For block b < ceil(nbin / n) of n bins (1 ... 65536; the last may be
+ * short) the winner over the present (L, j), b n <= j < min((b + 1) n, nbin), is written as out[s][b][0][e] =
+ * its snr, out[s][b][1][e] = (float)(j - b n), out[s][b][2][e] = (float)L: the largest snr, then the smaller
+ * L, then the smaller j; a NaN never wins, and a block with nothing else gives (-inf, 0, 0).  The winner
+ * is the maximum of a total order and no sum is shared between threads, so results do not depend on
+ * the launch or the tiling (BBT_HSUM_WIDTH = 16, 32 or 64 elements per workgroup, BBT_HSUM_SPLIT = 1, 2,
+ * 4, 8 or 16 threads per (spectrum, block, element), BBT_HSUM_ROWS = 1, 2, 4, 8 or 16 segment rows in
+ * bbt_hsum_whiten, read from the environment at every call, only change the speed).  nbin 1 ... 2^24, 0
+ * <= lo < nbin.  No scratch.  plan_info takes a null plan (the tiling only); scales: 6 floats.
+ * Every refusal -- a null or misaligned pointer, a size out of range, no spectra -- comes before
+ * anything is launched.  Asynchronous on `stream`. */
+int bbt_hsum_whiten(const float* x_dev, float* out_dev, int64_t n_spec, int64_t nbin, int64_t n_elem, int64_t m,
+                    int64_t skip, bbt_stream stream);
+int bbt_hsum_plan_create(bbt_hsum_plan** plan, int64_t nbin, int64_t n, int64_t n_levels, int64_t lo,
+                         int64_t n_elem, const float* scales_host);
+int bbt_hsum_plan_destroy(bbt_hsum_plan* plan);
+int bbt_hsum_plan_info(const bbt_hsum_plan* plan, int* width, int* split, int* rows, float* scales);
+int bbt_hsum_execute(bbt_hsum_plan* plan, const float* in_dev, int64_t n_spec, float* out_dev, bbt_stream stream);
 
 /* ---- real-valued streams ------------------------------------------------------
  * float32 streams run through the complex kernels (the reference's rfft/irfft
