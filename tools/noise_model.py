@@ -4,8 +4,11 @@ scanned over the tiles of a frame, then a walk from each tile's entry state that
 
 It is the specification the kernels are written against (same decisions, same order of floating
 point operations, same ambiguity flags) and it reproduces `NoiseGenerator`'s frames bit for bit
-(tests/test_noise_model.py).  `frames(...)` also reports which paths of the sampler the words of
-a frame exercise, which is how the inputs of tests/test_noise_gpu.py were chosen.
+(tests/test_noise_model.py).  `frame(...)` also reports which paths of the sampler and which seams
+of the three passes the words of a frame exercise (the state each tile and each round of the scan
+is entered in, tail pairs across tiles, counter carries, ...), which is how the inputs of
+tests/test_noise_gpu.py were chosen (tools/noise_find_cases.py); `numpy_frame(...)` is NumPy
+itself for a frame given by key and counter.
 """
 import os
 import re
@@ -177,7 +180,18 @@ def frame(key, counter, n, n_words=None, guard=GUARD, stats=None):
 
     Returns (values float32[n], total emits within the words, ambiguous flag).  If the words do
     not hold n normals the missing values are left 0 (the host then asks again with more words).
-    ``stats``: a dict that receives counts of the paths taken by the normals that are kept."""
+    ``stats``: a dict that receives what the frame exercises; only tiles and decisions that bear
+    on the first n normals count.  The tally of paths (direct, wedge_accept, wedge_reject, tail,
+    tail_reject, wedge_straddle), total, n_tile, and
+      last_kind               how normal n - 1 is made: 'direct', 'wedge', 'tail', or 'tail_straddled'
+                              for a tail opened in an earlier tile than the one that emits it
+      tile_entry              per state, the tiles t >= 1 with off[t] < n entered in it
+      tail_pair_across_tiles  tail pairs whose words lie in two tiles: dict(accepted=, rejected=)
+      tail_reject_runs        the longest run of rejected pairs in one tail
+      round_entry             the state carried into tile 256 k, k >= 1 (a round of the scan)
+      host_carry, wrap_block  words the host's + 1 turns to zero; the block of the frame at
+                              which the device's sum wraps word 0, or None
+      tail_ranks, walk        the ranks of the normals made by tails; the walk, for `ambiguous_at`"""
     if n_words is None:
         n_words = word_count(n)
     assert n_words % 4 == 0 and n_words > 0
@@ -213,12 +227,17 @@ def frame(key, counter, n, n_words=None, guard=GUARD, stats=None):
     rank = off.copy()
     tiles = np.arange(n_tile)
     tally = dict(direct=0, wedge_accept=0, wedge_reject=0, tail=0, tail_reject=0, wedge_straddle=0)
-    last_kind = None
+    n_all = n_tile * TILE
+    st_at = np.zeros(n_all, np.int64)                      # the state in which each word is met
+    kept_at = np.zeros(n_all, bool)
+    emit_at = np.zeros(n_all, bool)
+    rank_at = np.zeros(n_all, np.int64)
     for j in range(TILE):
         i = tiles * TILE + j
         live = ~beyond[i]
         kept = live & (rank < n)                           # decisions that bear on the output
         e = emit[i, st].astype(bool) & live
+        st_at[i], kept_at[i], emit_at[i], rank_at[i] = st, kept, e, rank
         is_tail2 = st >= TAIL2
         val = np.where(st == START, W.x[i], np.where(st == WEDGE, W.x_prev[i],
                                                      np.where(st == TAIL2 + 1, -W.tail_v[i], W.tail_v[i])))
@@ -234,14 +253,89 @@ def frame(key, counter, n, n_words=None, guard=GUARD, stats=None):
         tally['tail_reject'] += int((kept & ~e & is_tail2).sum())
         if j == TILE - 1:
             tally['wedge_straddle'] += int((kept & (st == START) & W.wedge_init[i] & (tiles < n_tile - 1)).sum())
-        if (put & (rank == n - 1)).any():
-            last_kind = ('direct', 'wedge', 'tail', 'tail', 'tail', 'tail')[int(st[put & (rank == n - 1)][0])]
         rank = rank + e
         st = np.where(live, nxt[i, st], st)
     if stats is not None:
-        stats.update(tally, last_kind=last_kind, total=total, n_tile=n_tile)
-        # is normal n - 2 a wedge acceptance (the last one sits right after one)?
+        stats.update(tally, total=total, n_tile=n_tile)
+        stats.update(_walk_stats(W, st_at, kept_at, emit_at, rank_at, entry, off, n))
+        stats.update(_counter_stats(counter, n_words))
     return out, total, flag
+
+
+def _walk_stats(W, st_at, kept_at, emit_at, rank_at, entry, off, n):
+    """What the walk of one frame exercised beyond the tally: only tiles and decisions that bear
+    on the first n normals count (arrays over the words of the frame, as the walk met them)."""
+    where = np.arange(len(st_at))
+    pair = kept_at & (st_at >= TAIL2)                      # word i closes the tail pair (i - 1, i)
+    accepted, rejected = pair & emit_at, pair & ~emit_at
+    tile_start = where % TILE == 0
+    # rejected pairs of one tail follow each other at a distance of two words
+    longest = run = 0
+    before = None
+    for i in np.nonzero(rejected)[0]:
+        run = run + 1 if before is not None and i - before == 2 else 1
+        longest, before = max(longest, run), i
+    # a tail was entered in an earlier tile if the word that opened it lies in one
+    tail_ranks, straddled = [], []
+    for i in np.nonzero(accepted)[0]:
+        k = i
+        while st_at[k] != START:
+            k -= 1
+        tail_ranks.append(int(rank_at[i]))
+        straddled.append(bool(k // TILE < i // TILE))
+    last = np.nonzero(kept_at & emit_at & (rank_at == n - 1))[0]
+    last_kind = None
+    if len(last):
+        last_kind = ('direct', 'wedge', 'tail', 'tail', 'tail', 'tail')[int(st_at[last[0]])]
+        if last_kind == 'tail' and straddled[tail_ranks.index(n - 1)]:
+            last_kind = 'tail_straddled'
+    bears = off < n
+    tile_entry = [int(((entry[1:] == s) & bears[1:]).sum()) for s in range(N_STATE)]
+    rounds = np.arange(256, len(entry), 256)
+    walk = dict(w=W.w, st=st_at, kept=kept_at, emit=emit_at)
+    return dict(last_kind=last_kind, tile_entry=tile_entry,
+                tail_pair_across_tiles=dict(accepted=int((accepted & tile_start).sum()),
+                                            rejected=int((rejected & tile_start).sum())),
+                tail_reject_runs=longest, round_entry=[int(entry[t]) for t in rounds if bears[t]],
+                tail_ranks=tail_ranks, walk=walk)
+
+
+def ambiguous_at(walk, guard):
+    """How many of the decisions that bear on a frame's normals (``walk``: what `frame` leaves in
+    its stats) a guard calls ambiguous: wedge and tail comparisons, and float32 roundings of an
+    accepted tail's value.  The walk itself does not depend on the guard, so one run of `frame`
+    serves any number of guards."""
+    W = Words(walk['w'], guard)
+    pair = walk['kept'] & (walk['st'] >= TAIL2)
+    return int((walk['kept'] & (walk['st'] == WEDGE) & W.wedge_amb).sum() + (pair & W.tail_amb).sum() +
+               (pair & walk['emit'] & W.tail_v_amb).sum())
+
+
+def _counter_stats(counter, n_words):
+    """Where the counter carries: how many words the host's + 1 turns to zero, and the block of
+    the frame at which the device's sum wraps word 0 (None if none does)."""
+    host_carry = 0
+    while host_carry < 4 and int(counter[host_carry]) == 2**64 - 1:
+        host_carry += 1
+    first0 = (int(counter[0]) + 1) % 2**64
+    wrap = 2**64 - first0
+    return dict(host_carry=host_carry, wrap_block=wrap if first0 and wrap < n_words // 4 else None)
+
+
+def numpy_frame(key, counter, n):
+    """The first n normals, as float32, that NumPy gives for a Philox state with this key and
+    counter and an empty buffer (buffer_pos = 4, has_uint32 = 0)."""
+    bg = np.random.Philox(0)
+    state = bg.state
+    state['state']['key'][:] = [int(k) for k in key]
+    state['state']['counter'][:] = [int(c) for c in counter]
+    state.update(buffer_pos=4, has_uint32=0, uinteger=0)
+    bg.state = state
+    return np.random.Generator(bg).normal(size=int(n)).astype(np.float32)
+
+
+#: the keys of a frame's stats that `frames` adds up over its frames
+_SUMMED = ('direct', 'wedge_accept', 'wedge_reject', 'tail', 'tail_reject', 'wedge_straddle')
 
 
 def frames(key, counters, n, n_words=None, guard=GUARD, stats=None):
@@ -259,10 +353,15 @@ def frames(key, counters, n, n_words=None, guard=GUARD, stats=None):
             W *= 2
         out[f], flags[f] = v, flag
         if stats is not None:
-            for k, x in s.items():
-                if isinstance(x, int) and k not in ('total', 'n_tile'):
-                    stats[k] = stats.get(k, 0) + x
+            for k in _SUMMED:
+                stats[k] = stats.get(k, 0) + s[k]
+            stats['tile_entry'] = [a + b for a, b in zip(stats.get('tile_entry', [0] * N_STATE), s['tile_entry'])]
+            across = stats.setdefault('tail_pair_across_tiles', dict(accepted=0, rejected=0))
+            for k, x in s['tail_pair_across_tiles'].items():
+                across[k] += x
+            stats['tail_reject_runs'] = max(stats.get('tail_reject_runs', 0), s['tail_reject_runs'])
             stats.setdefault('last_kinds', []).append(s['last_kind'])
+            stats.setdefault('per_frame', []).append(s)
     return out, flags
 
 
@@ -287,4 +386,4 @@ if __name__ == '__main__':
     seed = int(sys.argv[1]) if len(sys.argv) > 1 else 0
     st = {}
     got, flags = stream_frames(seed, 4096, (2,), np.complex64, [0, 1, 1000], stats=st)
-    print(st, flags)
+    print({k: v for k, v in st.items() if k != 'per_frame'}, flags)
