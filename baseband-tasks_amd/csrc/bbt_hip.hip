@@ -36,6 +36,7 @@
 #include "dmt_kernels.hpp"
 #include "sps_kernels.hpp"
 #include "hsum_kernels.hpp"
+#include "lspec_kernels.hpp"
 #include "r2c_kernels.hpp"
 #include "gather_kernels.hpp"
 #include "pack_kernels.hpp"
@@ -45,7 +46,7 @@
 
 using namespace bbt;
 
-#define BBT_VERSION 165
+#define BBT_VERSION 166
 
 // ---------------------------------------------------------------------------
 // errors
@@ -3924,6 +3925,129 @@ extern "C" int bbt_hsum_execute(bbt_hsum_plan* p, const float* in_dev, int64_t n
         case 5: hipLaunchKernelGGL((k_hsum_search<5>), grid, block, 0, st, in_dev, out_dev, g); break;
         default: hipLaunchKernelGGL((k_hsum_search<6>), grid, block, 0, st, in_dev, out_dev, g); break;
     }
+    HIP_TRY(hipGetLastError());
+    return 0;
+}
+
+// ---------------------------------------------------------------------------
+// fluctuation spectra of 2^15 ... 2^22 points (lspec_kernels.hpp; every index is lspec_geo.hpp's)
+struct bbt_lspec_plan {
+    long long n = 0, stack = 0, n_elem = 0;
+    float2 *tw1 = nullptr, *tw2 = nullptr, *tw_hi = nullptr, *tw_lo = nullptr;
+    float2* scratch = nullptr;
+    size_t scratch_bytes = 0;
+};
+
+// BBT_LSPEC_THREADS: threads of a workgroup of both passes (256, 512, 1024).  Read at every call, for
+// measuring; which thread moves which cell changes, no value of the output does.  Anything else leaves
+// the default.
+static int lspec_env_threads() {
+    const int t = dmt_env("BBT_LSPEC_THREADS", {256, 512, 1024});
+    return t ? t : BBT_LSPEC_THREADS;
+}
+
+// count entries exp(-2 pi i j mult / len), j < count, made in float64 and rounded once
+static int lspec_table(float2** dst, long long count, long long mult, long long len) {
+    std::vector<float2> h((size_t)count);
+    const double unit = -2. * 3.14159265358979323846264338327950288 / (double)len;
+    for (long long j = 0; j < count; ++j) {
+        const long long m = (j * mult) % len;                   // reduced in integers first
+        h[(size_t)j] = make_float2((float)std::cos(unit * (double)m), (float)std::sin(unit * (double)m));
+    }
+    HIP_TRY(hipMalloc((void**)dst, h.size() * sizeof(float2)));
+    HIP_TRY(hipMemcpy(*dst, h.data(), h.size() * sizeof(float2), hipMemcpyHostToDevice));
+    return 0;
+}
+
+extern "C" int bbt_lspec_plan_destroy(bbt_lspec_plan* p) {
+    if (!p) return 0;
+    for (float2* t : {p->tw1, p->tw2, p->tw_hi, p->tw_lo, p->scratch})
+        if (t) (void)hipFree(t);
+    delete p;
+    return 0;
+}
+
+extern "C" int bbt_lspec_plan_create(bbt_lspec_plan** plan, int64_t n, int64_t stack, int64_t n_elem) {
+    ARG_TRY(plan, "bbt_lspec_plan_create: null argument");
+    *plan = nullptr;
+    const char* err = lspec_sizes(n, stack, n_elem);
+    ARG_TRY(!err, "bbt_lspec_plan_create: %s (n=%lld, stack=%lld, n_elem=%lld)", err ? err : "", (long long)n,
+            (long long)stack, (long long)n_elem);
+    LspecGeo g = {};
+    err = lspec_geo(n, n_elem, 1, 0, &g);
+    ARG_TRY(!err, "bbt_lspec_plan_create: %s", err ? err : "");
+    bbt_lspec_plan* p = new bbt_lspec_plan;
+    p->n = n, p->stack = stack, p->n_elem = n_elem;
+    const long long lo = 1ll << BBT_LSPEC_TW_LO_LOG2;
+    if (lspec_table(&p->tw1, g.n1 / 2, 1, g.n1) || lspec_table(&p->tw2, g.n2 / 2, 1, g.n2) ||
+        lspec_table(&p->tw_hi, n / lo, lo, n) || lspec_table(&p->tw_lo, lo, 1, n)) {
+        bbt_lspec_plan_destroy(p);
+        return 1;
+    }
+    *plan = p;
+    return 0;
+}
+
+// the split and the tiling, and what a call under `budget` bytes of scratch (<= 0: the default) takes:
+// pairs per launch and the bytes of scratch
+extern "C" int bbt_lspec_plan_info(const bbt_lspec_plan* p, int64_t budget, int* n1, int* n2, int* cols, int* pairs,
+                                   int* threads, int64_t* pairs_per_launch, int64_t* scratch_bytes) {
+    ARG_TRY(p, "bbt_lspec_plan_info: null argument");
+    LspecGeo g = {};
+    const long long per = lspec_pairs_per_launch(p->n, p->n_elem, budget > 0 ? budget : BBT_LSPEC_BUDGET);
+    const char* err = lspec_geo(p->n, p->n_elem, per, 0, &g);
+    ARG_TRY(!err, "bbt_lspec_plan_info: %s", err ? err : "");
+    if (n1) *n1 = g.n1;
+    if (n2) *n2 = g.n2;
+    if (cols) *cols = g.c1;
+    if (pairs) *pairs = g.cp;
+    if (threads) *threads = lspec_env_threads();
+    if (pairs_per_launch) *pairs_per_launch = per;
+    if (scratch_bytes) *scratch_bytes = 8 * p->n * per;
+    return 0;
+}
+
+// out[m][k][e], m < n_spec, k <= n / 2, from in[t][e], t < n_in, n_in >= n_spec * stack * n
+extern "C" int bbt_lspec_execute(bbt_lspec_plan* p, const float* in_dev, int64_t n_in, float* out_dev,
+                                 int64_t n_spec, int64_t budget, bbt_stream stream) {
+    ARG_TRY(p && in_dev && out_dev, "bbt_lspec_execute: null argument");
+    ARG_TRY((((uintptr_t)in_dev | (uintptr_t)out_dev) & 3) == 0, "bbt_lspec_execute: arrays must be 4-byte aligned");
+    ARG_TRY(n_spec >= 1, "bbt_lspec_execute: no whole transform (n_spec=%lld)", (long long)n_spec);
+    ARG_TRY(n_spec <= BBT_LSPEC_MAX_VALUES / (p->n * p->stack * p->n_elem),
+            "bbt_lspec_execute: more than 2^40 values in one call");
+    ARG_TRY(n_in >= n_spec * p->stack * p->n, "bbt_lspec_execute: %lld samples are not %lld stacks of %lld x %lld",
+            (long long)n_in, (long long)n_spec, p->stack, p->n);
+    const long long per = lspec_pairs_per_launch(p->n, p->n_elem, budget > 0 ? budget : BBT_LSPEC_BUDGET);
+    const long long n_launch = lspec_n_launch(p->n_elem, per);
+    LspecGeo g = {};
+    for (long long i : {0ll, n_launch - 1}) {
+        const char* err = lspec_geo(p->n, p->n_elem, per, i, &g);
+        ARG_TRY(!err, "bbt_lspec_execute: %s (n=%lld, n_elem=%lld)", err ? err : "", p->n, p->n_elem);
+    }
+    const size_t need = (size_t)(8 * p->n * per);
+    if (p->scratch_bytes < need) {
+        if (p->scratch) HIP_TRY(hipFree(p->scratch));
+        p->scratch = nullptr, p->scratch_bytes = 0;
+        HIP_TRY(hipMalloc((void**)&p->scratch, need));
+        p->scratch_bytes = need;
+    }
+    hipStream_t st = (hipStream_t)stream;
+    const float scale = 1.f / (float)p->stack;
+    const dim3 block((unsigned)lspec_env_threads());
+    const long long nbin = p->n / 2 + 1;
+    for (long long m = 0; m < n_spec; ++m)
+        for (long long q = 0; q < p->stack; ++q) {
+            const float* x = in_dev + (m * p->stack + q) * p->n * p->n_elem;
+            float* o = out_dev + m * nbin * p->n_elem;
+            const int mode = q == 0 ? 0 : (q + 1 < p->stack ? 1 : 2);
+            for (long long i = 0; i < n_launch; ++i) {
+                lspec_geo(p->n, p->n_elem, per, i, &g);
+                hipLaunchKernelGGL(k_lspec_first, dim3((unsigned)g.n_wg1), block, 0, st, x,
+                                   p->scratch, p->tw1, p->tw_hi, p->tw_lo, g);
+                hipLaunchKernelGGL(k_lspec_last, dim3((unsigned)g.n_wg2), block, 0, st, p->scratch, o,
+                                   p->tw2, g, mode, scale);
+            }
+        }
     HIP_TRY(hipGetLastError());
     return 0;
 }

@@ -123,6 +123,11 @@ SIGNATURES = {
     'bbt_hsum_plan_destroy': [_vp],
     'bbt_hsum_plan_info': [_vp, C.POINTER(_int), C.POINTER(_int), C.POINTER(_int), C.POINTER(C.c_float)],
     'bbt_hsum_execute': [_vp, _vp, _i64, _vp, _vp],
+    'bbt_lspec_plan_create': [_pvp, _i64, _i64, _i64],
+    'bbt_lspec_plan_destroy': [_vp],
+    'bbt_lspec_plan_info': [_vp, _i64, C.POINTER(_int), C.POINTER(_int), C.POINTER(_int), C.POINTER(_int),
+                            C.POINTER(_int), _pi64, _pi64],
+    'bbt_lspec_execute': [_vp, _vp, _i64, _vp, _i64, _i64, _vp],
     'bbt_fir_plan_create': [_pvp, _int, _int, _vp],
     'bbt_fir_plan_destroy': [_vp],
     'bbt_fir_execute': [_vp, _vp, _vp, _i64, _vp],
@@ -157,7 +162,7 @@ SIGNATURES = {
 }
 
 #: oldest libbbt_hip.so whose entry points and argument meanings this binding assumes
-MIN_LIB_VERSION = 165
+MIN_LIB_VERSION = 166
 
 _lib = None
 _lock = threading.Lock()
@@ -1815,6 +1820,49 @@ class HsumPlan(_Plan):
             raise ValueError("HsumPlan.execute: float32 DeviceArrays of n_spec * nbin * n_elem and n_spec * "
                              "n_blocks * 3 * n_elem values are needed")
         check(lib().bbt_hsum_execute(self._h, in_dev.ptr_to_read(), n_spec, out_dev.ptr, _stream))
+
+
+#: bounds of the long fluctuation spectra (csrc/lspec_geo.hpp)
+LSPEC_MIN_LOG2, LSPEC_MAX_LOG2, LSPEC_MAX_STACK, LSPEC_BUDGET = 15, 22, 1 << 20, 1 << 29
+LSPEC_LDS_CELLS, LSPEC_MAX_COLS, LSPEC_MAX_PAIRS = 8192, 32, 16
+
+
+class LongSpectraPlan(_Plan):
+    """out[m, k, e] = the mean over ``stack`` consecutive transforms of ``|sum_t in[(m stack + q) n + t, e]
+    exp(-2 pi i k t / n)|^2``, ``k <= n / 2``, for ``n`` a power of two from 2^15 to 2^22 (bbt_lspec_* in
+    include/bbt_hip.h; `periodicity.long_spectra_samples` is the NumPy yardstick)."""
+    _destroy = 'bbt_lspec_plan_destroy'
+
+    def __init__(self, n, stack, n_elem):
+        super().__init__()
+        self.n, self.stack, self.n_elem = int(n), int(stack), int(n_elem)
+        self.nbin = self.n // 2 + 1
+        check(lib().bbt_lspec_plan_create(C.byref(self._h), self.n, self.stack, self.n_elem))
+
+    def info(self, budget=0):
+        """The split ``n1 x n2``, the columns of a first-pass and the column pairs of a last-pass
+        workgroup, its threads (BBT_LSPEC_THREADS), and what a call under ``budget`` bytes of scratch (0: the default, 512 MiB) takes: the
+        pairs of a launch and the scratch bytes."""
+        n1, n2, cols, pairs, threads = _int(0), _int(0), _int(0), _int(0), _int(0)
+        per, scratch = C.c_int64(0), C.c_int64(0)
+        check(lib().bbt_lspec_plan_info(self._h, int(budget), C.byref(n1), C.byref(n2), C.byref(cols), C.byref(pairs),
+                                        C.byref(threads), C.byref(per), C.byref(scratch)))
+        return dict(n1=n1.value, n2=n2.value, cols=cols.value, pairs=pairs.value, threads=threads.value,
+                    pairs_per_launch=per.value,
+                    scratch_bytes=scratch.value)
+
+    def execute(self, in_dev, n_spec, out_dev, budget=0):
+        """``in_dev``: float32, at least ``n_spec * stack * n * n_elem`` values; ``out_dev``: float32, at least
+        ``n_spec * (n // 2 + 1) * n_elem``.  ``budget``: bytes of scratch a launch may use (0: the default)."""
+        n_spec = int(n_spec)
+        if in_dev.dtype != np.float32 or out_dev.dtype != np.float32:
+            raise TypeError("LongSpectraPlan.execute: float32 DeviceArrays are needed")
+        if (n_spec < 1 or in_dev.size < n_spec * self.stack * self.n * self.n_elem
+                or out_dev.size < n_spec * self.nbin * self.n_elem):
+            raise ValueError("LongSpectraPlan.execute: float32 DeviceArrays of n_spec * stack * n * n_elem and "
+                             "n_spec * (n // 2 + 1) * n_elem values are needed, n_spec >= 1")
+        check(lib().bbt_lspec_execute(self._h, in_dev.ptr_to_read(), in_dev.size // self.n_elem, out_dev.ptr, n_spec,
+                                      int(budget), _stream))
 
 
 COMM_ID_BYTES = 128

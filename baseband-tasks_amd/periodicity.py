@@ -1,6 +1,6 @@
 """Periodicity search on the (time, DM) plane: the fluctuation spectrum of every trial, made in
-stacks of short transforms by tasks the package has already (`fluctuation_spectra`), whitened block
-by block (`Whiten`), the sums of 1, 2, 4, ... 32 harmonics formed and the best S/N kept per block of
+stacks of short transforms by tasks the package has already or, from 2^15 to 2^22 points, by
+`LongSpectra` (`fluctuation_spectra` routes), whitened block by block (`Whiten`), the sums of 1, 2, 4, ... 32 harmonics formed and the best S/N kept per block of
 frequency bins (`HarmonicSearch`), the local maxima of which are the candidates
 (`harmonic_candidates`, on the host).
 
@@ -8,7 +8,9 @@ The reference has no such tasks, so the rules are this package's, restated in Nu
 (`whiten_samples`, `harmonic_search_samples`) and computed by csrc/hsum_kernels.hpp.  A block's mean
 is one float64 sum in a fixed two-level order; a harmonic sum is ONE float32 accumulator per top
 harmonic, the gathered bins added in a fixed order; the winner of a block is the maximum of a total
-order.  So every value has one correct bit pattern, whatever the tiling or the chunking."""
+order.  So every value has one correct bit pattern, whatever the tiling or the chunking.  `LongSpectra`
+is the exception: a float32 transform has no single correct rounding, so `long_spectra_samples` is a
+float64 yardstick its values are near, and what is exact is that they do not depend on the chunking."""
 import operator
 
 import numpy as np
@@ -16,12 +18,13 @@ import numpy as np
 from . import hip
 from .base import META_ATTRIBUTES, BaseTaskBase, SetAttribute, _stream_rate, check_broadcast_to, simplify_shape
 from .channelize import Channelize
+from .fourier import check_transform_length
 from .device_task import DeviceTaskMixin, fetch_device
 from .functions import Square
 from .integration import Integrate
 from .search import _check_plane_stream, _local_maxima, _lone_frequency, _prod
 
-__all__ = ['fluctuation_spectra', 'Whiten', 'whiten_samples', 'HarmonicSearch', 'harmonic_search_samples',
+__all__ = ['fluctuation_spectra', 'LongSpectra', 'long_spectra_samples', 'Whiten', 'whiten_samples', 'HarmonicSearch', 'harmonic_search_samples',
            'harmonic_scales', 'harmonic_candidates', 'SNR', 'OFFSET', 'LEVEL']
 
 #: rows of `HarmonicSearch`'s output: the best S/N of a block, its top harmonic's bin relative to the
@@ -31,32 +34,86 @@ SNR, OFFSET, LEVEL = 0, 1, 2
 SEGMENT = 32          # bins of a segment of Whiten's two-level sums (BBT_HSUM_SEG)
 MIN_M, MAX_M = hip.HSUM_MIN_M, hip.HSUM_MAX_M
 MAX_N, MAX_LEVELS, MAX_NBIN = hip.HSUM_MAX_N, hip.HSUM_MAX_LEVELS, hip.HSUM_MAX_NBIN
+#: the transform lengths of `LongSpectra`: 2^15 ... 2^22
+LONG_LENGTHS = tuple(1 << k for k in range(hip.LSPEC_MIN_LOG2, hip.LSPEC_MAX_LOG2 + 1))
+_LONG_RANGE = f"a power of two from 2^{hip.LSPEC_MIN_LOG2} = {LONG_LENGTHS[0]} to 2^{hip.LSPEC_MAX_LOG2} = {LONG_LENGTHS[-1]}"
 
 
 # -- the spectra ----------------------------------------------------------------------------------------
 def fluctuation_spectra(plane, n, stack=1):
-    """Stacked power spectra of every column of a float32 stream: ``Integrate(Square(Channelize(plane,
-    n)), stack)``, nothing else -- the transform of a real stream is an ``rfft`` per element, so the
-    result is float32 ``(nspec, n // 2 + 1) + plane.sample_shape`` at ``plane.sample_rate / (n * stack)``,
-    every value the average of ``stack`` consecutive power spectra of ``n`` samples, and it never leaves
-    the device.
+    """Stacked power spectra of every column of a float32 stream, float32 ``(nspec, n // 2 + 1) +
+    plane.sample_shape`` at ``plane.sample_rate / (n * stack)``, every value the average of ``stack``
+    consecutive power spectra of ``n`` samples; it never leaves the device.
+
+    For the ``n`` that `Channelize` takes -- up to 8192, and 16384 -- it is ``Integrate(Square(Channelize(
+    plane, n)), stack)``, nothing else: the transform of a real stream is an ``rfft`` per element.  For ``n`` a
+    power of two from 2^15 to 2^22 it is `LongSpectra`, the same unnormalised transform and the same mean
+    over the stack.  Any other ``n`` is a ``ValueError``.
 
     ``plane`` is usually the (time, DM) plane of `DMTrials`, which has a frequency and no sideband; such
-    a stream is relabelled with ``sideband=1`` first, as the base classes take the two together.  ``n``
-    is what `Channelize` takes: up to 16384.  Bin ``j`` is fluctuation frequency ``j * bin_width`` with
-    ``bin_width = plane.sample_rate / n`` in Hz, an attribute of the task returned.  The ``frequency``
-    `Channelize` attaches to the bins -- the plane's own plus the bin's -- is meaningless here:
-    `HarmonicSearch` drops it."""
+    a stream is relabelled with ``sideband=1`` first on the short route, as the base classes take the two
+    together.  Bin ``j`` is fluctuation frequency ``j * bin_width`` with ``bin_width = plane.sample_rate / n``
+    in Hz, an attribute of the task returned.  The ``frequency`` `Channelize` attaches to the bins on the
+    short route -- the plane's own plus the bin's -- is meaningless here: `HarmonicSearch` drops it.
+    `LongSpectra` attaches none."""
     if np.dtype(plane.dtype) != np.dtype(np.float32):
         raise TypeError(f"fluctuation_spectra works on a float32 stream; got {plane.dtype}.")
     n, stack = operator.index(n), operator.index(stack)
     if stack < 1:
         raise ValueError(f"stack must be at least 1, not {stack}.")
+    if n in LONG_LENGTHS:
+        return LongSpectra(plane, n, stack)
+    try:
+        check_transform_length(n)
+    except ValueError as exc:
+        raise ValueError(f"{exc}  Longer spectra (LongSpectra) take n {_LONG_RANGE}.") from None
     if _lone_frequency(plane):
         plane = SetAttribute(plane, frequency=plane.frequency, sideband=1)
     spectra = Integrate(Square(Channelize(plane, n)), stack)
     spectra.bin_width = _stream_rate(plane) / n
     return spectra
+
+
+def _check_long(n, stack):
+    n, stack = operator.index(n), operator.index(stack)
+    if n not in LONG_LENGTHS:
+        raise ValueError(f"LongSpectra transforms n samples with n {_LONG_RANGE}, not {n}.")
+    if not 1 <= stack <= hip.LSPEC_MAX_STACK:
+        raise ValueError(f"stack must be 1 ... {hip.LSPEC_MAX_STACK}, not {stack}.")
+    return n, stack
+
+
+def _long_spectra(data, n, stack):
+    data = np.asarray(data)
+    if data.dtype != np.float32 or data.ndim < 1:
+        raise TypeError(f"long_spectra_samples: data must be float32 (N, ...), not {data.dtype} {data.shape}.")
+    nspec = data.shape[0] // (n * stack)
+    if nspec < 1:
+        raise ValueError(f"{data.shape[0]} samples are less than one stack of {stack} transforms of {n}.")
+    out = np.empty((nspec, n // 2 + 1) + data.shape[1:], np.float32)
+    scale = np.float64(np.float32(1. / stack))
+    with np.errstate(all='ignore'):
+        for m in range(nspec):
+            acc = 0.
+            for q in range(stack):
+                x = data[(m * stack + q) * n:(m * stack + q + 1) * n].astype(np.float64)
+                z = np.fft.rfft(x, axis=0)
+                acc = acc + (z.real ** 2 + z.imag ** 2)
+            out[m] = acc * scale if stack > 1 else acc
+    return out
+
+
+def long_spectra_samples(data, n, stack=1):
+    """NumPy yardstick of `LongSpectra`: float32 ``data`` of shape ``(N,) + s`` gives float32 ``(N // (n *
+    stack), n // 2 + 1) + s``; per output spectrum ``m``, bin ``j`` and element ::
+
+        p_q[j] = | sum_t data[(m * stack + q) * n + t] * exp(-2 pi i j t / n) |^2     (np.fft.rfft in float64)
+        out[j] = p_0[j]  for stack == 1,  else  (p_0 + ... + p_{stack-1}) * float32(1 / stack)
+
+    all in float64 and rounded to float32 once at the end; a tail shorter than ``n * stack`` is dropped.
+    It is the yardstick, not a bit-for-bit twin: a float32 transform has no single correct rounding."""
+    n, stack = _check_long(n, stack)
+    return _long_spectra(data, n, stack)
 
 
 # -- the NumPy twins ------------------------------------------------------------------------------------
@@ -394,6 +451,91 @@ class HarmonicSearch(DeviceTaskMixin, BaseTaskBase):
             c1 = min(b, c0 + per)
             x = fetch_device(self.ih, c0, c1 - c0)
             self._plan.execute(x, c1 - c0, out[c0 - a:c1 - a])
+
+    def close(self):
+        super().close()
+        self._drop_cache()
+        if self._plan is not None:
+            self._plan.close()
+            self._plan = None
+
+
+class LongSpectra(DeviceTaskMixin, BaseTaskBase):
+    """Power spectra of ``n`` = 2^15 ... 2^22 samples of every column of a float32 stream: the whole
+    pointing in one coherent transform, where `Channelize` stops at 16384 points.
+
+    Parameters
+    ----------
+    ih : stream
+        float32 of shape ``(N,) + s`` -- usually the (time, DM) plane of `DMTrials`, `Standardize`d or
+        not.  A plane with a frequency and no sideband is taken as it is.
+    n : int
+        Samples of a transform: a power of two, 2^15 ... 2^22.
+    stack : int, optional
+        Consecutive spectra averaged into one output spectrum.  ``N >= n * stack``.
+    samples_per_frame : int, optional
+        Output spectra per frame.  Default 1.
+
+    The output is float32 ``(N // (n * stack), n // 2 + 1) + s`` at ``ih.sample_rate / (n * stack)`` from the
+    start time of ``ih``; a tail shorter than ``n * stack`` is dropped.  Per output spectrum ``m``, bin ``j`` and
+    element, ``p_q[j] = |sum_t ih[(m stack + q) n + t] exp(-2 pi i j t / n)|^2`` and ``out = (p_0 + ... +
+    p_{stack-1}) * float32(1 / stack)``, float32 adds in ascending ``q`` (no scaling for ``stack == 1``): the
+    unnormalised transform and the mean of `fluctuation_spectra`'s short route.  Bin ``j`` is fluctuation
+    frequency ``j * bin_width``, ``bin_width = ih.sample_rate / n`` in Hz (an attribute).  Metadata of ``ih``
+    describe ``s`` and are kept; no per-bin ``frequency`` is attached.  `Whiten`, `HarmonicSearch` and
+    `harmonic_candidates` take the result as it is.
+
+    How it is made (csrc/lspec_kernels.hpp): columns ``2c, 2c + 1`` are one complex stream, transformed by
+    a four-step transform ``n = n1 n2`` in two passes through a scratch of ``8 n`` bytes per column pair, and
+    untangled, detected and stacked in the second pass; the complex spectra are never stored and an odd
+    last column pairs with zeros.  A launch takes as many pairs as fit `spectra_budget`, one at least; the
+    pairing is fixed, so no value depends on the budget, on the framing or on where a read starts.  Values
+    are those of a float32 transform with twiddles from float64 tables: near `long_spectra_samples`, not
+    bit-equal to it.  Two consequences of the pairing: the rounding error of a column scales with the
+    larger of its and its partner's norm (about 1e-7 of that per bin, so a column 1000 times fainter than
+    its neighbour keeps 1e-4 of its own); and a NaN or an Inf in a column makes that column's spectrum
+    and its partner's non-finite, and changes no other column by a bit.
+
+    What it costs: the first pass of a long transform touches every sample, so the ``n * stack`` samples
+    of ALL elements behind one output spectrum are fetched in one piece: ``4 n n_elem`` bytes resident per
+    transform, 8 GiB for 2^22 x 512, beside the scratch and the output."""
+
+    #: bytes of scratch a launch may use (assignable): 8 n bytes per column pair, one pair at least
+    spectra_budget = hip.LSPEC_BUDGET
+
+    def __init__(self, ih, n, stack=1, *, samples_per_frame=1):
+        _check_plane_stream(ih, 'LongSpectra')
+        self.n, self.stack = _check_long(n, stack)
+        if ih.shape[0] < self.n * self.stack:
+            raise ValueError(f"the stream has {ih.shape[0]} samples: less than one stack of {self.stack} "
+                             f"transforms of {self.n}.")
+        rest = tuple(ih.shape[1:])
+        self._n_elem = _prod(rest)
+        if self._n_elem < 1:
+            raise ValueError("LongSpectra needs at least one element per sample.")
+        self._plan = None
+        lone = _lone_frequency(ih)
+        rate = _stream_rate(ih)
+        super().__init__(ih, shape=(ih.shape[0] // (self.n * self.stack), self.n // 2 + 1) + rest,
+                         sample_rate=rate / (self.n * self.stack), samples_per_frame=operator.index(samples_per_frame),
+                         dtype=np.float32, **(dict(sideband=1) if lone else {}))
+        if lone:
+            del self.meta['__attributes__']['sideband']
+        self.bin_width = rate / self.n
+
+    def _input_span(self, first, last):
+        a, b = self._frame_span(first, last)
+        per = self.n * self.stack
+        return (self.ih, a * per, per) if b - a == 1 else None                     # (one fetch only)
+
+    def _compute_frames(self, first, last, out):
+        if self._plan is None:
+            self._plan = hip.LongSpectraPlan(self.n, self.stack, self._n_elem)
+        a, b = self._frame_span(first, last)
+        per = self.n * self.stack
+        for m in range(a, b):
+            x = fetch_device(self.ih, m * per, per)
+            self._plan.execute(x, 1, out[m - a:m - a + 1], max(int(self.spectra_budget), 1))
 
     def close(self):
         super().close()

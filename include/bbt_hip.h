@@ -49,6 +49,7 @@ typedef struct bbt_shift_plan bbt_shift_plan;
 typedef struct bbt_dmt_plan bbt_dmt_plan;
 typedef struct bbt_sps_plan bbt_sps_plan;
 typedef struct bbt_hsum_plan bbt_hsum_plan;
+typedef struct bbt_lspec_plan bbt_lspec_plan;
 typedef struct bbt_fir_plan bbt_fir_plan;
 typedef struct bbt_r2c_plan bbt_r2c_plan;
 typedef struct bbt_gather_plan bbt_gather_plan;
@@ -625,6 +626,31 @@ int bbt_hsum_plan_create(bbt_hsum_plan** plan, int64_t nbin, int64_t n, int64_t 
 int bbt_hsum_plan_destroy(bbt_hsum_plan* plan);
 int bbt_hsum_plan_info(const bbt_hsum_plan* plan, int* width, int* split, int* rows, float* scales);
 int bbt_hsum_execute(bbt_hsum_plan* plan, const float* in_dev, int64_t n_spec, float* out_dev, bbt_stream stream);
+
+/* ---- fluctuation spectra of 2^15 ... 2^22 points (periodicity.py: LongSpectra) ----
+ * in[t][e], t < n_in samples of n_elem float32 elements, element fastest; every column e is a real
+ * stream of its own.  out[m][k][e], m < n_spec, k <= n / 2:
+ *   p_q[k][e] = | sum_t in[(m stack + q) n + t][e] exp(-2 pi i k t / n) |^2,  q < stack,
+ *   out = p_0 for stack == 1, else (p_0 + p_1 + ... + p_{stack-1}) * (float)(1 / stack): float32 adds in
+ *   ascending q, one multiply.
+ * n a power of two, 2^15 ... 2^22; stack 1 ... 2^20; n_in >= n_spec * stack * n (a tail is not read).
+ * Columns (2p, 2p + 1) are transformed as one complex stream and untangled (an odd last column pairs
+ * with zeros), by a four-step transform n = n1 n2 in two passes through a scratch the plan owns, 8 n
+ * bytes a column pair; a launch takes as many pairs as fit `budget` bytes (<= 0: 512 MiB), one at
+ * least.  All twiddles come from float64 tables.  A value depends on the samples of its own column
+ * pair only: not on the budget, and a NaN or an Inf stays within its pair.  Values are those of a
+ * float32 transform: about 1e-7 of the pair's larger rms spectrum, not bit-exact against any host
+ * transform.  Every refusal -- a null or misaligned pointer, a size out of range, no whole transform
+ * -- comes before anything is launched.  plan_info: the split n1 x n2, the columns of a first-pass
+ * and the pairs of a last-pass workgroup, its threads (BBT_LSPEC_THREADS = 256, 512 or 1024, read from
+ * the environment at every call, only changes the speed), and for `budget` the pairs of a launch and
+ * the scratch bytes.  Asynchronous on `stream`; calls on one plan must be on one stream. */
+int bbt_lspec_plan_create(bbt_lspec_plan** plan, int64_t n, int64_t stack, int64_t n_elem);
+int bbt_lspec_plan_destroy(bbt_lspec_plan* plan);
+int bbt_lspec_plan_info(const bbt_lspec_plan* plan, int64_t budget, int* n1, int* n2, int* cols, int* pairs,
+                        int* threads, int64_t* pairs_per_launch, int64_t* scratch_bytes);
+int bbt_lspec_execute(bbt_lspec_plan* plan, const float* in_dev, int64_t n_in, float* out_dev, int64_t n_spec,
+                      int64_t budget, bbt_stream stream);
 
 /* ---- real-valued streams ------------------------------------------------------
  * float32 streams run through the complex kernels (the reference's rfft/irfft
