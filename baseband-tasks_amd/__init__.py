@@ -27,7 +27,8 @@ from .search import (DMTrials, dm_trial_shifts, dm_trials_samples, Standardize, 
                      BoxcarSearch, boxcar_search_samples, boxcar_candidates)
 from . import search
 from .periodicity import (fluctuation_spectra, Whiten, whiten_samples, HarmonicSearch, harmonic_search_samples,
-                          harmonic_scales, harmonic_candidates, LongSpectra, long_spectra_samples)
+                          harmonic_scales, harmonic_candidates, LongSpectra, long_spectra_samples, Accelerate,
+                          accelerate_samples)
 from . import periodicity
 from .conversion import Real2Complex
 from .shaping import (ChangeSampleShapeBase, ChangeSampleShape, Reshape, Transpose, ReshapeAndTranspose,

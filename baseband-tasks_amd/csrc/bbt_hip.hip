@@ -37,6 +37,7 @@
 #include "sps_kernels.hpp"
 #include "hsum_kernels.hpp"
 #include "lspec_kernels.hpp"
+#include "accel_kernels.hpp"
 #include "r2c_kernels.hpp"
 #include "gather_kernels.hpp"
 #include "pack_kernels.hpp"
@@ -46,7 +47,7 @@
 
 using namespace bbt;
 
-#define BBT_VERSION 166
+#define BBT_VERSION 167
 
 // ---------------------------------------------------------------------------
 // errors
@@ -4048,6 +4049,104 @@ extern "C" int bbt_lspec_execute(bbt_lspec_plan* p, const float* in_dev, int64_t
                                    p->tw2, g, mode, scale);
             }
         }
+    HIP_TRY(hipGetLastError());
+    return 0;
+}
+
+// ---------------------------------------------------------------------------
+// acceleration trials (accel_kernels.hpp; the rule and every index are accel_geo.hpp's)
+struct bbt_accel_plan {
+    long long n = 0, n_elem = 0, n_acc = 0;
+    double k_min = 0., k_max = 0.;
+    double* factors = nullptr;       // the k_j on the device, float64
+};
+
+// BBT_ACCEL_ROUTE: 0 automatic, 1 the window wherever it fits, 2 direct.  Read at every call, for
+// measuring and for the tests that walk the routes; no value of the output depends on it.
+static int accel_env_route() { return dmt_env("BBT_ACCEL_ROUTE", {1, 2}); }
+
+extern "C" int bbt_accel_plan_destroy(bbt_accel_plan* p) {
+    if (!p) return 0;
+    if (p->factors) (void)hipFree(p->factors);
+    delete p;
+    return 0;
+}
+
+extern "C" int bbt_accel_plan_create(bbt_accel_plan** plan, int64_t n, int64_t n_elem, const double* factors_host,
+                                     int64_t n_acc) {
+    ARG_TRY(plan && factors_host, "bbt_accel_plan_create: null argument");
+    *plan = nullptr;
+    const char* err = accel_sizes(n, n_elem, n_acc);
+    ARG_TRY(!err, "bbt_accel_plan_create: %s (n=%lld, n_elem=%lld, n_acc=%lld)", err ? err : "", (long long)n,
+            (long long)n_elem, (long long)n_acc);
+    double k_min = factors_host[0], k_max = factors_host[0];
+    for (int64_t j = 0; j < n_acc; ++j) {
+        const double k = factors_host[j];
+        ARG_TRY(accel_factor_ok(n, k), "bbt_accel_plan_create: factor %lld, %g, is beyond |k| n <= 1/4 (n=%lld)",
+                (long long)j, k, (long long)n);
+        k_min = k < k_min ? k : k_min, k_max = k > k_max ? k : k_max;
+    }
+    bbt_accel_plan* p = new bbt_accel_plan;
+    p->n = n, p->n_elem = n_elem, p->n_acc = n_acc, p->k_min = k_min, p->k_max = k_max;
+    if (hipMalloc((void**)&p->factors, (size_t)n_acc * sizeof(double)) != hipSuccess ||
+        hipMemcpy(p->factors, factors_host, (size_t)n_acc * sizeof(double), hipMemcpyHostToDevice) != hipSuccess) {
+        (void)hipGetLastError();
+        bbt_accel_plan_destroy(p);
+        ARG_TRY(false, "bbt_accel_plan_create: no device table of %lld factors", (long long)n_acc);
+    }
+    *plan = p;
+    return 0;
+}
+
+// For output rows [out_first, out_first + n_out): the route a launch takes now (1: the window wherever it
+// fits, 2: direct), the rows of a tile, the LDS bytes the window kernel declares, the input rows the run
+// needs (first, count) and whether that window, taken as one tile, would fit the LDS.
+extern "C" int bbt_accel_plan_info(const bbt_accel_plan* p, int64_t out_first, int64_t n_out, int* route, int* rows,
+                                   int64_t* lds_bytes, int64_t* win_first, int64_t* win_rows, int* fits) {
+    ARG_TRY(p, "bbt_accel_plan_info: null argument");
+    ARG_TRY(out_first >= 0 && n_out >= 1, "bbt_accel_plan_info: no rows");
+    ARG_TRY(n_out <= BBT_ACCEL_MAX_VALUES && out_first <= BBT_ACCEL_MAX_VALUES - n_out,
+            "bbt_accel_plan_info: rows beyond 2^40");
+    long long lo, hi;
+    accel_window(p->n, p->k_min, p->k_max, out_first, out_first + n_out - 1, &lo, &hi);
+    AccelGeo g = {};
+    const char* err = accel_geo(p->n, p->n_elem, p->n_acc, 4, p->k_min, p->k_max, lo, hi - lo + 1, out_first, n_out, &g);
+    ARG_TRY(!err, "bbt_accel_plan_info: %s", err ? err : "");
+    if (route) *route = accel_route(accel_env_route(), g);
+    if (rows) *rows = g.rows;
+    if (lds_bytes) *lds_bytes = BBT_ACCEL_LDS_BYTES;
+    if (win_first) *win_first = lo;
+    if (win_rows) *win_rows = hi - lo + 1;
+    if (fits) *fits = (hi - lo + 1) * p->n_elem * 4 <= BBT_ACCEL_LDS_BYTES;
+    return 0;
+}
+
+// out[g - out_first][j][e] = in[q n + src(i, j) - in_first][e] for the global rows g = q n + i of
+// [out_first, out_first + n_out); in_dev holds global rows [in_first, in_first + n_in)
+extern "C" int bbt_accel_execute(bbt_accel_plan* p, const float* in_dev, int64_t in_first, int64_t n_in,
+                                 float* out_dev, int64_t out_first, int64_t n_out, bbt_stream stream) {
+    ARG_TRY(p && in_dev && out_dev, "bbt_accel_execute: null argument");
+    ARG_TRY((((uintptr_t)in_dev | (uintptr_t)out_dev) & 3) == 0, "bbt_accel_execute: arrays must be 4-byte aligned");
+    const bool wide = p->n_elem % 4 == 0 && (((uintptr_t)in_dev | (uintptr_t)out_dev) & 15) == 0;
+    AccelGeo g = {};
+    const char* err = accel_geo(p->n, p->n_elem, p->n_acc, wide ? 16 : 4, p->k_min, p->k_max, in_first, n_in,
+                                out_first, n_out, &g);
+    ARG_TRY(!err, "bbt_accel_execute: %s (rows %lld + %lld from a piece %lld + %lld, n=%lld)", err ? err : "",
+            (long long)out_first, (long long)n_out, (long long)in_first, (long long)n_in, p->n);
+    const int route = accel_route(accel_env_route(), g);
+    hipStream_t st = (hipStream_t)stream;
+    const dim3 grid((unsigned)g.n_tile, (unsigned)g.n_seg), block(BBT_ACCEL_THREADS);
+    if (wide) {
+        const uint4* x = (const uint4*)in_dev;
+        uint4* o = (uint4*)out_dev;
+        if (route == 1) hipLaunchKernelGGL((k_accel<uint4, true>), grid, block, 0, st, x, o, p->factors, g);
+        else hipLaunchKernelGGL((k_accel<uint4, false>), grid, block, 0, st, x, o, p->factors, g);
+    } else {
+        const unsigned* x = (const unsigned*)in_dev;
+        unsigned* o = (unsigned*)out_dev;
+        if (route == 1) hipLaunchKernelGGL((k_accel<unsigned, true>), grid, block, 0, st, x, o, p->factors, g);
+        else hipLaunchKernelGGL((k_accel<unsigned, false>), grid, block, 0, st, x, o, p->factors, g);
+    }
     HIP_TRY(hipGetLastError());
     return 0;
 }

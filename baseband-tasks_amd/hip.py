@@ -128,6 +128,10 @@ SIGNATURES = {
     'bbt_lspec_plan_info': [_vp, _i64, C.POINTER(_int), C.POINTER(_int), C.POINTER(_int), C.POINTER(_int),
                             C.POINTER(_int), _pi64, _pi64],
     'bbt_lspec_execute': [_vp, _vp, _i64, _vp, _i64, _i64, _vp],
+    'bbt_accel_plan_create': [_pvp, _i64, _i64, C.POINTER(C.c_double), _i64],
+    'bbt_accel_plan_destroy': [_vp],
+    'bbt_accel_plan_info': [_vp, _i64, _i64, C.POINTER(_int), C.POINTER(_int), _pi64, _pi64, _pi64, C.POINTER(_int)],
+    'bbt_accel_execute': [_vp, _vp, _i64, _i64, _vp, _i64, _i64, _vp],
     'bbt_fir_plan_create': [_pvp, _int, _int, _vp],
     'bbt_fir_plan_destroy': [_vp],
     'bbt_fir_execute': [_vp, _vp, _vp, _i64, _vp],
@@ -162,7 +166,7 @@ SIGNATURES = {
 }
 
 #: oldest libbbt_hip.so whose entry points and argument meanings this binding assumes
-MIN_LIB_VERSION = 166
+MIN_LIB_VERSION = 167
 
 _lib = None
 _lock = threading.Lock()
@@ -1863,6 +1867,58 @@ class LongSpectraPlan(_Plan):
                              "n_spec * (n // 2 + 1) * n_elem values are needed, n_spec >= 1")
         check(lib().bbt_lspec_execute(self._h, in_dev.ptr_to_read(), in_dev.size // self.n_elem, out_dev.ptr, n_spec,
                                       int(budget), _stream))
+
+
+#: bounds of the acceleration trials (csrc/accel_geo.hpp)
+ACCEL_MIN_N, ACCEL_MAX_N, ACCEL_MAX_TRIALS, ACCEL_BUDGET = 2, 1 << 24, 4096, 1 << 29
+ACCEL_LDS_BYTES, ACCEL_TILE_UNITS, ACCEL_MAX_ROWS, ACCEL_MAX_WIDTH = 32768, 16384, 256, 1 << 28
+
+
+class AccelPlan(_Plan):
+    """out[q n + i, j, e] = in[q n + i + rint(k_j * float64(i * (i - n))), e]: every block of ``n`` rows of a
+    float32 stream resampled along a parabola for each of the float64 ``factors`` k_j, ``|k_j| n <= 1/4``, the
+    32 bits copied (bbt_accel_* in include/bbt_hip.h; `periodicity.accelerate_samples` is the NumPy twin)."""
+    _destroy = 'bbt_accel_plan_destroy'
+
+    def __init__(self, n, n_elem, factors):
+        super().__init__()
+        self.n, self.n_elem = int(n), int(n_elem)
+        factors = np.ascontiguousarray(factors, dtype=np.float64)
+        if factors.ndim != 1:
+            raise ValueError("AccelPlan: factors must be a 1-D sequence of float64")
+        self.factors = factors
+        self.n_acc = factors.shape[0]
+        check(lib().bbt_accel_plan_create(C.byref(self._h), self.n, self.n_elem,
+                                          factors.ctypes.data_as(C.POINTER(C.c_double)), self.n_acc))
+
+    def info(self, out_first=0, n_out=1):
+        """For output rows ``[out_first, out_first + n_out)``: the route a launch takes now (BBT_ACCEL_ROUTE;
+        1: the window wherever it fits, 2: direct), the rows of a tile, the LDS bytes the window kernel
+        declares, the input rows the run needs and whether they would fit that LDS as one tile."""
+        route, rows, fits = _int(0), _int(0), _int(0)
+        lds, first, count = _i64(0), _i64(0), _i64(0)
+        check(lib().bbt_accel_plan_info(self._h, int(out_first), int(n_out), C.byref(route), C.byref(rows),
+                                        C.byref(lds), C.byref(first), C.byref(count), C.byref(fits)))
+        return dict(route=route.value, rows=rows.value, lds_bytes=lds.value, window_first=first.value,
+                    window_rows=count.value, fits=bool(fits.value))
+
+    def execute(self, in_dev, in_first, n_in, out_dev, out_first, n_out, n_rows=None):
+        """``in_dev``: float32, at least ``n_in * n_elem`` values, global rows ``[in_first, in_first + n_in)`` of
+        the stream; ``out_dev``: float32, at least ``n_out * n_acc * n_elem``, for global rows ``[out_first,
+        out_first + n_out)``.  ``n_rows``: the length of the stream, if known: rows beyond its last whole block
+        are refused."""
+        in_first, n_in, out_first, n_out = int(in_first), int(n_in), int(out_first), int(n_out)
+        if in_dev.dtype != np.float32 or out_dev.dtype != np.float32:
+            raise TypeError("AccelPlan.execute: float32 DeviceArrays are needed")
+        if (n_in < 1 or n_out < 1 or in_first < 0 or out_first < 0 or in_dev.size < n_in * self.n_elem
+                or out_dev.size < n_out * self.n_acc * self.n_elem):
+            raise ValueError("AccelPlan.execute: float32 DeviceArrays of n_in * n_elem and n_out * n_acc * n_elem "
+                             "values are needed, n_in >= 1, n_out >= 1")
+        if n_rows is not None and out_first + n_out > int(n_rows) // self.n * self.n:
+            raise ValueError(f"AccelPlan.execute: rows {out_first} ... {out_first + n_out - 1} run beyond the last "
+                             f"whole block of {self.n} of a stream of {n_rows}")
+        check(lib().bbt_accel_execute(self._h, in_dev.ptr_to_read(), in_first, n_in, out_dev.ptr, out_first, n_out,
+                                      _stream))
 
 
 COMM_ID_BYTES = 128

@@ -10,7 +10,12 @@ is one float64 sum in a fixed two-level order; a harmonic sum is ONE float32 acc
 harmonic, the gathered bins added in a fixed order; the winner of a block is the maximum of a total
 order.  So every value has one correct bit pattern, whatever the tiling or the chunking.  `LongSpectra`
 is the exception: a float32 transform has no single correct rounding, so `long_spectra_samples` is a
-float64 yardstick its values are near, and what is exact is that they do not depend on the chunking."""
+float64 yardstick its values are near, and what is exact is that they do not depend on the chunking.
+
+For pulsars in binaries `Accelerate` goes in front of the spectra: per trial acceleration every block of the
+time series is resampled along a parabola, nearest sample, by one integer rule (`accelerate_rows`; the twin is
+`accelerate_samples`, csrc/accel_kernels.hpp computes it), and `acceleration_candidates` takes the maxima over
+(block, acceleration, trial)."""
 import operator
 
 import numpy as np
@@ -22,10 +27,11 @@ from .fourier import check_transform_length
 from .device_task import DeviceTaskMixin, fetch_device
 from .functions import Square
 from .integration import Integrate
-from .search import _check_plane_stream, _local_maxima, _lone_frequency, _prod
+from .search import _check_plane, _check_plane_stream, _local_maxima, _local_maxima_3d, _lone_frequency, _prod
 
 __all__ = ['fluctuation_spectra', 'LongSpectra', 'long_spectra_samples', 'Whiten', 'whiten_samples', 'HarmonicSearch', 'harmonic_search_samples',
-           'harmonic_scales', 'harmonic_candidates', 'SNR', 'OFFSET', 'LEVEL']
+           'harmonic_scales', 'harmonic_candidates', 'Accelerate', 'accelerate_samples', 'accelerate_rows',
+           'acceleration_factors', 'acceleration_grid', 'acceleration_candidates', 'SNR', 'OFFSET', 'LEVEL']
 
 #: rows of `HarmonicSearch`'s output: the best S/N of a block, its top harmonic's bin relative to the
 #: block, its level L (2^L harmonics)
@@ -290,6 +296,138 @@ def harmonic_candidates(best, n, threshold, bin_width=None):
     return out[np.lexsort((out['trial'], out['bin'], -out['snr'].astype(np.float64)))]
 
 
+# -- acceleration trials: the rule in NumPy ------------------------------------------------------------------
+#: the speed of light, m / s
+C_LIGHT = 299792458.
+ACCEL_MIN_N, ACCEL_MAX_N, ACCEL_MAX_TRIALS = hip.ACCEL_MIN_N, hip.ACCEL_MAX_N, hip.ACCEL_MAX_TRIALS
+
+
+def acceleration_factors(accelerations, sample_rate):
+    """``k_j = a_j / (2. * 299792458. * sample_rate)``, float64, evaluated in exactly this order:
+    ``accelerations`` in m / s^2 and ``sample_rate`` in Hz give the factors of `accelerate_rows` in 1 / sample."""
+    a = np.array(accelerations, dtype=np.float64, ndmin=1)
+    if a.ndim != 1 or not 1 <= a.shape[0] <= ACCEL_MAX_TRIALS:
+        raise ValueError(f"the trial accelerations must be a 1-D sequence of 1 ... {ACCEL_MAX_TRIALS} values.")
+    if not np.all(np.isfinite(a)):
+        raise ValueError("the trial accelerations must be finite.")
+    rate = float(sample_rate)
+    if not (np.isfinite(rate) and rate > 0.):
+        raise ValueError(f"the sample rate must be positive and finite, not {sample_rate}.")
+    return a / (2. * C_LIGHT * rate)
+
+
+def _check_accel(n, factors):
+    n = operator.index(n)
+    if not ACCEL_MIN_N <= n <= ACCEL_MAX_N:
+        raise ValueError(f"a block of Accelerate must have {ACCEL_MIN_N} ... 2^24 samples, not {n}.")
+    k = np.array(factors, dtype=np.float64, ndmin=1)
+    if k.ndim != 1 or not 1 <= k.shape[0] <= ACCEL_MAX_TRIALS:
+        raise ValueError(f"there must be 1 ... {ACCEL_MAX_TRIALS} trials in a 1-D sequence.")
+    bad = ~np.isfinite(k) | ~(np.abs(k) * np.float64(n) <= .25)
+    if bad.any():
+        j = int(np.argmax(bad))
+        raise ValueError(f"trial {j}: the factor {k[j]} is beyond |k| n <= 1/4 for n = {n} (|a| T / 2c <= 1/4).")
+    return n, k
+
+
+def _accel_src(n, k, i):
+    """The rule for one row: python ints and one float64 product."""
+    return i + int(np.rint(np.float64(k) * np.float64(i * (i - n))))
+
+
+def _accel_window(n, k_min, k_max, g0, g1):
+    """The input rows ``[lo, hi]`` (global, inclusive) that output rows ``g0 <= g1`` need over all trials."""
+    q0, q1 = g0 // n, g1 // n
+    return q0 * n + _accel_src(n, k_max, g0 - q0 * n), q1 * n + _accel_src(n, k_min, g1 - q1 * n)
+
+
+def accelerate_rows(n, factors):
+    """The input row of every output row of a block: int64 ``(A, n)`` ::
+
+        src[j, i] = i + int64(rint(factors[j] * float64(i * (i - n))))
+
+    ``i * (i - n)`` in int64 (exact), ONE float64 multiply, round half to even, an integer add.  The parabola
+    is zero at both ends of the block.  ``|factors[j]| * n <= 1/4`` or ``ValueError``: then ``src`` stays in ``[0,
+    n - 1]``, does not decrease with ``i``, steps by 0, 1 or 2, and for a fixed ``i`` does not increase with the
+    factor."""
+    n, k = _check_accel(n, factors)
+    i = np.arange(n, dtype=np.int64)
+    p = (i * (i - n)).astype(np.float64)
+    return i + np.rint(k[:, np.newaxis] * p).astype(np.int64)
+
+
+def accelerate_samples(data, factors, n):
+    """NumPy twin of `Accelerate`, bit for bit: float32 ``data`` of shape ``(N,) + s`` gives float32 ``(N // n *
+    n, A) + s`` with ``out[q n + i, j] = data[q n + accelerate_rows(n, factors)[j, i]]``, the 32 bits copied; a
+    tail shorter than ``n`` is dropped."""
+    data = _check_plane(data, 'accelerate_samples')
+    src = accelerate_rows(n, factors)
+    n = src.shape[1]
+    nb = data.shape[0] // n
+    if nb < 1:
+        raise ValueError(f"{data.shape[0]} samples are less than one block of {n}.")
+    bits = np.ascontiguousarray(data[:nb * n]).view(np.uint32).reshape((nb, n) + data.shape[1:])
+    out = bits[:, src.T]                                         # (nb, n, A) + s
+    return out.reshape((nb * n, src.shape[0]) + data.shape[1:]).view(np.float32)
+
+
+def acceleration_grid(a_max, n, sample_rate, tol=1.):
+    """The symmetric grid of trial accelerations ``j * da``, ``|j| <= ceil(a_max / da)``, with ``da = 8 c
+    sample_rate tol / n^2`` (m / s^2): neighbouring trials then differ by ``tol`` samples in the middle of a
+    block of ``n``, as ``dk n^2 / 4 = tol``.  ``ValueError`` if that is more than 4096 trials."""
+    n = operator.index(n)
+    a_max, rate, tol = float(a_max), float(sample_rate), float(tol)
+    if not (ACCEL_MIN_N <= n <= ACCEL_MAX_N and np.isfinite(a_max) and a_max >= 0. and np.isfinite(rate) and rate > 0.
+            and np.isfinite(tol) and tol > 0.):
+        raise ValueError("acceleration_grid needs n = 2 ... 2^24, a_max >= 0, sample_rate > 0 and tol > 0.")
+    step = 8. * C_LIGHT * rate * tol / (float(n) * float(n))
+    reach = int(np.ceil(a_max / step))
+    if 2 * reach + 1 > ACCEL_MAX_TRIALS:
+        raise ValueError(f"{2 * reach + 1} trials of {step} m/s^2 up to {a_max}: more than {ACCEL_MAX_TRIALS}.")
+    return np.arange(-reach, reach + 1, dtype=np.float64) * step
+
+
+def acceleration_candidates(best, n, threshold, bin_width=None, accelerations=None):
+    """The local maxima of one spectrum's `HarmonicSearch` result over acceleration trials (host, NumPy).
+
+    ``best``: ``(blocks, 3, A, ndm)``, one sample as read from ``HarmonicSearch(... Accelerate(plane, ...) ...,
+    n, ...)``.  A cell ``(b, a, d)`` is a candidate if its S/N is ``>= threshold``, none of its up to 26
+    neighbours in (block, acceleration, trial) has a larger S/N, and no neighbour with an equal S/N comes
+    before it in ``(b, a, d)`` raster order: the rule of `harmonic_candidates` with one more axis.  Returns a
+    structured array with the fields of `harmonic_candidates` -- ``bin``, ``trial``, ``harmonics``, ``snr`` and, if
+    ``bin_width`` (Hz) is given, ``frequency`` -- then ``acc``, the index of the acceleration trial, and, if
+    ``accelerations`` (the ``A`` trial values) are given, ``acceleration``; sorted by descending ``snr``, then
+    ``bin``, then ``acc``, then ``trial``.  Nothing is merged across trials or harmonics."""
+    best = np.asarray(best)
+    n = _check_search(n, 1)[0]
+    if best.ndim != 4 or best.shape[1] != 3:
+        raise ValueError(f"best must be (blocks, 3, A, ndm), one sample of HarmonicSearch, not {best.shape}.")
+    if accelerations is not None:
+        accelerations = np.asarray(accelerations, dtype=np.float64)
+        if accelerations.shape != (best.shape[2],):
+            raise ValueError(f"{best.shape[2]} trials need as many accelerations, not {accelerations.shape}.")
+    snr = best[:, SNR].astype(np.float32)
+    b, a, d = _local_maxima_3d(snr, threshold)
+    fields = [('bin', np.float64), ('trial', np.int64), ('harmonics', np.int64), ('snr', np.float32)]
+    if bin_width is not None:
+        fields.append(('frequency', np.float64))
+    fields.append(('acc', np.int64))
+    if accelerations is not None:
+        fields.append(('acceleration', np.float64))
+    out = np.empty(b.shape[0], np.dtype(fields))
+    harmonics = np.int64(1) << best[b, LEVEL, a, d].astype(np.int64)
+    out['bin'] = (b * n + best[b, OFFSET, a, d].astype(np.int64)) / harmonics
+    out['trial'] = d
+    out['harmonics'] = harmonics
+    out['snr'] = snr[b, a, d]
+    if bin_width is not None:
+        out['frequency'] = out['bin'] * float(bin_width)
+    out['acc'] = a
+    if accelerations is not None:
+        out['acceleration'] = accelerations[a]
+    return out[np.lexsort((out['trial'], out['acc'], out['bin'], -out['snr'].astype(np.float64)))]
+
+
 # -- the tasks ------------------------------------------------------------------------------------------
 def _check_spectra_stream(ih, who):
     _check_plane_stream(ih, who)
@@ -536,6 +674,114 @@ class LongSpectra(DeviceTaskMixin, BaseTaskBase):
         for m in range(a, b):
             x = fetch_device(self.ih, m * per, per)
             self._plan.execute(x, 1, out[m - a:m - a + 1], max(int(self.spectra_budget), 1))
+
+    def close(self):
+        super().close()
+        self._drop_cache()
+        if self._plan is not None:
+            self._plan.close()
+            self._plan = None
+
+
+class Accelerate(DeviceTaskMixin, BaseTaskBase):
+    """Acceleration trials: resample every block of ``n`` samples of a dedispersed time series along a
+    parabola, once per trial acceleration, so that a pulsar whose apparent spin frequency drifts at that
+    rate -- one in a binary -- becomes strictly periodic and `LongSpectra`, `Whiten` and `HarmonicSearch`
+    find it as they are.
+
+    Parameters
+    ----------
+    ih : stream
+        float32 of shape ``(N,) + s`` with at least one element per sample -- usually a slice of the
+        standardized (time, DM) plane.  A plane with a frequency and no sideband is taken as it is.
+    accelerations : sequence of float
+        The ``A`` trial line-of-sight accelerations in m / s^2, 1 ... 4096 of them, finite: any order, any
+        sign, repeats allowed (`acceleration_grid` makes a grid).
+    n : int
+        Samples of a block, 2 ... 2^24, counted from sample 0 of ``ih``, not necessarily a power of two:
+        the coherent transform of the `LongSpectra` that follows.  ``N >= n``.
+    samples_per_frame : int, optional
+        Of the output.  Default: that of ``ih``, at most the length of the output.
+
+    The output is float32 ``(N // n * n, A) + s`` at the sample rate and start time of ``ih``; a tail
+    shorter than ``n`` is dropped, as `LongSpectra` drops it.  With ``factors = acceleration_factors(
+    accelerations, ih.sample_rate)``, that is ``k_j = a_j / (2 c sample_rate)`` in float64, row ``q n + i`` of
+    trial ``j`` is ::
+
+        out[q n + i, j] = ih[q n + i + int64(rint(k_j * float64(i * (i - n))))]
+
+    -- ``i (i - n)`` in integers, one float64 multiply, round half to even, an integer add -- the 32 bits
+    copied, NaN payloads and -0 included: `accelerate_rows` is the table and `accelerate_samples` the twin,
+    bit for bit.  The parabola is zero at both ends of a block, so blocks do not mix and a trial of 0 is the
+    identity.  Sign: a trial ``a > 0`` makes periodic a signal whose apparent frequency falls as ``f(t) = f0 (1 -
+    a (t - T / 2) / c)`` over a block of length ``T``.  It is a nearest-sample resampling, on purpose: that keeps
+    the stage exact.  Every trial must satisfy ``|k_j| n <= 1/4`` (``|a| T / 2c <= 1/4``: far beyond any binary)
+    or the task raises ``ValueError``; under that bound the source row stays inside the block, never steps
+    back, and moves at most ``n / 16`` rows -- ``max_shift`` is the largest move of this task.  Metadata of
+    ``ih`` describe ``s`` and are kept; they broadcast over the new trial axis.  Attributes: ``accelerations``,
+    ``factors``, ``n``, ``max_shift``.
+
+    What it costs: the output is ``A`` times the input, and `LongSpectra` behind it holds ``4 n A n_elem`` bytes
+    per transform -- 8.6 GB for 2^22 samples x 64 trials x 8 DMs.  So give it a slice of the plane, the DMs
+    that are worth it: ``bt.Accelerate(bt.Standardize(plane, 4096)[:, 40:48], accs, n)``.  A chunk of
+    `accel_budget` output bytes fetches only the input rows its own window needs -- for rows ``i0 ... i1`` of a
+    block, ``[src(i0, k_max), src(i1, k_min)]`` -- and one kernel (csrc/accel_kernels.hpp) writes every output
+    row as one contiguous run.  No value depends on the budget, on the framing or on a seek."""
+
+    #: output bytes at most per `fetch_device` call and launch (assignable); a chunk is a whole number
+    #: of rows, one at least
+    accel_budget = hip.ACCEL_BUDGET
+
+    def __init__(self, ih, accelerations, n, *, samples_per_frame=None):
+        _check_plane_stream(ih, 'Accelerate')
+        self.accelerations = np.array(accelerations, dtype=np.float64, ndmin=1)
+        factors = acceleration_factors(self.accelerations, _stream_rate(ih))
+        self.n, self.factors = _check_accel(n, factors)
+        n = self.n
+        if ih.shape[0] < n:
+            raise ValueError(f"the stream has {ih.shape[0]} samples: less than one block of {n}.")
+        rest = tuple(ih.shape[1:])
+        self._n_elem = _prod(rest)
+        if self._n_elem < 1:
+            raise ValueError("Accelerate needs at least one element per sample.")
+        if self._n_elem * len(self.factors) > hip.ACCEL_MAX_WIDTH:
+            raise ValueError(f"an output sample of {len(self.factors)} trials x {self._n_elem} elements has more "
+                             f"than 2^28 values.")
+        self._k_min, self._k_max = float(self.factors.min()), float(self.factors.max())
+        mid = n // 2
+        self.max_shift = int(np.rint(np.abs(self.factors).max() * np.float64(mid * (n - mid))))
+        length = ih.shape[0] // n * n
+        if samples_per_frame is None:
+            samples_per_frame = max(min(operator.index(ih.samples_per_frame), length), 1)
+        self._plan = None
+        lone = _lone_frequency(ih)
+        super().__init__(ih, shape=(length, len(self.factors)) + rest, samples_per_frame=operator.index(samples_per_frame),
+                         dtype=np.float32, **(dict(sideband=1) if lone else {}))
+        if lone:
+            del self.meta['__attributes__']['sideband']
+
+    def _chunk_rows(self):
+        return max(1, int(self.accel_budget) // (4 * len(self.factors) * self._n_elem))
+
+    def _window(self, c0, c1):
+        """The input samples output rows [c0, c1) need: (first, count)."""
+        lo, hi = _accel_window(self.n, self._k_min, self._k_max, c0, c1 - 1)
+        return lo, hi + 1 - lo
+
+    def _input_span(self, first, last):
+        a, b = self._frame_span(first, last)
+        return (self.ih,) + self._window(a, b) if b - a <= self._chunk_rows() else None      # (one fetch only)
+
+    def _compute_frames(self, first, last, out):
+        if self._plan is None:
+            self._plan = hip.AccelPlan(self.n, self._n_elem, self.factors)
+        a, b = self._frame_span(first, last)
+        per = self._chunk_rows()
+        for c0 in range(a, b, per):
+            c1 = min(b, c0 + per)
+            start, n_in = self._window(c0, c1)
+            x = fetch_device(self.ih, start, n_in)
+            self._plan.execute(x, start, n_in, out[c0 - a:c1 - a], c0, c1 - c0, n_rows=self.shape[0])
 
     def close(self):
         super().close()

@@ -380,6 +380,26 @@ def _local_maxima(snr, threshold):
     return np.nonzero(keep)
 
 
+def _local_maxima_3d(snr, threshold):
+    """`_local_maxima` for a float32 cube ``snr`` of cells ``(b, a, d)``: ``>= threshold``, no larger value
+    among the up to 26 neighbours and no equal one before the cell in raster order: three index arrays."""
+    nb, na, nd = snr.shape
+    padded = np.full((nb + 2, na + 2, nd + 2), np.nan, np.float32)     # (a NaN compares False: no neighbour)
+    padded[1:-1, 1:-1, 1:-1] = snr
+    with np.errstate(invalid='ignore'):
+        keep = snr >= np.float32(threshold)
+        for db in (-1, 0, 1):
+            for da in (-1, 0, 1):
+                for dd in (-1, 0, 1):
+                    if db == 0 and da == 0 and dd == 0:
+                        continue
+                    other = padded[1 + db:1 + db + nb, 1 + da:1 + da + na, 1 + dd:1 + dd + nd]
+                    keep &= ~(other > snr)
+                    if (db, da, dd) < (0, 0, 0):
+                        keep &= ~(other == snr)
+    return np.nonzero(keep)
+
+
 def boxcar_candidates(best, n, threshold):
     """The local maxima of a `BoxcarSearch` result above a threshold (host, NumPy).
 

@@ -50,6 +50,7 @@ typedef struct bbt_dmt_plan bbt_dmt_plan;
 typedef struct bbt_sps_plan bbt_sps_plan;
 typedef struct bbt_hsum_plan bbt_hsum_plan;
 typedef struct bbt_lspec_plan bbt_lspec_plan;
+typedef struct bbt_accel_plan bbt_accel_plan;
 typedef struct bbt_fir_plan bbt_fir_plan;
 typedef struct bbt_r2c_plan bbt_r2c_plan;
 typedef struct bbt_gather_plan bbt_gather_plan;
@@ -651,6 +652,34 @@ int bbt_lspec_plan_info(const bbt_lspec_plan* plan, int64_t budget, int* n1, int
                         int* threads, int64_t* pairs_per_launch, int64_t* scratch_bytes);
 int bbt_lspec_execute(bbt_lspec_plan* plan, const float* in_dev, int64_t n_in, float* out_dev, int64_t n_spec,
                       int64_t budget, bbt_stream stream);
+
+/* ---- acceleration trials --------------------------------------------------------
+ * A float32 stream x[t][e], e < n_elem, cut into blocks of n rows, t = q n + i, is resampled along a
+ * parabola for each of n_acc trial factors k_j (float64: a_j / (2 c rate), made by the caller):
+ *   out[q n + i][j][e] = x[q n + src(i, j)][e],  src(i, j) = i + (int64)rint(k_j * (double)(i * (i - n))),
+ * i (i - n) in 64-bit integers, ONE double multiply, round half to even, an integer add; the 32 bits
+ * are copied (periodicity.accelerate_samples is the NumPy twin, to the bit).  n is 2 ... 2^24, n_acc 1
+ * ... 4096, n_elem >= 1 with n_acc n_elem <= 2^28, and every factor is finite with |k| n <= 1/4: then src
+ * stays in [0, n - 1], does not decrease with i and does not increase with k, so output rows g0 ... g1
+ * need exactly the input rows [q0 n + src(i0, k_max), q1 n + src(i1, k_min)].  execute takes output rows
+ * [out_first, out_first + n_out) (global row numbers) into out_dev from a piece in_dev that holds input
+ * rows [in_first, in_first + n_in), which must cover that window; a call may start and end inside a
+ * block.  No value depends on how a stream is cut into calls.  One kernel, two routes over one index
+ * map: the window of a tile of rows staged in LDS where it fits, or read from global memory;
+ * BBT_ACCEL_ROUTE (0 automatic, 1 the window wherever it fits, 2 direct; read from the environment at
+ * every call) only changes the speed.  16-byte moves are used when n_elem % 4 == 0 and both arrays are
+ * 16-byte aligned.  Every refusal -- a null or misaligned pointer, a size out of range, a factor beyond
+ * the bound, a piece that does not cover the window -- comes before anything is launched.  plan_info,
+ * for a run of output rows: the route a launch takes (1 or 2), the rows of a tile, the LDS bytes the
+ * window kernel declares, the input rows the run needs (first, count) and whether they would fit that
+ * LDS as one tile.  Asynchronous on `stream`. */
+int bbt_accel_plan_create(bbt_accel_plan** plan, int64_t n, int64_t n_elem, const double* factors_host,
+                          int64_t n_acc);
+int bbt_accel_plan_destroy(bbt_accel_plan* plan);
+int bbt_accel_plan_info(const bbt_accel_plan* plan, int64_t out_first, int64_t n_out, int* route, int* rows,
+                        int64_t* lds_bytes, int64_t* win_first, int64_t* win_rows, int* fits);
+int bbt_accel_execute(bbt_accel_plan* plan, const float* in_dev, int64_t in_first, int64_t n_in, float* out_dev,
+                      int64_t out_first, int64_t n_out, bbt_stream stream);
 
 /* ---- real-valued streams ------------------------------------------------------
  * float32 streams run through the complex kernels (the reference's rfft/irfft
