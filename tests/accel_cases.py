@@ -25,7 +25,11 @@ def _k(values):
 #: the smallest block; a tail that is dropped and a row count that is no multiple of a tile; a block
 #: length that is no power of two, with ties; ties of both signs on the 16-byte path (8 elements); ties
 #: that round both ways; scalar samples (rows narrower than a wavefront); a row wider than a workgroup;
-#: more trials than lanes; shifts of 2048 rows, which no LDS window holds
+#: more trials than lanes; shifts of 2048 rows, which no LDS window holds; and the rows wider than a tile
+#: (csrc/accel_geo.hpp: BBT_ACCEL_TILE_UNITS = 16384 units of 4 or of 16 bytes), two blocks of 32 rows and a
+#: dropped tail each: 127 x 130 = 16510 four-byte units, cut into a whole segment and one of 126 units,
+#: narrower than a workgroup; 1025 x 64 = 16400 units of 16, cut in two (from arrays that are not 16-byte
+#: aligned, 65600 units of 4 in five); and the fence post, 1024 x 64 = exactly 16384 units of 16, one segment
 CASES = [
     Case('n2', 2, 5, (1,), _k([0., .125, -.125])),
     Case('n64', 64, 3 * 64 + 17, (3,), _k(np.linspace(-1., 1., 5) / 256.)),
@@ -36,7 +40,13 @@ CASES = [
     Case('n256_wide', 256, 259, (300,), _k([1. / 1024., 0., -3e-4])),
     Case('n128_trials', 128, 256, (3,), _k(np.linspace(-1., 1., 129) / 512.)),
     Case('n32768_far', 1 << 15, 1 << 15, (6,), _k(np.linspace(-1., 1., 7) / float(1 << 17))),
+    Case('seg_scalar', 32, 2 * 32 + 5, (130,), _k(np.linspace(-1., 1., 127) / 128.)),
+    Case('seg_wide', 32, 2 * 32 + 5, (64,), _k(np.linspace(-1., 1., 1025) / 128.)),
+    Case('one_seg_wide', 32, 2 * 32 + 5, (64,), _k(np.linspace(-1., 1., 1024) / 128.)),
 ]
+#: the cases whose rows are cut into segments whatever the alignment, and the one that just is not
+SEGMENTED, FENCE_POST = ('seg_scalar', 'seg_wide'), 'one_seg_wide'
+TILE_UNITS = 16384
 IDS = [c.name for c in CASES]
 
 
@@ -169,6 +179,16 @@ assert len(ties(512, 2. ** -11)) == 8 and len(ties(512, -2. ** -11)) == 8
 assert sorted(up for _, up in ties(1000, -2. ** -12)) == [False, False, True, True]
 assert {up for _, up in ties(512, 2. ** -11)} | {up for _, up in ties(512, -2. ** -11)} == {False, True}
 assert len(ties(500, 2. ** -11)) > 0
+# the rows wider than a tile: the widths they are named for, and extreme trials that really move rows
+for _name, _n_acc, _n_elem in (('seg_scalar', 127, 130), ('seg_wide', 1025, 64), ('one_seg_wide', 1024, 64)):
+    _case = by_name(_name)
+    assert (len(_case.factors), _case.shape) == (_n_acc, (_n_elem,)) and _case.length // _case.n == 2 < _case.length / _case.n
+    assert -min(_case.factors) * _case.n == max(_case.factors) * _case.n == .25
+    _rows = periodicity.accelerate_rows(_case.n, [_case.factors[0], _case.factors[-1]])
+    assert (_rows[0] >= np.arange(_case.n)).all() and (_rows[0] != np.arange(_case.n)).sum() > _case.n // 2
+    assert (_rows[1] <= np.arange(_case.n)).all() and (_rows[1] != np.arange(_case.n)).sum() > _case.n // 2
+assert 130 % 4 != 0 and TILE_UNITS < 127 * 130 < TILE_UNITS + 256          # (a last segment narrower than a workgroup)
+assert 64 % 4 == 0 and TILE_UNITS < 1025 * 64 // 4 and -(-1025 * 64 // TILE_UNITS) == 5 and 1024 * 64 // 4 == TILE_UNITS
 # the planted pulsar: 128 samples of shift in the middle of the block, a drift of 16 bins at the fundamental
 assert PULSAR_K0 * PULSAR_N ** 2 / 4 == 128. and abs(PULSAR_K0) * 2 * PULSAR_N <= .25
 assert PULSAR_BIN == 512 and 2 * PULSAR_K0 * PULSAR_N * PULSAR_BIN == 16.

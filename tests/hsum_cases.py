@@ -36,9 +36,16 @@ CASES = [
     Case('wide', (300, 4), 513, 2, 128, 4, 0, 5),
     # one bin per block
     Case('single_bin_blocks', (16,), 700, 4, 1, 5, 3, 6),
+    # two and three levels, the only depths no other case has (k_hsum_search<2> and <3>): a prime element
+    # count above a wave, a short last block (777 = 59 * 13 + 10), lo cutting into level-dependent j.  Blocks
+    # of 13 bins, since among 61 integers 0 ... 8 some pair always beats the best single bin and level 0 never wins
+    Case('two_levels', (67,), 777, 2, 13, 2, 2, 7),
+    Case('three_levels', (67,), 777, 2, 13, 3, 2, 8),
 ]
 IDS = [c.name for c in CASES]
 KINDS = ('int', 'noise')
+#: the cases that pin an instantiation by name: test_hsum_host.py holds the twin to winners at every level
+EVERY_LEVEL_WINS = ('two_levels', 'three_levels')
 
 #: tilings from the smallest to the largest: (BBT_HSUM_WIDTH, BBT_HSUM_SPLIT)
 TILINGS = [(16, 1), (16, 16), (32, 4), (64, 2), (64, 16)]

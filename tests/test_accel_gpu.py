@@ -52,7 +52,12 @@ def test_table_against_the_twin(case, route, monkeypatch):
     i0 = case.n // 2 // info['rows'] * info['rows']
     middle_fits = plan.info(i0, min(case.n, i0 + info['rows']) - i0)['fits']
     plan.close()
-    if route == 2 or 2 * n_elem * 4 > hip.ACCEL_LDS_BYTES:
+    # (info counts in units of 4 bytes: a row of more than a tile of them is cut into segments, and those go direct)
+    segmented = n_elem * len(case.factors) > hip.ACCEL_TILE_UNITS
+    assert segmented == (case.name in accel_cases.SEGMENTED + (accel_cases.FENCE_POST,))
+    if segmented:
+        assert info['route'] == 2 and info['rows'] == 1
+    if route == 2 or 2 * n_elem * 4 > hip.ACCEL_LDS_BYTES or segmented:
         assert info['route'] == 2
     else:
         assert info['route'] == (1 if route == 1 or (n_elem >= 4 and middle_fits) else 2)

@@ -375,6 +375,8 @@ def _walk_groups():
         n_elem = int(np.prod(case.shape, dtype=np.int64))
         units = (4, 16) if n_elem % 4 == 0 else (4,)
         chunks = (case.length,) if case.n >= 4096 else (case.length, 1, 37, case.n + case.n // 2)
+        if len(case.factors) > 1000:
+            chunks = (case.length, 37)                 # (every group repeats its factors on the command line)
         for unit in units:
             for route in (0, 1, 2):
                 for chunk in chunks:
@@ -426,6 +428,12 @@ def test_kernel_indexing_on_the_host(geo_check):
             assert g['direct'] > 0            # (shifts of 2048 rows: no window of the middle fits)
         past += g['max_out'] * per >= 1 << 31
     assert past >= 2
+    # the rows of the table that are wider than a tile: cut into segments in either unit, but for the fence
+    # post, which in units of 16 bytes is exactly one tile wide
+    seen = {(n_elem * len(factors), unit): g for (_, n, n_elem, unit, _, _, factors), g in zip(groups, lines) if n == 32}
+    assert sorted(seen) == [(16510, 4), (65536, 4), (65536, 16), (65600, 4), (65600, 16)]
+    assert [(seen[key]['n_seg'], seen[key]['ws'], seen[key]['rows']) for key in sorted(seen)] == [
+        (2, 16384, 1), (4, 16384, 1), (1, 16384, 1), (5, 16384, 1), (2, 16384, 1)]
     # what the library refuses
     bad = subprocess.run([geo_check, 'walk'] + '64 1 1 4 0 8 1 0  64 64 0 4 0 8 1 0  64 64 1 4 0 8 0  64 64 1 4 0 8 1 0.004'
                          '  64 64 2 16 0 8 1 0  10 64 1 4 0 8 1 0'.split(), stdout=subprocess.PIPE, text=True)

@@ -68,6 +68,20 @@ def test_twin_is_the_brute_force_rule_on_integers(case):
         assert len(np.unique(got[:, :, LEVEL])) > 1            # (winners at more than one level)
 
 
+@pytest.mark.parametrize('kind', hsum_cases.KINDS)
+@pytest.mark.parametrize('name', hsum_cases.EVERY_LEVEL_WINS)
+def test_every_level_wins_in_the_cases_that_pin_an_instantiation(name, kind):
+    """The two- and the three-level case are the only ones that reach their instantiation of the search
+    kernel: their data must exercise every level of it, behind a ragged last block, a prime element count
+    above a wave and a lo that cuts off another first j at every level."""
+    case = hsum_cases.by_name(name)
+    got = hsum_cases.expected(case, kind)
+    assert case.K in (2, 3) and sorted(np.unique(got[:, :, LEVEL]).tolist()) == list(range(case.K))
+    assert 0 < case.nbin % case.n < case.n and int(np.prod(case.s)) == 67 and np.isfinite(got).all()
+    first = [min(j for j in range(case.n) if (j + ((1 << L) >> 1)) >> L >= case.lo) for L in range(case.K)]
+    assert len(set(first)) == case.K and first[0] == case.lo
+
+
 def test_brute_force_agrees_on_the_prototype_shape():
     rng = np.random.default_rng(11)
     x = rng.integers(0, 9, size=(2, 1501, 7)).astype(np.float32)
