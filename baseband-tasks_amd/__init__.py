@@ -24,11 +24,12 @@ from .integration import Integrate, Fold, PulseStack
 from .modulation import Modulate, modulate_samples
 from .rfi import SpectralKurtosis, Excise, sk_limits, spectral_kurtosis, excise_flags, excise_samples
 from .search import (DMTrials, dm_trial_shifts, dm_trials_samples, Standardize, standardize_samples,
-                     BoxcarSearch, boxcar_search_samples, boxcar_candidates)
+                     BoxcarSearch, boxcar_search_samples, boxcar_candidates, RobustStandardize,
+                     robust_standardize_samples, block_median_mad_samples)
 from . import search
 from .periodicity import (fluctuation_spectra, Whiten, whiten_samples, HarmonicSearch, harmonic_search_samples,
                           harmonic_scales, harmonic_candidates, LongSpectra, long_spectra_samples, Accelerate,
-                          accelerate_samples)
+                          accelerate_samples, MedianWhiten, median_whiten_samples, median_ratio)
 from . import periodicity
 from .conversion import Real2Complex
 from .shaping import (ChangeSampleShapeBase, ChangeSampleShape, Reshape, Transpose, ReshapeAndTranspose,

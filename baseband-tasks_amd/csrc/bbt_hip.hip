@@ -38,6 +38,7 @@
 #include "hsum_kernels.hpp"
 #include "lspec_kernels.hpp"
 #include "accel_kernels.hpp"
+#include "rank_kernels.hpp"
 #include "r2c_kernels.hpp"
 #include "gather_kernels.hpp"
 #include "pack_kernels.hpp"
@@ -47,7 +48,7 @@
 
 using namespace bbt;
 
-#define BBT_VERSION 167
+#define BBT_VERSION 168
 
 // ---------------------------------------------------------------------------
 // errors
@@ -4148,6 +4149,100 @@ extern "C" int bbt_accel_execute(bbt_accel_plan* p, const float* in_dev, int64_t
         else hipLaunchKernelGGL((k_accel<unsigned, false>), grid, block, 0, st, x, o, p->factors, g);
     }
     HIP_TRY(hipGetLastError());
+    return 0;
+}
+
+// ---------------------------------------------------------------------------
+// block median / MAD by selection (rank_kernels.hpp; the tiling is rank_geo.hpp's)
+
+// BBT_RANK_ROUTE: lds (wherever the block fits), global, or auto; BBT_RANK_DIGIT: bits of a radix digit
+// (4, 8); BBT_RANK_WIDTH: elements of a workgroup (16, 32, 64).  Read at every call, for measuring and for
+// the tests that walk the routes; no value of the output depends on any.  Anything else leaves the default.
+static int rank_env_route() {
+    const char* e = getenv("BBT_RANK_ROUTE");
+    if (e && !strcmp(e, "lds")) return BBT_RANK_ROUTE_LDS;
+    if (e && !strcmp(e, "global")) return BBT_RANK_ROUTE_GLOBAL;
+    return BBT_RANK_ROUTE_AUTO;
+}
+static int rank_env_digit() { return dmt_env("BBT_RANK_DIGIT", {4, 8}); }
+static int rank_env_width() { return dmt_env("BBT_RANK_WIDTH", {16, 32, 64}); }
+
+static int rank_launch(const RankGeo& g, const float* x, float* out, float* med, float* mad, hipStream_t st) {
+    const dim3 grid((unsigned)g.n_wg), block(BBT_RANK_THREADS);
+    const size_t lds = (size_t)g.lds_bytes;
+    const bool in_lds = g.route == BBT_RANK_ROUTE_LDS;
+    // (up to 72 KiB of dynamic LDS: beyond what a kernel may take unasked)
+    const void* func = g.digit == 4 ? (in_lds ? (const void*)k_rank<4, true> : (const void*)k_rank<4, false>)
+                                    : (in_lds ? (const void*)k_rank<8, true> : (const void*)k_rank<8, false>);
+    if (ensure_dyn_lds(func, BBT_RANK_LDS_BYTES)) return 1;
+    if (g.digit == 4) {
+        if (in_lds) hipLaunchKernelGGL((k_rank<4, true>), grid, block, lds, st, x, out, med, mad, g);
+        else hipLaunchKernelGGL((k_rank<4, false>), grid, block, lds, st, x, out, med, mad, g);
+    } else {
+        if (in_lds) hipLaunchKernelGGL((k_rank<8, true>), grid, block, lds, st, x, out, med, mad, g);
+        else hipLaunchKernelGGL((k_rank<8, false>), grid, block, lds, st, x, out, med, mad, g);
+    }
+    HIP_TRY(hipGetLastError());
+    return 0;
+}
+
+// med[s][b][e] (and mad[s][b][e]) of block b < ceil((nbin - skip) / m) of spectrum s < n_spec; NaN where flagged
+extern "C" int bbt_rank_stats(const float* x_dev, float* med_dev, float* mad_dev, int64_t n_spec, int64_t nbin,
+                              int64_t n_elem, int64_t m, int64_t skip, bbt_stream stream) {
+    ARG_TRY(x_dev && med_dev, "bbt_rank_stats: null argument");
+    ARG_TRY((((uintptr_t)x_dev | (uintptr_t)med_dev | (uintptr_t)mad_dev) & 3) == 0,
+            "bbt_rank_stats: arrays must be 4-byte aligned");
+    RankGeo g = {};
+    const char* err = rank_geo(n_spec, nbin, n_elem, m, skip, rank_env_width(), rank_env_digit(), rank_env_route(), &g);
+    ARG_TRY(!err, "bbt_rank_stats: %s (n_spec=%lld, nbin=%lld, n_elem=%lld, m=%lld, skip=%lld)", err ? err : "",
+            (long long)n_spec, (long long)nbin, (long long)n_elem, (long long)m, (long long)skip);
+    g.mode = BBT_RANK_STATS, g.with_mad = mad_dev != nullptr;
+    return rank_launch(g, x_dev, nullptr, med_dev, mad_dev, (hipStream_t)stream);
+}
+
+// out[b * n + t][e] = (x[b * n + t][e] - med) * (1 / (1.4826 mad)) of block b < n_block, element e < n_elem
+extern "C" int bbt_rank_standardize(const float* x_dev, float* out_dev, int64_t n_block, int64_t n, int64_t n_elem,
+                                    bbt_stream stream) {
+    ARG_TRY(x_dev && out_dev, "bbt_rank_standardize: null argument");
+    ARG_TRY((((uintptr_t)x_dev | (uintptr_t)out_dev) & 3) == 0, "bbt_rank_standardize: arrays must be 4-byte aligned");
+    RankGeo g = {};
+    const char* err = rank_std_geo(n_block, n, n_elem, rank_env_width(), rank_env_digit(), rank_env_route(), &g);
+    ARG_TRY(!err, "bbt_rank_standardize: %s (n_block=%lld, n=%lld, n_elem=%lld)", err ? err : "", (long long)n_block,
+            (long long)n, (long long)n_elem);
+    g.mode = BBT_RANK_STANDARDIZE;
+    return rank_launch(g, x_dev, out_dev, nullptr, nullptr, (hipStream_t)stream);
+}
+
+// out[s][j][e] = x[s][j][e] * (1 / (med / ratio)) with the median of the block of m bins that holds j, +0 for j < skip
+extern "C" int bbt_rank_whiten(const float* x_dev, float* out_dev, int64_t n_spec, int64_t nbin, int64_t n_elem,
+                               int64_t m, int64_t skip, double ratio, bbt_stream stream) {
+    ARG_TRY(x_dev && out_dev, "bbt_rank_whiten: null argument");
+    ARG_TRY((((uintptr_t)x_dev | (uintptr_t)out_dev) & 3) == 0, "bbt_rank_whiten: arrays must be 4-byte aligned");
+    ARG_TRY(ratio > 0. && ratio < __builtin_inf(), "bbt_rank_whiten: ratio must be finite and > 0");
+    RankGeo g = {};
+    const char* err = rank_geo(n_spec, nbin, n_elem, m, skip, rank_env_width(), rank_env_digit(), rank_env_route(), &g);
+    ARG_TRY(!err, "bbt_rank_whiten: %s (n_spec=%lld, nbin=%lld, n_elem=%lld, m=%lld, skip=%lld)", err ? err : "",
+            (long long)n_spec, (long long)nbin, (long long)n_elem, (long long)m, (long long)skip);
+    g.mode = BBT_RANK_WHITEN, g.ratio = ratio;
+    return rank_launch(g, x_dev, out_dev, nullptr, nullptr, (hipStream_t)stream);
+}
+
+// the route (1 lds, 2 global), digit and width a launch of these sizes takes, the LDS bytes of a workgroup,
+// and lds_rows[3]: the longest block the lds route takes at widths 16, 32, 64 with that digit.  No device.
+extern "C" int bbt_rank_info(int64_t n_spec, int64_t nbin, int64_t n_elem, int64_t m, int64_t skip, int* route,
+                             int* digit, int* width, int64_t* lds_bytes, int64_t* lds_rows) {
+    RankGeo g = {};
+    const char* err = rank_geo(n_spec, nbin, n_elem, m, skip, rank_env_width(), rank_env_digit(), rank_env_route(), &g);
+    ARG_TRY(!err, "bbt_rank_info: %s (n_spec=%lld, nbin=%lld, n_elem=%lld, m=%lld, skip=%lld)", err ? err : "",
+            (long long)n_spec, (long long)nbin, (long long)n_elem, (long long)m, (long long)skip);
+    if (route) *route = g.route;
+    if (digit) *digit = g.digit;
+    if (width) *width = g.nx;
+    if (lds_bytes) *lds_bytes = g.lds_bytes;
+    if (lds_rows) {
+        const int d = rank_env_digit() ? rank_env_digit() : BBT_RANK_DIGIT_LDS;
+        lds_rows[0] = rank_lds_rows(16, d), lds_rows[1] = rank_lds_rows(32, d), lds_rows[2] = rank_lds_rows(64, d);
+    }
     return 0;
 }
 

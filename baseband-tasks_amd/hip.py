@@ -132,6 +132,10 @@ SIGNATURES = {
     'bbt_accel_plan_destroy': [_vp],
     'bbt_accel_plan_info': [_vp, _i64, _i64, C.POINTER(_int), C.POINTER(_int), _pi64, _pi64, _pi64, C.POINTER(_int)],
     'bbt_accel_execute': [_vp, _vp, _i64, _i64, _vp, _i64, _i64, _vp],
+    'bbt_rank_stats': [_vp, _vp, _vp, _i64, _i64, _i64, _i64, _i64, _vp],
+    'bbt_rank_standardize': [_vp, _vp, _i64, _i64, _i64, _vp],
+    'bbt_rank_whiten': [_vp, _vp, _i64, _i64, _i64, _i64, _i64, C.c_double, _vp],
+    'bbt_rank_info': [_i64, _i64, _i64, _i64, _i64, C.POINTER(_int), C.POINTER(_int), C.POINTER(_int), _pi64, _pi64],
     'bbt_fir_plan_create': [_pvp, _int, _int, _vp],
     'bbt_fir_plan_destroy': [_vp],
     'bbt_fir_execute': [_vp, _vp, _vp, _i64, _vp],
@@ -166,7 +170,7 @@ SIGNATURES = {
 }
 
 #: oldest libbbt_hip.so whose entry points and argument meanings this binding assumes
-MIN_LIB_VERSION = 167
+MIN_LIB_VERSION = 168
 
 _lib = None
 _lock = threading.Lock()
@@ -1919,6 +1923,95 @@ class AccelPlan(_Plan):
                              f"whole block of {self.n} of a stream of {n_rows}")
         check(lib().bbt_accel_execute(self._h, in_dev.ptr_to_read(), in_first, n_in, out_dev.ptr, out_first, n_out,
                                       _stream))
+
+
+#: bounds of the block median / MAD (csrc/rank_geo.hpp)
+RANK_MIN_N, RANK_MAX_N, RANK_LDS_BYTES, RANK_MISC_BYTES = 2, 65536, 73728, 1024
+RANK_MAD_SCALE = 1.482602218505602
+RANK_ROUTES = {1: 'lds', 2: 'global'}
+
+
+def rank_info(n_spec=1, nbin=2, n_elem=1, m=2, skip=0):
+    """For a launch of these sizes: the route it takes now (BBT_RANK_ROUTE; 'lds' or 'global'), the bits of a
+    digit (BBT_RANK_DIGIT), the elements of a workgroup (BBT_RANK_WIDTH), the LDS bytes of a workgroup and
+    ``lds_rows``: per width 16, 32, 64 the longest block the lds route takes.  No device is needed."""
+    route, digit, width, lds = _int(0), _int(0), _int(0), _i64(0)
+    rows = (_i64 * 3)()
+    check(lib().bbt_rank_info(int(n_spec), int(nbin), int(n_elem), int(m), int(skip), C.byref(route), C.byref(digit),
+                              C.byref(width), C.byref(lds), rows))
+    return dict(route=RANK_ROUTES[route.value], digit=digit.value, width=width.value, lds_bytes=lds.value,
+                lds_rows={16: rows[0], 32: rows[1], 64: rows[2]})
+
+
+def _rank_sizes(who, x, nbin, n_elem, m, skip):
+    if x.dtype != np.float32:
+        raise TypeError(f"{who}: x must be float32, not {x.dtype}")
+    if n_elem < 1 or nbin < 1 or x.size % (nbin * n_elem) or x.size == 0:
+        raise ValueError(f"{who}: {x.size} values are not spectra of {nbin} rows of {n_elem} elements")
+    if not RANK_MIN_N <= m <= RANK_MAX_N:
+        raise ValueError(f"{who}: a block must have {RANK_MIN_N} ... {RANK_MAX_N} values, not {m}")
+    if not 0 <= skip < nbin:
+        raise ValueError(f"{who}: skip must be 0 ... {nbin - 1}, not {skip}")
+    return x.size // (nbin * n_elem)
+
+
+def rank_stats(x, nbin, n_elem, m, skip=0, mad=True, out=None):
+    """The median -- and, with ``mad``, the median absolute deviation from it -- of every block of ``m`` rows,
+    counted from row ``skip``, the last block whatever is left, of every spectrum of float32 ``x`` (spectra of
+    ``nbin`` rows of ``n_elem`` elements), by exact selection (bbt_rank_stats in include/bbt_hip.h;
+    `search.block_median_mad_samples` is the NumPy restatement).  Returns float32 DeviceArrays ``(n_spec,
+    ceil((nbin - skip) / m), n_elem)``: ``(med, mad)`` or ``med``; NaN where a block holds a NaN or an Inf.
+    ``out``: the arrays to fill, ``(med, mad)`` or ``(med,)``."""
+    nbin, n_elem, m, skip = int(nbin), int(n_elem), int(m), int(skip)
+    n_spec = _rank_sizes('rank_stats', x, nbin, n_elem, m, skip)
+    shape = (n_spec, -(-(nbin - skip) // m), n_elem)
+    if out is None:
+        out = tuple(DeviceArray(shape, np.float32) for _ in range(2 if mad else 1))
+    size = shape[0] * shape[1] * shape[2]
+    if len(out) != (2 if mad else 1) or any(a.dtype != np.float32 or a.size != size for a in out):
+        raise ValueError(f"rank_stats: out must be {2 if mad else 1} float32 DeviceArrays of {size} values")
+    med, dev = out[0], (out[1] if mad else None)
+    check(lib().bbt_rank_stats(x.ptr_to_read(), med.ptr, dev.ptr if mad else None, n_spec, nbin, n_elem, m, skip,
+                               _stream))
+    return (med, dev) if mad else med
+
+
+def rank_standardize(x, n, n_elem, out=None):
+    """Every whole block of ``n`` samples of float32 ``x`` (samples of ``n_elem`` elements) brought to zero
+    median and unit ``1.4826 MAD`` per element (bbt_rank_standardize in include/bbt_hip.h;
+    `search.robust_standardize_samples` is the NumPy restatement).  Returns ``out``, float32 of ``(x.size //
+    n_elem // n) * n * n_elem`` values."""
+    n, n_elem = int(n), int(n_elem)
+    if x.dtype != np.float32:
+        raise TypeError(f"rank_standardize: x must be float32, not {x.dtype}")
+    if n_elem < 1 or x.size % n_elem:
+        raise ValueError(f"rank_standardize: {x.size} values are not samples of {n_elem} elements")
+    if not RANK_MIN_N <= n <= RANK_MAX_N:
+        raise ValueError(f"rank_standardize: n must be {RANK_MIN_N} ... {RANK_MAX_N}, not {n}")
+    n_block = x.size // n_elem // n
+    if out is None:
+        out = DeviceArray((n_block * n, n_elem), np.float32)
+    elif out.dtype != np.float32 or out.size != n_block * n * n_elem:
+        raise ValueError(f"rank_standardize: out must be a float32 DeviceArray of {n_block * n * n_elem} values")
+    check(lib().bbt_rank_standardize(x.ptr_to_read(), out.ptr, n_block, n, n_elem, _stream))
+    return out
+
+
+def rank_whiten(x, nbin, n_elem, m, skip=1, ratio=0.6931471805599453, out=None):
+    """Every block of ``m`` bins, counted from bin ``skip``, of every spectrum of float32 ``x`` (spectra of
+    ``nbin`` bins of ``n_elem`` elements) divided by its own median over ``ratio``, the bins below ``skip`` +0
+    (bbt_rank_whiten in include/bbt_hip.h; `periodicity.median_whiten_samples` is the NumPy restatement).
+    Returns ``out``, float32 of the size of ``x``."""
+    nbin, n_elem, m, skip, ratio = int(nbin), int(n_elem), int(m), int(skip), float(ratio)
+    n_spec = _rank_sizes('rank_whiten', x, nbin, n_elem, m, skip)
+    if not 0. < ratio < float('inf'):
+        raise ValueError(f"rank_whiten: ratio must be finite and > 0, not {ratio}")
+    if out is None:
+        out = DeviceArray((n_spec, nbin, n_elem), np.float32)
+    elif out.dtype != np.float32 or out.size != x.size:
+        raise ValueError(f"rank_whiten: out must be a float32 DeviceArray of {x.size} values")
+    check(lib().bbt_rank_whiten(x.ptr_to_read(), out.ptr, n_spec, nbin, n_elem, m, skip, ratio, _stream))
+    return out
 
 
 COMM_ID_BYTES = 128

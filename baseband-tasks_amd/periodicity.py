@@ -11,11 +11,15 @@ harmonic, the gathered bins added in a fixed order; the winner of a block is the
 order.  So every value has one correct bit pattern, whatever the tiling or the chunking.  `LongSpectra`
 is the exception: a float32 transform has no single correct rounding, so `long_spectra_samples` is a
 float64 yardstick its values are near, and what is exact is that they do not depend on the chunking.
+`MedianWhiten` divides by the block median over `median_ratio` instead of the mean, an exact selection
+(csrc/rank_kernels.hpp; the twin is `median_whiten_samples`) that lines in the block do not raise.
 
 For pulsars in binaries `Accelerate` goes in front of the spectra: per trial acceleration every block of the
 time series is resampled along a parabola, nearest sample, by one integer rule (`accelerate_rows`; the twin is
 `accelerate_samples`, csrc/accel_kernels.hpp computes it), and `acceleration_candidates` takes the maxima over
 (block, acceleration, trial)."""
+import functools
+import math
 import operator
 
 import numpy as np
@@ -27,9 +31,10 @@ from .fourier import check_transform_length
 from .device_task import DeviceTaskMixin, fetch_device
 from .functions import Square
 from .integration import Integrate
-from .search import _check_plane, _check_plane_stream, _local_maxima, _local_maxima_3d, _lone_frequency, _prod
+from .search import _block_median, _check_plane, _check_plane_stream, _local_maxima, _local_maxima_3d, _lone_frequency, _prod
 
-__all__ = ['fluctuation_spectra', 'LongSpectra', 'long_spectra_samples', 'Whiten', 'whiten_samples', 'HarmonicSearch', 'harmonic_search_samples',
+__all__ = ['fluctuation_spectra', 'LongSpectra', 'long_spectra_samples', 'Whiten', 'whiten_samples', 'MedianWhiten',
+           'median_whiten_samples', 'median_ratio', 'LN2', 'HarmonicSearch', 'harmonic_search_samples',
            'harmonic_scales', 'harmonic_candidates', 'Accelerate', 'accelerate_samples', 'accelerate_rows',
            'acceleration_factors', 'acceleration_grid', 'acceleration_candidates', 'SNR', 'OFFSET', 'LEVEL']
 
@@ -187,6 +192,109 @@ def whiten_samples(data, m, skip=1):
         out[:, skip:skip + n_full * m] = _whiten_blocks(x).reshape((data.shape[0], n_full * m) + data.shape[2:])
     if skip + n_full * m < nbin:
         out[:, skip + n_full * m:] = _whiten_blocks(data[:, np.newaxis, skip + n_full * m:])[:, 0]
+    return out
+
+
+#: the median of an exponential distribution of unit mean
+LN2 = math.log(2.)
+
+
+#: the most averaged powers `median_ratio` computes the median for: the longest stack of `LongSpectra`
+MAX_AVERAGED = hip.LSPEC_MAX_STACK
+
+
+@functools.lru_cache(maxsize=64)
+def _erlang_median_ratio(k):
+    """``x / k`` with ``x`` the root of the Erlang CDF ``1 - sum_{j<k} exp(j log x - x - log j!) = 1/2``.  Every
+    term is formed in log space, so nothing overflows however large ``k``; the exponents, up to 1.4e7 for
+    ``k`` = 2^20 and needed to 1e-12, are formed in extended precision (`numpy.longdouble`).  Terms more than
+    40 sqrt(k) below the peak at ``j = x`` are below ``exp(-800)`` of it and are left out.  The median of a
+    gamma distribution of shape ``k`` lies in ``(k - 1/3, k)``, so 64 bisections of ``[k - 1, k]`` end at
+    neighbouring float64.  One step is one vectorised pass over at most ``40 sqrt(k)`` terms."""
+    first = max(0, int(k - 1 - 40. * math.sqrt(k)))
+    j = np.arange(k, dtype=np.longdouble)
+    log_fact = np.concatenate([[np.longdouble(0.)], np.cumsum(np.log(j[1:]))])[first:]
+    j = j[first:]
+
+    def cdf(x):
+        x = np.longdouble(x)
+        return 1. - float(np.exp(j * np.log(x) - x - log_fact).sum())
+
+    lo, hi = k - 1., float(k)
+    for _ in range(64):
+        mid = 0.5 * (lo + hi)
+        if cdf(mid) < 0.5:
+            lo = mid
+        else:
+            hi = mid
+    return 0.5 * (lo + hi) / k
+
+
+def median_ratio(averaged=1):
+    """The median, in units of the mean, of the average of ``averaged`` exponential powers -- what
+    ``stack=averaged`` of `fluctuation_spectra` makes of noise: ``log(2)`` for 1, and for an integer ``k`` from 2
+    to `MAX_AVERAGED` = 2^20 ``x / k`` with ``x`` the root of ``1 - exp(-x) sum_{j<k} x^j / j! = 1/2`` (the Erlang
+    distribution), found by 64 bisections of ``[k - 1, k]`` with the terms formed in log space, in extended
+    precision (64 passes over at most ``40 sqrt(k)`` terms; results are remembered).  For anything else -- a
+    fraction, more powers -- pass ``ratio=`` to `MedianWhiten` yourself; ``1 - 1 / (3 k)`` is within ``8 / (405
+    k^2)`` of it."""
+    try:
+        k = operator.index(averaged)
+    except TypeError:
+        value = float(averaged)
+        if not math.isfinite(value) or value != int(value):
+            raise ValueError(f"median_ratio knows the median for a whole number of averaged powers, not "
+                             f"{averaged}: pass ratio= yourself.") from None
+        k = int(value)
+    if not 1 <= k <= MAX_AVERAGED:
+        raise ValueError(f"averaged must be 1 ... {MAX_AVERAGED}, not {averaged}: pass ratio= yourself.")
+    return LN2 if k == 1 else _erlang_median_ratio(k)
+
+
+def _check_ratio(ratio):
+    ratio = float(ratio)
+    if not 0. < ratio < math.inf:
+        raise ValueError(f"ratio must be finite and > 0, not {ratio}.")
+    return ratio
+
+
+def _median_whiten_blocks(x, ratio):
+    """``x``: float32 ``(N, blocks, len) + s``, every ``x[:, b]`` one block."""
+    flat = x.reshape((x.shape[0] * x.shape[1],) + x.shape[2:])
+    med = _block_median(flat).reshape(x.shape[:2] + x.shape[3:])
+    flagged = ~np.isfinite(x).all(axis=2)
+    with np.errstate(all='ignore'):
+        mean = med.astype(np.float64) / np.float64(ratio)
+        r32 = (1. / mean).astype(np.float32)
+        ok = ~flagged & np.isfinite(mean) & (mean > 0.) & np.isfinite(r32)
+        z = x * r32[:, :, np.newaxis]
+    assert z.dtype == np.float32
+    z[np.broadcast_to(~ok[:, :, np.newaxis], z.shape)] = 0.
+    return z
+
+
+def median_whiten_samples(data, m, skip=1, ratio=LN2):
+    """NumPy restatement of the `MedianWhiten` kernel.
+
+    ``data``: float32 ``(N, nbin) + s``.  Bins below ``skip`` come out ``+0``; from ``skip`` on the bins are
+    cut into blocks of ``m``, the last one whatever is left, exactly as `whiten_samples` cuts them.  Per
+    spectrum, block and element, with ``med`` the median of the block by the rule of
+    `search.block_median_mad_samples` (the keys sorted; the two middle values averaged in float64) ::
+
+        mean = float64(med) / ratio;  r = 1 / mean;  z = x * float32(r)          (float32: one multiply)
+
+    A block that holds a NaN or an Inf, one whose ``mean`` is not finite or not ``> 0``, and one whose
+    ``float32(r)`` is not finite are ``+0`` throughout."""
+    data, m = _check_spectra(data, 'median_whiten_samples'), _check_m(m)
+    nbin = data.shape[1]
+    skip, ratio = _check_skip(skip, nbin), _check_ratio(ratio)
+    out = np.zeros(data.shape, np.float32)
+    n_full = (nbin - skip) // m
+    if n_full:
+        x = data[:, skip:skip + n_full * m].reshape((data.shape[0], n_full, m) + data.shape[2:])
+        out[:, skip:skip + n_full * m] = _median_whiten_blocks(x, ratio).reshape((data.shape[0], n_full * m) + data.shape[2:])
+    if skip + n_full * m < nbin:
+        out[:, skip + n_full * m:] = _median_whiten_blocks(data[:, np.newaxis, skip + n_full * m:], ratio)[:, 0]
     return out
 
 
@@ -454,7 +562,8 @@ class Whiten(DeviceTaskMixin, BaseTaskBase):
     the block, summed in float64 in a fixed order, and the values equal `whiten_samples` bit for
     bit.  A block that is all zero, holds a NaN or an Inf, or has a negative or a denormal mean comes
     out as +0.  There is no median and no running fit: a bright line raises the mean of its own block,
-    and red noise steeper than a block is not flattened inside it."""
+    and red noise steeper than a block is not flattened inside it.  `MedianWhiten` is the median-based
+    counterpart."""
 
     #: input bytes fetched at most per `fetch_device` call and launch (assignable); a chunk is a
     #: whole number of spectra, one at least
@@ -488,6 +597,78 @@ class Whiten(DeviceTaskMixin, BaseTaskBase):
             c1 = min(b, c0 + per)
             x = fetch_device(self.ih, c0, c1 - c0)
             hip.hsum_whiten(x, self._nbin, self._n_elem, self.m, self.skip, out=out[c0 - a:c1 - a])
+
+
+class MedianWhiten(DeviceTaskMixin, BaseTaskBase):
+    """Divide every block of ``m`` frequency bins of every spectrum by the noise mean its own median
+    implies, per element: `Whiten` with an estimate the pulsar's harmonics and birdies cannot raise.
+
+    Parameters
+    ----------
+    ih : stream
+        float32 spectra of shape ``(N, nbin) + s``: the bin axis is the first sample axis -- usually
+        `fluctuation_spectra` of the (time, DM) plane.
+    m : int
+        Bins of a block, 2 ... 65536, counted from bin ``skip``; the last block is whatever is left.
+    skip : int, optional
+        Bins below it come out ``+0``: the DC bin by default.  ``0 <= skip < nbin``.
+    averaged : int, optional
+        Power spectra averaged into every value (``stack`` of `fluctuation_spectra`): it fixes the ratio
+        of the noise's median to its mean, `median_ratio`.  Default 1: exponential powers, ``log(2)``.
+    ratio : float, optional
+        That ratio itself, finite and ``> 0``, for any other noise; not together with ``averaged``.
+    samples_per_frame : int, optional
+        Spectra per frame.  Default: that of ``ih``.
+
+    Shape, sample rate, start time and metadata are those of ``ih``.  Per block ``mean = float64(med) /
+    ratio`` with ``med`` the block's median, an exact selection on the GPU (the mean of the two middle
+    values for an even count), and ``z = x * float32(1 / mean)``: the values equal `median_whiten_samples`
+    bit for bit, whatever the route, the tiling or the chunking.  A block that holds a NaN or an Inf, or
+    whose median is not ``> 0`` or denormal, comes out as +0.  There is no running median and no fit: red
+    noise steeper than a block is not flattened inside it."""
+
+    #: input bytes fetched at most per `fetch_device` call and launch (assignable); a chunk is a
+    #: whole number of spectra, one at least
+    whiten_budget = 1 << 29
+
+    def __init__(self, ih, m, skip=1, *, averaged=1, ratio=None, samples_per_frame=None):
+        _check_spectra_stream(ih, 'MedianWhiten')
+        self.m = _check_m(m)
+        self._nbin = ih.shape[1]
+        self.skip = _check_skip(skip, self._nbin)
+        if ratio is not None and averaged != 1:
+            raise ValueError("give averaged or ratio, not both: ratio is what averaged stands for.")
+        self.ratio = median_ratio(averaged) if ratio is None else _check_ratio(ratio)
+        self._ratio_given = ratio is not None
+        self.averaged = averaged
+        self._n_elem = _prod(ih.shape[2:])
+        if samples_per_frame is None:
+            samples_per_frame = max(min(operator.index(ih.samples_per_frame), ih.shape[0]), 1)
+        lone = _lone_frequency(ih)
+        super().__init__(ih, samples_per_frame=operator.index(samples_per_frame), dtype=np.float32,
+                         **(dict(sideband=1) if lone else {}))
+        if lone:
+            del self.meta['__attributes__']['sideband']
+
+    def _chunk_spectra(self):
+        return max(1, int(self.whiten_budget) // (self._nbin * self._n_elem * 4))
+
+    def _input_span(self, first, last):
+        a, b = self._frame_span(first, last)
+        return (self.ih, a, b - a) if b - a <= self._chunk_spectra() else None      # (one fetch only)
+
+    def _compute_frames(self, first, last, out):
+        a, b = self._frame_span(first, last)
+        per = self._chunk_spectra()
+        for c0 in range(a, b, per):
+            c1 = min(b, c0 + per)
+            x = fetch_device(self.ih, c0, c1 - c0)
+            hip.rank_whiten(x, self._nbin, self._n_elem, self.m, self.skip, self.ratio, out=out[c0 - a:c1 - a])
+
+    def _repr_item(self, key, default, value=None):
+        if key == 'ratio' and not self._ratio_given:
+            return None
+        return super()._repr_item(key, default, value)
 
 
 class HarmonicSearch(DeviceTaskMixin, BaseTaskBase):

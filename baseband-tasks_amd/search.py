@@ -9,7 +9,11 @@ The reference has no such tasks, so the rules are this package's, restated in Nu
 (`dm_trial_shifts`, `dm_trials_samples`, `standardize_samples`, `boxcar_search_samples`) and
 computed by csrc/dmt_kernels.hpp and csrc/sps_kernels.hpp.  The shifts are those of
 `DedisperseSamples`, to the bit; the trial sum is one float32 accumulator per output element, the
-channels added in ascending index; a boxcar sum is a fixed binary tree over its own samples."""
+channels added in ascending index; a boxcar sum is a fixed binary tree over its own samples.
+
+`RobustStandardize` is `Standardize` with the block median and the median absolute deviation, both
+exact selections (csrc/rank_kernels.hpp; the twins are `block_median_mad_samples` and
+`robust_standardize_samples`): a bright pulse does not lower its own S/N."""
 import operator
 
 import numpy as np
@@ -21,6 +25,7 @@ from .dispersion import dispersion_sample_delays, with_band
 from .dm import DispersionMeasure
 
 __all__ = ['DMTrials', 'dm_trial_shifts', 'dm_trials_samples', 'Standardize', 'standardize_samples',
+           'RobustStandardize', 'robust_standardize_samples', 'block_median_mad_samples',
            'BoxcarSearch', 'boxcar_search_samples', 'boxcar_candidates', 'SNR', 'OFFSET', 'WIDTH']
 
 MAX_NCHAN, MAX_NDM = hip.DMT_MAX_NCHAN, hip.DMT_MAX_NDM
@@ -315,6 +320,88 @@ def standardize_samples(data, n):
     return z.reshape((nb * n,) + data.shape[1:])
 
 
+#: sd = mad * this for normal noise: 1 / (sqrt(2) erfinv(1/2)) (BBT_RANK_MAD_SCALE)
+MAD_SCALE = hip.RANK_MAD_SCALE
+_SIGN = np.uint32(0x80000000)
+
+
+def _rank_keys(x):
+    """The monotone integer keys of float32 ``x``: ``bits ^ 0xffffffff`` where the sign bit is set, ``bits |
+    0x80000000`` otherwise, so that -0 comes just before +0."""
+    bits = np.ascontiguousarray(x, dtype=np.float32).view(np.uint32)
+    return np.where(bits & _SIGN != 0, ~bits, bits | _SIGN)
+
+
+def _rank_values(keys):
+    keys = np.ascontiguousarray(keys, dtype=np.uint32)
+    return np.where(keys & _SIGN != 0, keys & ~_SIGN, ~keys).astype(np.uint32).view(np.float32)
+
+
+def _block_median(x):
+    """``x``: float32 ``(a, L) + s``, every ``x[i]`` one block: float32 ``(a,) + s``, the median by the rule."""
+    ln = x.shape[1]
+    keys = np.sort(_rank_keys(x), axis=1)
+    lo, hi = _rank_values(keys[:, (ln - 1) // 2]), _rank_values(keys[:, ln // 2])
+    with np.errstate(all='ignore'):
+        return ((lo.astype(np.float64) + hi.astype(np.float64)) * 0.5).astype(np.float32)
+
+
+def _block_median_mad(x):
+    """``x``: float32 ``(a, L) + s``: ``(med, mad, flagged)``, each ``(a,) + s``."""
+    flagged = ~np.isfinite(x).all(axis=1)
+    med = _block_median(x)
+    with np.errstate(all='ignore'):
+        d = np.abs(x - med[:, np.newaxis])
+    assert d.dtype == np.float32
+    return med, _block_median(d), flagged
+
+
+def block_median_mad_samples(data, n):
+    """NumPy restatement of the selection of `RobustStandardize`: the median and the median absolute
+    deviation of every block of ``n`` samples, per element.
+
+    ``data``: float32 ``(N,) + s``; a tail shorter than ``n`` is dropped.  Values are ordered by the monotone
+    integer key of their bits (`_rank_keys`: -0 just before +0), and the keys are what is sorted.  With ``lo``
+    the value of rank ``(n - 1) // 2`` and ``hi`` that of rank ``n // 2`` (0-based), ``med = float32((float64(lo)
+    + float64(hi)) * 0.5)``; ``mad`` is the same median of ``d[i] = |x[i] - med|`` (one rounded float32 subtract,
+    the sign cleared).  Returns ``(med, mad)``, float32 ``(N // n,) + s``, NaN in both where the block holds
+    a NaN or an Inf."""
+    data, n = _check_plane(data, 'block_median_mad_samples'), _check_block(n, 2)
+    nb = data.shape[0] // n
+    x = data[:nb * n].reshape((nb, n) + data.shape[1:])
+    med, mad, flagged = _block_median_mad(x)
+    med[flagged] = np.nan
+    mad[flagged] = np.nan
+    return med, mad
+
+
+def robust_standardize_samples(data, n):
+    """NumPy restatement of the `RobustStandardize` kernel.
+
+    ``data``: float32 ``(N,) + s``; a tail shorter than ``n`` is dropped.  Per block of ``n`` samples and
+    element, with ``med`` and ``mad`` of `block_median_mad_samples` ::
+
+        sd = float64(mad) * 1.482602218505602;  r = 1 / sd
+        z[i] = (x[i] - med) * float32(r)                    (float32: one subtract, one multiply)
+
+    A block that holds a NaN or an Inf, one whose ``mad`` is not ``> 0`` -- more than half of its values
+    equal -- and one whose ``float32(r)`` is not finite are ``+0`` throughout.  Returns float32 ``((N // n) *
+    n,) + s``."""
+    data, n = _check_plane(data, 'robust_standardize_samples'), _check_block(n, 2)
+    nb = data.shape[0] // n
+    x = data[:nb * n].reshape((nb, n) + data.shape[1:])
+    med, mad, flagged = _block_median_mad(x)
+    with np.errstate(all='ignore'):
+        sd = mad.astype(np.float64) * MAD_SCALE
+        r32 = (1. / sd).astype(np.float32)
+        ok = ~flagged & (mad > 0.) & np.isfinite(r32)
+        z = x - med[:, np.newaxis]
+        z = z * r32[:, np.newaxis]
+    assert z.dtype == np.float32
+    z[np.broadcast_to(~ok[:, np.newaxis], z.shape)] = 0.
+    return z.reshape((nb * n,) + data.shape[1:])
+
+
 def boxcar_search_samples(data, n, n_widths=MAX_WIDTHS):
     """NumPy restatement of the `BoxcarSearch` kernels.
 
@@ -458,7 +545,8 @@ class Standardize(DeviceTaskMixin, BaseTaskBase):
     the values equal `standardize_samples` bit for bit.  A block that is constant, all zero (what
     `Excise` leaves) or holds a NaN or an Inf comes out as +0.  There is no median / MAD, no running
     baseline, and a pulse's own power is not clipped from the estimate: a bright pulse in a short
-    block lowers its own S/N.  Choose blocks much longer than the widest boxcar."""
+    block lowers its own S/N.  Choose blocks much longer than the widest boxcar.  `RobustStandardize` is
+    the median / MAD counterpart."""
 
     #: input bytes fetched at most per `fetch_device` call and launch (assignable); a chunk is a
     #: whole number of blocks
@@ -497,6 +585,74 @@ class Standardize(DeviceTaskMixin, BaseTaskBase):
             c1 = min(b, c0 + per)
             x = fetch_device(self.ih, c0, c1 - c0)
             hip.sps_standardize(x, self.n, self._n_elem, out=out[c0 - a:c1 - a])
+
+    def _repr_item(self, key, default, value=None):
+        if key == 'samples_per_frame' and default is None:
+            default = min(-(-self._ih_samples_per_frame // self.n) * self.n, self.shape[0])
+        return super()._repr_item(key, default, value)
+
+
+class RobustStandardize(DeviceTaskMixin, BaseTaskBase):
+    """Bring every block of ``n`` samples to zero median and unit robust scale (1.4826 MAD), per element
+    of a sample: `Standardize` with statistics a bright pulse or residual RFI in the block cannot move.
+
+    Parameters
+    ----------
+    ih : stream
+        float32, any sample shape -- usually the (time, DM) plane of `DMTrials`.
+    n : int
+        Samples of a block, 2 ... 65536, counted from sample 0 of ``ih``; a tail shorter than ``n`` is
+        dropped.
+    samples_per_frame : int, optional
+        A multiple of ``n``.  Default: the smallest one that is at least ``ih.samples_per_frame``, at
+        most the length of the output.
+
+    Sample rate, start time and metadata are those of ``ih``; the length is ``(len // n) * n``.  Per block
+    and element ``med`` is the median and ``mad`` the median of ``|x - med|``, both exact selections on the
+    GPU (the mean of the two middle values for even ``n``), and ``z = (x - med) * float32(1 / (mad *
+    1.482602218505602))``: the values equal `robust_standardize_samples` bit for bit, whatever the
+    route, the tiling or the chunking.  A block that holds a NaN or an Inf, or in which more than half
+    of the values are equal (``mad = 0``: constant, all zero, what `Excise` leaves) comes out as +0.  The
+    scale is that of normal noise; there is no clipping and re-estimation, no running median, and no
+    percentile other than the median."""
+
+    #: input bytes fetched at most per `fetch_device` call and launch (assignable); a chunk is a
+    #: whole number of blocks
+    robust_budget = 1 << 29
+
+    def __init__(self, ih, n, *, samples_per_frame=None):
+        _check_plane_stream(ih, 'RobustStandardize')
+        self.n = n = _check_block(n, 2)
+        if ih.shape[0] < n:
+            raise ValueError(f"the stream has {ih.shape[0]} samples: less than one block of {n}.")
+        self._n_elem = _prod(ih.shape[1:])
+        length = ih.shape[0] // n * n
+        if samples_per_frame is None:
+            samples_per_frame = min(-(-operator.index(ih.samples_per_frame) // n) * n, length)
+        samples_per_frame = operator.index(samples_per_frame)
+        if samples_per_frame < n or samples_per_frame % n:
+            raise ValueError(f"samples_per_frame must be a multiple of the block, {n}; got {samples_per_frame}.")
+        lone = _lone_frequency(ih)
+        super().__init__(ih, shape=(length,) + tuple(ih.shape[1:]), samples_per_frame=samples_per_frame,
+                         dtype=np.float32, **(dict(sideband=1) if lone else {}))
+        if lone:
+            del self.meta['__attributes__']['sideband']
+
+    def _chunk_samples(self):
+        block_bytes = self.n * self._n_elem * 4
+        return max(1, int(self.robust_budget) // block_bytes) * self.n
+
+    def _input_span(self, first, last):
+        a, b = self._frame_span(first, last)
+        return (self.ih, a, b - a) if b - a <= self._chunk_samples() else None      # (one fetch only)
+
+    def _compute_frames(self, first, last, out):
+        a, b = self._frame_span(first, last)          # (frames and the stream are whole blocks)
+        per = self._chunk_samples()
+        for c0 in range(a, b, per):
+            c1 = min(b, c0 + per)
+            x = fetch_device(self.ih, c0, c1 - c0)
+            hip.rank_standardize(x, self.n, self._n_elem, out=out[c0 - a:c1 - a])
 
     def _repr_item(self, key, default, value=None):
         if key == 'samples_per_frame' and default is None:

@@ -681,6 +681,42 @@ int bbt_accel_plan_info(const bbt_accel_plan* plan, int64_t out_first, int64_t n
 int bbt_accel_execute(bbt_accel_plan* plan, const float* in_dev, int64_t in_first, int64_t n_in, float* out_dev,
                       int64_t out_first, int64_t n_out, bbt_stream stream);
 
+/* ---- block median / MAD by selection: RobustStandardize, MedianWhiten -----
+ * A chunk is x[s][j][e], s < n_spec spectra of nbin rows, float32, element fastest.  Rows j < skip belong
+ * to no block; from skip on the rows are cut into blocks of m (2 ... 65536), the last one whatever is
+ * left: ceil((nbin - skip) / m) blocks per spectrum.  Time-domain blocks are n_spec = 1, skip = 0.
+ *
+ * The order of float32 values is that of key = bits ^ 0xffffffff (sign set) or bits | 0x80000000 (else),
+ * so -0 comes just before +0.  The median of L values: lo of rank (L - 1) / 2, hi of rank L / 2, med =
+ * (float)(((double)lo + (double)hi) * 0.5).  A block that holds a NaN or an Inf is flagged.
+ *
+ * bbt_rank_stats: med[s][b][e], and mad[s][b][e] if mad_or_null is given: the median of |x - med| (one
+ * rounded float32 subtract, the sign cleared) by the same rule.  NaN in both for a flagged block.
+ * bbt_rank_standardize: per block b < n_block of n rows, sd = (double)mad * 1.482602218505602, r = 1 / sd,
+ * out = (x - med) * (float)r in float32, one rounded subtract and one rounded multiply; +0 throughout
+ * where the block is flagged, mad is not > 0 or (float)r is not finite.
+ * bbt_rank_whiten: rows j < skip come out +0; mean = (double)med / ratio, r = 1 / mean, out = x * (float)r;
+ * +0 throughout where the block is flagged, mean is not finite or not > 0, or (float)r is not finite.
+ * ratio must be finite and > 0.  out may not overlap x.
+ *
+ * A selection is exact, so results do not depend on the launch, the tiling or the route: BBT_RANK_ROUTE
+ * = lds (the block of a tile staged in LDS wherever it fits), global (re-read from global memory) or
+ * auto, BBT_RANK_DIGIT = 4 or 8 bits of a radix digit, BBT_RANK_WIDTH = 16, 32 or 64 elements per
+ * workgroup, read from the environment at every call, only change the speed.  No scratch.
+ * bbt_rank_info, for a launch of these sizes (n_spec = 1, skip = 0 for the time domain): the route it
+ * takes (1 lds, 2 global), the digit and the width, the LDS bytes of a workgroup, and lds_rows[3]: the
+ * longest block the lds route takes at widths 16, 32 and 64 with that digit.  It needs no device.
+ * Every refusal -- a null or misaligned pointer, a size out of range -- comes before anything is
+ * launched.  Asynchronous on `stream`. */
+int bbt_rank_stats(const float* x_dev, float* med_dev, float* mad_dev_or_null, int64_t n_spec, int64_t nbin,
+                   int64_t n_elem, int64_t m, int64_t skip, bbt_stream stream);
+int bbt_rank_standardize(const float* x_dev, float* out_dev, int64_t n_block, int64_t n, int64_t n_elem,
+                         bbt_stream stream);
+int bbt_rank_whiten(const float* x_dev, float* out_dev, int64_t n_spec, int64_t nbin, int64_t n_elem, int64_t m,
+                    int64_t skip, double ratio, bbt_stream stream);
+int bbt_rank_info(int64_t n_spec, int64_t nbin, int64_t n_elem, int64_t m, int64_t skip, int* route, int* digit,
+                  int* width, int64_t* lds_bytes, int64_t* lds_rows);
+
 /* ---- real-valued streams ------------------------------------------------------
  * float32 streams run through the complex kernels (the reference's rfft/irfft
  * engine paths, fourier/numpy.py:41-49).  Element-wise glue, n_total = number
