@@ -31,6 +31,9 @@ from .periodicity import (fluctuation_spectra, Whiten, whiten_samples, HarmonicS
                           harmonic_scales, harmonic_candidates, LongSpectra, long_spectra_samples, Accelerate,
                           accelerate_samples, MedianWhiten, median_whiten_samples, median_ratio)
 from . import periodicity
+from .ffa import (FFASearch, ffa_search_samples, ffa_transform_samples, ffa_shift, ffa_scales, ffa_period,
+                  ffa_candidates, ffa_plan)
+from . import ffa
 from .conversion import Real2Complex
 from .shaping import (ChangeSampleShapeBase, ChangeSampleShape, Reshape, Transpose, ReshapeAndTranspose,
                       GetItem, GetSlice)

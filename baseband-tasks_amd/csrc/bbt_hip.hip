@@ -35,6 +35,7 @@
 #include "sk_kernels.hpp"
 #include "dmt_kernels.hpp"
 #include "sps_kernels.hpp"
+#include "ffa_kernels.hpp"
 #include "hsum_kernels.hpp"
 #include "lspec_kernels.hpp"
 #include "accel_kernels.hpp"
@@ -48,7 +49,7 @@
 
 using namespace bbt;
 
-#define BBT_VERSION 168
+#define BBT_VERSION 169
 
 // ---------------------------------------------------------------------------
 // errors
@@ -3837,6 +3838,124 @@ extern "C" int bbt_sps_execute(bbt_sps_plan* p, const float* in_dev, int64_t n_i
         case 1: sps_launch<1>(p, g, in_dev, out_dev, st); break;
         case 2: sps_launch<2>(p, g, in_dev, out_dev, st); break;
         default: sps_launch<3>(p, g, in_dev, out_dev, st); break;
+    }
+    HIP_TRY(hipGetLastError());
+    return 0;
+}
+
+// ---------------------------------------------------------------------------
+// fast-folding period search on the (time, DM) plane (ffa_kernels.hpp; the tiling is ffa_geo.hpp's)
+struct bbt_ffa_plan {
+    long long n = 0, p_lo = 0, p_hi = 0, n_elem = 0, max_mp = 0;
+    int K = 0;
+    float* scratch = nullptr;        // the running segment sums, the c_k, the two buffers of the passes; grown on demand
+    long long scratch_floats = 0;
+};
+
+// BBT_FFA_FUSE: stages per pass (1, 2, 3); BBT_FFA_WIDTH: columns of an S/N workgroup at most (4, 8, 16,
+// 32).  Read at every call, for measuring and for the tests that walk the tilings; no value of the output
+// depends on either.  Anything else leaves the default.
+static int ffa_env_fuse() { return dmt_env("BBT_FFA_FUSE", {1, 2, 3}); }
+static int ffa_env_width() { return dmt_env("BBT_FFA_WIDTH", {4, 8, 16, 32}); }
+
+extern "C" int bbt_ffa_plan_destroy(bbt_ffa_plan* p) {
+    if (!p) return 0;
+    if (p->scratch) hipFree(p->scratch);
+    delete p;
+    return 0;
+}
+
+extern "C" int bbt_ffa_plan_create(bbt_ffa_plan** plan, int64_t n, int64_t p_lo, int64_t p_hi, int64_t n_widths,
+                                   int64_t n_elem) {
+    ARG_TRY(plan, "bbt_ffa_plan_create: null argument");
+    *plan = nullptr;
+    const char* err = ffa_sizes(n, p_lo, p_hi, n_widths, n_elem);
+    ARG_TRY(!err, "bbt_ffa_plan_create: %s", err ? err : "");
+    bbt_ffa_plan* p = new bbt_ffa_plan;
+    p->n = n, p->p_lo = p_lo, p->p_hi = p_hi, p->K = (int)n_widths, p->n_elem = n_elem;
+    p->max_mp = ffa_max_mp(n, p_lo, p_hi);
+    *plan = p;
+    return 0;
+}
+
+// the tiling the next call will use, the bytes of scratch the plan holds and the floats of scratch it needs
+// per column; for a base period `period` of the plan (else 0) its rows of data, rows and the 10 scales a_k
+extern "C" int bbt_ffa_plan_info(const bbt_ffa_plan* p, int64_t period, int* fuse, int* width, int64_t* rows,
+                                 int64_t* padded_rows, int64_t* scratch_bytes, int64_t* column_floats, float* scales) {
+    const int f = ffa_env_fuse(), w = ffa_env_width();
+    if (fuse) *fuse = f ? f : BBT_FFA_FUSE;
+    if (width) *width = w ? w : BBT_FFA_WIDTH;
+    if (scratch_bytes) *scratch_bytes = p ? p->scratch_floats * (long long)sizeof(float) : 0;
+    if (column_floats) *column_floats = p ? ffa_scratch(p->n, p->max_mp, 1) : 0;
+    if (rows) *rows = 0;
+    if (padded_rows) *padded_rows = 0;
+    if (p && period) {
+        ARG_TRY(period >= p->p_lo && period < p->p_hi, "bbt_ffa_plan_info: the period is not one of the plan's");
+        long long m, M;
+        int L;
+        ffa_rows(p->n, period, &m, &M, &L);
+        if (rows) *rows = m;
+        if (padded_rows) *padded_rows = M;
+        if (scales)
+            for (int k = 0; k < BBT_FFA_MAX_WIDTHS; ++k) scales[k] = k < p->K ? ffa_scale(period, m, k) : 0.f;
+    }
+    return 0;
+}
+
+static void ffa_launch_pass(const FfaGeo& g, const FfaPass& ps, const float* src, float* dst, int first, hipStream_t st) {
+    const dim3 grid((unsigned)ps.n_wg), block(BBT_FFA_THREADS);
+    switch (ps.lv) {
+        case 1: hipLaunchKernelGGL((k_ffa_pass<1>), grid, block, 0, st, src, dst, g, ps.s0, first); break;
+        case 2: hipLaunchKernelGGL((k_ffa_pass<2>), grid, block, 0, st, src, dst, g, ps.s0, first); break;
+        default: hipLaunchKernelGGL((k_ffa_pass<3>), grid, block, 0, st, src, dst, g, ps.s0, first); break;
+    }
+}
+
+// best[p - p_lo][4][e], pa <= p < pb, e0 <= e < e0 + ne, of out[p_hi - p_lo][4][n_elem], from the block
+// in[i][e], i < n, e < n_elem; the other cells of out are not touched.  One plan serves one stream at a
+// time: the scratch is the plan's.
+extern "C" int bbt_ffa_execute(bbt_ffa_plan* p, const float* in_dev, float* out_dev, int64_t e0, int64_t ne, int64_t pa,
+                               int64_t pb, bbt_stream stream) {
+    ARG_TRY(p && in_dev && out_dev, "bbt_ffa_execute: null argument");
+    ARG_TRY((((uintptr_t)in_dev | (uintptr_t)out_dev) & 3) == 0, "bbt_ffa_execute: arrays must be 4-byte aligned");
+    ARG_TRY(pa >= p->p_lo && pa < pb && pb <= p->p_hi, "bbt_ffa_execute: the periods %lld ... %lld are not the plan's",
+            (long long)pa, (long long)pb);
+    const int fuse = ffa_env_fuse(), width = ffa_env_width();
+    FfaGeo g = {};
+    for (long long q = pa; q < pb; ++q) {                       // (every refusal comes before any launch)
+        const char* err = ffa_geo(p->n, q, p->K, p->n_elem, e0, ne, fuse, width, &g);
+        ARG_TRY(!err, "bbt_ffa_execute: %s (p=%lld, e0=%lld, ne=%lld)", err ? err : "", q, (long long)e0, (long long)ne);
+    }
+    const long long need = ffa_scratch(p->n, p->max_mp, ne);
+    if (need > p->scratch_floats) {
+        if (p->scratch) HIP_TRY(hipFree(p->scratch));          // (waits for the launches that use it)
+        p->scratch = nullptr, p->scratch_floats = 0;
+        HIP_TRY(hipMalloc((void**)&p->scratch, (size_t)need * sizeof(float)));
+        p->scratch_floats = need;
+    }
+    hipStream_t st = (hipStream_t)stream;
+    double* pre = (double*)p->scratch;                         // (hipMalloc aligns far beyond 8 bytes)
+    float* c = p->scratch + 2 * ffa_prefix(p->n) * ne;
+    float* buf[2] = {c + BBT_FFA_MAX_WIDTHS * ne, c + (BBT_FFA_MAX_WIDTHS + p->max_mp) * ne};
+    const float* x = in_dev + e0;
+    const dim3 block(BBT_FFA_THREADS);
+    const unsigned per_column = (unsigned)((ne + BBT_FFA_THREADS - 1) / BBT_FFA_THREADS);
+    const long long n_seg = p->n / BBT_FFA_SEG * ne;
+    if (n_seg) hipLaunchKernelGGL(k_ffa_segments, dim3((unsigned)((n_seg + BBT_FFA_THREADS - 1) / BBT_FFA_THREADS)), block, 0, st, x, pre, g);
+    hipLaunchKernelGGL(k_ffa_prefix, dim3(per_column), block, 0, st, pre, g);
+    for (long long q = pa; q < pb; ++q) {
+        ffa_geo(p->n, q, p->K, p->n_elem, e0, ne, fuse, width, &g);
+        hipLaunchKernelGGL(k_ffa_total, dim3(per_column), block, 0, st, x, pre, c, g);
+        const float* src = x;
+        for (int i = 0; i < g.n_pass; ++i) {
+            const FfaPass ps = ffa_pass(g, i);
+            ffa_launch_pass(g, ps, src, buf[i & 1], (int)(i == 0), st);
+            src = buf[i & 1];
+        }
+        float* part = buf[g.n_pass & 1];
+        hipLaunchKernelGGL(k_ffa_snr, dim3((unsigned)(g.n_et * g.n_rg)), block, 0, st, src, c, part, g);
+        hipLaunchKernelGGL(k_ffa_merge, dim3((unsigned)((ne + BBT_FFA_MERGE_NX - 1) / BBT_FFA_MERGE_NX)), block, 0, st, part,
+                           out_dev + (q - p->p_lo) * 4 * p->n_elem + e0, p->n_elem, g);
     }
     HIP_TRY(hipGetLastError());
     return 0;

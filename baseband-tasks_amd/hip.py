@@ -118,6 +118,10 @@ SIGNATURES = {
     'bbt_sps_plan_info': [_vp, C.POINTER(_int), C.POINTER(_int), C.POINTER(_int), C.POINTER(_int), _pi64,
                           C.POINTER(C.c_float)],
     'bbt_sps_execute': [_vp, _vp, _i64, _vp, _i64, _vp],
+    'bbt_ffa_plan_create': [_pvp, _i64, _i64, _i64, _i64, _i64],
+    'bbt_ffa_plan_destroy': [_vp],
+    'bbt_ffa_plan_info': [_vp, _i64, C.POINTER(_int), C.POINTER(_int), _pi64, _pi64, _pi64, _pi64, C.POINTER(C.c_float)],
+    'bbt_ffa_execute': [_vp, _vp, _vp, _i64, _i64, _i64, _i64, _vp],
     'bbt_hsum_whiten': [_vp, _vp, _i64, _i64, _i64, _i64, _i64, _vp],
     'bbt_hsum_plan_create': [_pvp, _i64, _i64, _i64, _i64, _i64, C.POINTER(C.c_float)],
     'bbt_hsum_plan_destroy': [_vp],
@@ -170,7 +174,7 @@ SIGNATURES = {
 }
 
 #: oldest libbbt_hip.so whose entry points and argument meanings this binding assumes
-MIN_LIB_VERSION = 168
+MIN_LIB_VERSION = 169
 
 _lib = None
 _lock = threading.Lock()
@@ -1757,6 +1761,53 @@ class SpsPlan(_Plan):
             raise ValueError("SpsPlan.execute: float32 DeviceArrays of n_in * n_elem and n_blocks * 3 * n_elem "
                              "values are needed")
         check(lib().bbt_sps_execute(self._h, in_dev.ptr_to_read(), n_in, out_dev.ptr, n_blocks, _stream))
+
+
+#: bounds of the fast-folding search (csrc/ffa_geo.hpp)
+FFA_MIN_P, FFA_MAX_P, FFA_MAX_ROWS, FFA_MAX_WIDTHS, FFA_MAX_LANE = 4, 1025, 65536, 10, 1 << 30
+
+
+def ffa_info(plan=None, period=0):
+    """The tiling the next call will use (BBT_FFA_FUSE, BBT_FFA_WIDTH) and, for a plan, the bytes of scratch it
+    holds and the floats of scratch it needs per column; for a base period of the plan also its rows of data
+    ``m``, its rows ``M`` and the library's 10 scales a_k (0 beyond ``n_widths``)."""
+    fuse, width, rows, padded, scratch, column = _int(0), _int(0), _i64(0), _i64(0), _i64(0), _i64(0)
+    scales = (C.c_float * FFA_MAX_WIDTHS)()
+    check(lib().bbt_ffa_plan_info(plan._h if plan is not None else None, int(period), C.byref(fuse), C.byref(width),
+                                  C.byref(rows), C.byref(padded), C.byref(scratch), C.byref(column), scales))
+    return dict(fuse=fuse.value, width=width.value, m=rows.value, M=padded.value, scratch_bytes=scratch.value,
+                column_floats=column.value, scales=np.array(scales[:], dtype=np.float32))
+
+
+class FfaPlan(_Plan):
+    """best[p - p_lo, :, e] = (snr, shift, level, phase) of the best boxcar over every fold of a block of ``n``
+    samples at the base period ``p`` (bbt_ffa_* in include/bbt_hip.h; `ffa.ffa_search_samples` is the NumPy
+    restatement).  The plan owns the scratch of the fold stages."""
+    _destroy = 'bbt_ffa_plan_destroy'
+
+    def __init__(self, n, periods, n_widths, n_elem=1):
+        super().__init__()
+        self.n, self.n_widths, self.n_elem = int(n), int(n_widths), int(n_elem)
+        self.p_lo, self.p_hi = (int(p) for p in periods)
+        check(lib().bbt_ffa_plan_create(C.byref(self._h), self.n, self.p_lo, self.p_hi, self.n_widths, self.n_elem))
+
+    def info(self, period=0):
+        """The tiling the next call will use, the scratch, and the rows and scales of a base period (`ffa_info`)."""
+        return ffa_info(self, period)
+
+    def execute(self, in_dev, out_dev, e0=0, ne=None, pa=None, pb=None):
+        """``in_dev``: float32, one block of ``n * n_elem`` values at least; ``out_dev``: float32, ``(p_hi - p_lo) * 4
+        * n_elem``.  Only the columns ``e0 ... e0 + ne`` and the base periods ``pa ... pb`` are searched and
+        written (default: all)."""
+        e0 = int(e0)
+        ne = self.n_elem - e0 if ne is None else int(ne)
+        pa = self.p_lo if pa is None else int(pa)
+        pb = self.p_hi if pb is None else int(pb)
+        if (in_dev.dtype != np.float32 or out_dev.dtype != np.float32 or in_dev.size < self.n * self.n_elem
+                or out_dev.size < (self.p_hi - self.p_lo) * 4 * self.n_elem):
+            raise ValueError("FfaPlan.execute: float32 DeviceArrays of n * n_elem and (p_hi - p_lo) * 4 * n_elem "
+                             "values are needed")
+        check(lib().bbt_ffa_execute(self._h, in_dev.ptr_to_read(), out_dev.ptr, e0, ne, pa, pb, _stream))
 
 
 #: bounds of the periodicity search (csrc/hsum_geo.hpp)

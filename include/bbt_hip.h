@@ -48,6 +48,7 @@ typedef struct bbt_pfb_plan bbt_pfb_plan;
 typedef struct bbt_shift_plan bbt_shift_plan;
 typedef struct bbt_dmt_plan bbt_dmt_plan;
 typedef struct bbt_sps_plan bbt_sps_plan;
+typedef struct bbt_ffa_plan bbt_ffa_plan;
 typedef struct bbt_hsum_plan bbt_hsum_plan;
 typedef struct bbt_lspec_plan bbt_lspec_plan;
 typedef struct bbt_accel_plan bbt_accel_plan;
@@ -593,6 +594,36 @@ int bbt_sps_plan_info(const bbt_sps_plan* plan, int* width, int* fuse, int* spli
                       int64_t* scratch_bytes, float* scales);
 int bbt_sps_execute(bbt_sps_plan* plan, const float* in_dev, int64_t n_in, float* out_dev, int64_t n_blocks,
                     bbt_stream stream);
+
+/* ---- fast-folding period search on the (time, DM) plane: FFASearch -----
+ * A block is x[i][e], i < n, e < n_elem, float32, element fastest; every e is an independent column.
+ * A plan holds n, the base periods p_lo <= p < p_hi in whole samples (4 <= p_lo < p_hi <= 1025, n / (p_hi -
+ * 1) >= 2, n / p_lo <= 65536) and n_widths = K (1 ... 10, 2^(K-1) < p_lo).
+ *
+ * Per column and p: m = n / p rows d[r][j] = x[r p + j], padded with +0 to M rows, the power of two with M /
+ * 2 < m <= M.  For G = 2, 4, ... M every group of G rows becomes out[t] = A[t >> 1] + roll(B[t >> 1], -((t + 1)
+ * >> 1)), t < G, with A and B the transformed halves of the group and roll(v, -c)[j] = v[(j + c) mod p]: one
+ * rounded float32 add each, padded rows included.  Row t is the fold at p + t / (M - 1) samples.  Boxcars
+ * along phase: S_0 = row t, S_{k+1}[j] = S_k[j] + S_k[(j + 2^k) mod p].  With T the float64 sum of the m p
+ * used samples in the two-level order of bbt_sps_standardize, c_k = (float)((T 2^k) / p) and a_k =
+ * (float)sqrt(p / (2^k (p - 2^k) m)), snr = (S_k[t][j] - c_k) * a_k, one rounded float32 subtract and one
+ * rounded multiply.  The winner over all (t, k, j) -- the largest snr, among equals the smaller t, then k,
+ * then j; a NaN never wins; (-inf, 0, 0, 0) if there is nothing else -- is written as out[p - p_lo][0 ... 3][e]
+ * = snr, t, k, j.
+ *
+ * bbt_ffa_execute does this for the columns e0 <= e < e0 + ne and the periods pa <= p < pb of out[p_hi -
+ * p_lo][4][n_elem] and touches no other cell.  The plan owns the scratch, grown to the most columns seen and
+ * freed on destroy: it serves one stream at a time.  bbt_ffa_plan_info reports the tiling the next call
+ * will use (BBT_FFA_FUSE: stages per pass, 1, 2 or 3; BBT_FFA_WIDTH: columns of an S/N workgroup at most, 4,
+ * 8, 16 or 32), the bytes of scratch held, the floats of scratch needed per column and, for a base period
+ * of the plan, m, M and the 10 scales a_k (0 beyond K); plan may be null (the tiling only).
+ * Every refusal comes before anything is launched.  Asynchronous on `stream`. */
+int bbt_ffa_plan_create(bbt_ffa_plan** plan, int64_t n, int64_t p_lo, int64_t p_hi, int64_t n_widths, int64_t n_elem);
+int bbt_ffa_plan_destroy(bbt_ffa_plan* plan);
+int bbt_ffa_plan_info(const bbt_ffa_plan* plan, int64_t period, int* fuse, int* width, int64_t* rows,
+                      int64_t* padded_rows, int64_t* scratch_bytes, int64_t* column_floats, float* scales);
+int bbt_ffa_execute(bbt_ffa_plan* plan, const float* in_dev, float* out_dev, int64_t e0, int64_t ne, int64_t pa,
+                    int64_t pb, bbt_stream stream);
 
 /* ---- periodicity search on stacked fluctuation spectra: Whiten, HarmonicSearch -----
  * A chunk is p[s][j][e], s < n_spec spectra of nbin bins, float32, element fastest; every (s, e) is an

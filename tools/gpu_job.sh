@@ -14,6 +14,7 @@
 #   chain   LABEL=<label>     kernel trace of one chain of tools/default_device_reads.py -> tools/chain_timeline.py
 #   prof3   NAME=<n> CMD=".." kernel stats + FETCH_SIZE + WRITE_SIZE (three separate runs) of a command
 #   sq      [CMD=..]          SQ counters (two passes of 8) of a command (default: headline, 96 blocks)
+#   ffa     [ARGS=..] [ROW=n20_d64]   tools/bench_ffa.py $ARGS, then one row under a kernel trace: fold passes against the S/N pass
 #   gloo2                     bench.py --full rehearsal of two ranks sharing this GPU (gloo)
 #   evidence                  round-end: suite, profiles of every config, timeline, SQ counters, bench
 #                             lines, next rows, generic lengths, host path (then: tools/summarise.sh)
@@ -115,6 +116,13 @@ prof3)
     prof3 ${NAME:?NAME} $CMD ;;
 sq)
     sq ${NAME:-headline} ${CMD:-python3 $R/bench.py --steps 2 --warmup 1 --blocks 96 --no-cpu --no-verify --no-host-path --no-traffic} ;;
+ffa)
+    timeout -k 10 1100 python3 tools/bench_ffa.py --out $OUT/ffa_bench.jsonl $ARGS 2> $OUT/ffa_bench.err; rc=$?; say "ffa bench rc=$rc"
+    [ $rc -eq 0 ] || { tail -5 $OUT/ffa_bench.err; exit 1; }
+    mkdir -p $OUT/prof
+    ( cd /tmp
+      timeout -k 10 400 rocprofv3 --kernel-trace --stats -d $OUT/prof/ffa -o run -- python3 $R/tools/bench_ffa.py --child --reps 1 ${ROW:-n20_d64} > $OUT/prof/ffa.log 2>&1; say "ffa trace rc=$?" )
+    python3 tools/rocprof_db.py stats $OUT/prof/ffa/run_results.db $OUT/ffa_kernel_stats.csv ;;
 gloo2)
     gloo2 ;;
 evidence)

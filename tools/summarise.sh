@@ -20,4 +20,7 @@ cp $G/bench_one.jsonl profiles/${TAG}_bench_one.jsonl
 [ -f $G/host_path.jsonl ] && cp $G/host_path.jsonl profiles/${TAG}_host_path.jsonl
 [ -f $G/pcie.txt ] && grep -v amdgpu.ids $G/pcie.txt > profiles/${TAG}_pcie_probe.txt
 [ -f $G/import_order.txt ] && grep -v amdgpu.ids $G/import_order.txt > profiles/${TAG}_import_order.txt
+# (after `bash tools/gpu_job.sh ffa TAG=<tag>`)
+[ -f $G/ffa_bench.jsonl ] && cat $G/ffa_bench.jsonl >> profiles/ffa_bench.jsonl
+[ -f $G/ffa_kernel_stats.csv ] && cp $G/ffa_kernel_stats.csv profiles/ffa_kernel_stats.csv
 ls profiles | grep ${TAG}_ | wc -l
