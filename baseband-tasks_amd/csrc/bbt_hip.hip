@@ -78,6 +78,11 @@ static int fail(const char* fmt, ...) {
         if (!(cond)) return fail(__VA_ARGS__); \
     } while (0)
 
+// are the arrays of 4-byte elements aligned to them? (a null pointer is)
+static inline bool aligned4(const void* a, const void* b, const void* c = nullptr) {
+    return (((uintptr_t)a | (uintptr_t)b | (uintptr_t)c) & 3) == 0;
+}
+
 // ---------------------------------------------------------------------------
 // twiddle tables, per device
 struct FftTables {
@@ -2759,8 +2764,7 @@ static int modulate_args(const char* who, const void* in_dev, void* out_dev, int
     ARG_TRY(gain_stride == 0 || n_float == gain_stride || n_float == 2 * gain_stride,
             "%s: the gain stride must be 0 or the elements of a sample (%lld floats, stride %lld)", who,
             (long long)n_float, (long long)gain_stride);
-    ARG_TRY((((uintptr_t)in_dev | (uintptr_t)out_dev | (uintptr_t)gain_dev) & 3) == 0, "%s: arrays must be 4-byte aligned",
-            who);
+    ARG_TRY(aligned4(in_dev, out_dev, gain_dev), "%s: arrays must be 4-byte aligned", who);
     A->in = (const float*)in_dev;
     A->out = (float*)out_dev;
     A->n_in = n_in;
@@ -3638,18 +3642,13 @@ extern "C" int bbt_shift_execute(bbt_shift_plan* p, const void* in_dev, void* ou
 }
 
 // ---------------------------------------------------------------------------
-// incoherent dedispersion over many trial DMs (dmt_kernels.hpp; the tiling is dmt_geo.hpp's)
-struct bbt_dmt_plan {
-    int ndm = 0, nchan = 0, n_rest = 0, ndm_pad = 0, span = 0;
-    int* tab = nullptr;              // [nchan][ndm_pad], padding entries 0
-    float* scratch = nullptr;        // the transposed chunk, grown on demand
-    long long scratch_floats = 0;
-};
+// what the sections of the search chain share (dmt, sps, ffa, hsum, lspec, accel, rank)
 
-// BBT_DMT_TILE: output times of a workgroup (64, 128, 256); BBT_DMT_TRIALS: trials a thread holds
-// (1, 2, 4, 8, 16).  For measuring and for the tests that walk the tilings; no value of the output
-// depends on either.  Anything else leaves the default.
-static int dmt_env(const char* name, std::initializer_list<int> allowed) {
+// A tiling or routing knob from the environment: the value of `name` if it is one of `allowed`, else 0,
+// which stands for the section's default.  The contract of every knob below: it is read at every call,
+// for measuring and for the tests that walk the tilings and routes; no value of the output depends on
+// it; anything else leaves the default.
+static int env_knob(const char* name, std::initializer_list<int> allowed) {
     const char* e = getenv(name);
     if (e && *e) {
         const int v = atoi(e);
@@ -3659,10 +3658,42 @@ static int dmt_env(const char* name, std::initializer_list<int> allowed) {
     return 0;
 }
 
+// The scratch a plan owns, grown on demand and never shrunk.  One plan serves one stream at a time:
+// the scratch is the plan's.
+struct PlanScratch {
+    void* ptr = nullptr;
+    size_t bytes = 0;
+    int reserve(size_t need) {
+        if (need <= bytes) return 0;
+        if (ptr) HIP_TRY(hipFree(ptr));          // (waits for the launches that use it)
+        ptr = nullptr, bytes = 0;
+        HIP_TRY(hipMalloc(&ptr, need));
+        bytes = need;
+        return 0;
+    }
+    void release() {
+        if (ptr) (void)hipFree(ptr);
+        ptr = nullptr, bytes = 0;
+    }
+};
+
+// ---------------------------------------------------------------------------
+// incoherent dedispersion over many trial DMs (dmt_kernels.hpp; the tiling is dmt_geo.hpp's)
+struct bbt_dmt_plan {
+    int ndm = 0, nchan = 0, n_rest = 0, ndm_pad = 0, span = 0;
+    int* tab = nullptr;              // [nchan][ndm_pad], padding entries 0
+    PlanScratch scratch;             // the transposed chunk
+};
+
+// BBT_DMT_TILE: output times of a workgroup (64, 128, 256); BBT_DMT_TRIALS: trials a thread holds
+// (1, 2, 4, 8, 16).
+static int dmt_env_tile() { return env_knob("BBT_DMT_TILE", {64, 128, 256}); }
+static int dmt_env_trials() { return env_knob("BBT_DMT_TRIALS", {1, 2, 4, 8, 16}); }
+
 extern "C" int bbt_dmt_plan_destroy(bbt_dmt_plan* p) {
     if (!p) return 0;
     if (p->tab) hipFree(p->tab);
-    if (p->scratch) hipFree(p->scratch);
+    p->scratch.release();
     delete p;
     return 0;
 }
@@ -3696,11 +3727,11 @@ extern "C" int bbt_dmt_plan_create(bbt_dmt_plan** plan, const int32_t* offsets_h
 extern "C" int bbt_dmt_plan_info(const bbt_dmt_plan* p, int64_t* span, int* tile_t, int* trials,
                                  int64_t* scratch_bytes) {
     ARG_TRY(p, "bbt_dmt_plan_info: null argument");
-    const int t = dmt_env("BBT_DMT_TILE", {64, 128, 256}), b = dmt_env("BBT_DMT_TRIALS", {1, 2, 4, 8, 16});
+    const int t = dmt_env_tile(), b = dmt_env_trials();
     if (span) *span = p->span;
     if (tile_t) *tile_t = t ? t : BBT_DMT_TILE;
     if (trials) *trials = b ? b : BBT_DMT_DB;
-    if (scratch_bytes) *scratch_bytes = p->scratch_floats * (long long)sizeof(float);
+    if (scratch_bytes) *scratch_bytes = (int64_t)p->scratch.bytes;
     return 0;
 }
 
@@ -3709,29 +3740,24 @@ extern "C" int bbt_dmt_plan_info(const bbt_dmt_plan* p, int64_t* span, int* tile
 extern "C" int bbt_dmt_execute(bbt_dmt_plan* p, const float* in_dev, int64_t n_in, float* out_dev, int64_t n_out,
                                bbt_stream stream) {
     ARG_TRY(p && in_dev && out_dev, "bbt_dmt_execute: null argument");
-    ARG_TRY((((uintptr_t)in_dev | (uintptr_t)out_dev) & 3) == 0, "bbt_dmt_execute: arrays must be 4-byte aligned");
+    ARG_TRY(aligned4(in_dev, out_dev), "bbt_dmt_execute: arrays must be 4-byte aligned");
     DmtGeo g = {};
-    const char* err = dmt_geo(n_in, n_out, p->nchan, p->n_rest, p->ndm, p->span,
-                              dmt_env("BBT_DMT_TILE", {64, 128, 256}), dmt_env("BBT_DMT_TRIALS", {1, 2, 4, 8, 16}), &g);
+    const char* err = dmt_geo(n_in, n_out, p->nchan, p->n_rest, p->ndm, p->span, dmt_env_tile(), dmt_env_trials(), &g);
     ARG_TRY(!err, "bbt_dmt_execute: %s (n_in=%lld, n_out=%lld, span=%d)", err ? err : "", (long long)n_in,
             (long long)n_out, p->span);
-    if (g.scratch > p->scratch_floats) {
-        if (p->scratch) HIP_TRY(hipFree(p->scratch));          // (waits for the launches that use it)
-        p->scratch = nullptr, p->scratch_floats = 0;
-        HIP_TRY(hipMalloc((void**)&p->scratch, (size_t)g.scratch * sizeof(float)));
-        p->scratch_floats = g.scratch;
-    }
+    if (p->scratch.reserve((size_t)g.scratch * sizeof(float))) return 1;
+    float* scratch = (float*)p->scratch.ptr;
     hipStream_t st = (hipStream_t)stream;
     hipLaunchKernelGGL(k_dmt_transpose, dim3((unsigned)g.tr_t, (unsigned)g.tr_e), dim3(BBT_DMT_THREADS), 0, st, in_dev,
-                       p->scratch, (long long)n_in, p->nchan * p->n_rest, g.pitch);
+                       scratch, (long long)n_in, p->nchan * p->n_rest, g.pitch);
     HIP_TRY(hipGetLastError());
     const dim3 grid((unsigned)g.n_wg), block(BBT_DMT_THREADS);
     switch (g.db) {
-        case 1: hipLaunchKernelGGL((k_dmt_sweep<1>), grid, block, 0, st, p->scratch, p->tab, out_dev, g); break;
-        case 2: hipLaunchKernelGGL((k_dmt_sweep<2>), grid, block, 0, st, p->scratch, p->tab, out_dev, g); break;
-        case 4: hipLaunchKernelGGL((k_dmt_sweep<4>), grid, block, 0, st, p->scratch, p->tab, out_dev, g); break;
-        case 8: hipLaunchKernelGGL((k_dmt_sweep<8>), grid, block, 0, st, p->scratch, p->tab, out_dev, g); break;
-        default: hipLaunchKernelGGL((k_dmt_sweep<16>), grid, block, 0, st, p->scratch, p->tab, out_dev, g); break;
+        case 1: hipLaunchKernelGGL((k_dmt_sweep<1>), grid, block, 0, st, scratch, p->tab, out_dev, g); break;
+        case 2: hipLaunchKernelGGL((k_dmt_sweep<2>), grid, block, 0, st, scratch, p->tab, out_dev, g); break;
+        case 4: hipLaunchKernelGGL((k_dmt_sweep<4>), grid, block, 0, st, scratch, p->tab, out_dev, g); break;
+        case 8: hipLaunchKernelGGL((k_dmt_sweep<8>), grid, block, 0, st, scratch, p->tab, out_dev, g); break;
+        default: hipLaunchKernelGGL((k_dmt_sweep<16>), grid, block, 0, st, scratch, p->tab, out_dev, g); break;
     }
     HIP_TRY(hipGetLastError());
     return 0;
@@ -3742,24 +3768,22 @@ extern "C" int bbt_dmt_execute(bbt_dmt_plan* p, const float* in_dev, int64_t n_i
 struct bbt_sps_plan {
     long long n = 0, n_elem = 0;
     int K = 0;
-    float* scratch = nullptr;        // the partial sums between passes, grown on demand
-    long long scratch_floats = 0;
+    PlanScratch scratch;             // the partial sums between passes
 };
 
 // BBT_SPS_WIDTH: elements of a boxcar workgroup (16, 32, 64); BBT_SPS_FUSE: levels per pass (1, 2, 3);
 // BBT_SPS_SPLIT: threads that share a (block, element) at most (1, 2, 4, 8, 16); BBT_SPS_STD_ROWS: threads
-// along the segments in Standardize (1, 2, 4, 8, 16).  For measuring and for the tests that walk the
-// tilings; no value of the output depends on any.  Anything else leaves the default.
-static int sps_env_width() { return dmt_env("BBT_SPS_WIDTH", {16, 32, 64}); }
-static int sps_env_fuse() { return dmt_env("BBT_SPS_FUSE", {1, 2, 3}); }
-static int sps_env_split() { return dmt_env("BBT_SPS_SPLIT", {1, 2, 4, 8, 16}); }
-static int sps_env_rows() { return dmt_env("BBT_SPS_STD_ROWS", {1, 2, 4, 8, 16}); }
+// along the segments in Standardize (1, 2, 4, 8, 16).
+static int sps_env_width() { return env_knob("BBT_SPS_WIDTH", {16, 32, 64}); }
+static int sps_env_fuse() { return env_knob("BBT_SPS_FUSE", {1, 2, 3}); }
+static int sps_env_split() { return env_knob("BBT_SPS_SPLIT", {1, 2, 4, 8, 16}); }
+static int sps_env_rows() { return env_knob("BBT_SPS_STD_ROWS", {1, 2, 4, 8, 16}); }
 
 // out[b * n + t][e] = (x[b * n + t][e] - mean) * (1 / sd) of block b < n_block, element e < n_elem
 extern "C" int bbt_sps_standardize(const float* x_dev, float* out_dev, int64_t n_block, int64_t n, int64_t n_elem,
                                    bbt_stream stream) {
     ARG_TRY(x_dev && out_dev, "bbt_sps_standardize: null argument");
-    ARG_TRY((((uintptr_t)x_dev | (uintptr_t)out_dev) & 3) == 0, "bbt_sps_standardize: arrays must be 4-byte aligned");
+    ARG_TRY(aligned4(x_dev, out_dev), "bbt_sps_standardize: arrays must be 4-byte aligned");
     StdGeo g = {};
     const char* err = sps_std_geo(n_block, n, n_elem, sps_env_rows(), &g);
     ARG_TRY(!err, "bbt_sps_standardize: %s (n_block=%lld, n=%lld, n_elem=%lld)", err ? err : "", (long long)n_block,
@@ -3772,7 +3796,7 @@ extern "C" int bbt_sps_standardize(const float* x_dev, float* out_dev, int64_t n
 
 extern "C" int bbt_sps_plan_destroy(bbt_sps_plan* p) {
     if (!p) return 0;
-    if (p->scratch) hipFree(p->scratch);
+    p->scratch.release();
     delete p;
     return 0;
 }
@@ -3797,7 +3821,7 @@ extern "C" int bbt_sps_plan_info(const bbt_sps_plan* p, int* width, int* fuse, i
     if (fuse) *fuse = f ? f : BBT_SPS_FUSE;
     if (split) *split = s ? s : BBT_SPS_SPLIT;
     if (std_rows) *std_rows = r ? r : BBT_SPS_STD_ROWS;
-    if (scratch_bytes) *scratch_bytes = p ? p->scratch_floats * (long long)sizeof(float) : 0;
+    if (scratch_bytes) *scratch_bytes = p ? (int64_t)p->scratch.bytes : 0;
     if (scales)
         for (int k = 0; k < BBT_SPS_MAX_WIDTHS; ++k) scales[k] = sps_scale(k);
     return 0;
@@ -3805,7 +3829,8 @@ extern "C" int bbt_sps_plan_info(const bbt_sps_plan* p, int* width, int* fuse, i
 
 template <int F>
 static void sps_launch(const bbt_sps_plan* p, const SpsGeo& g, const float* in_dev, float* out_dev, hipStream_t st) {
-    float* buf[2] = {p->scratch, p->scratch + (g.n_pass > 2 ? g.n_in * g.n_elem : 0)};
+    float* scratch = (float*)p->scratch.ptr;
+    float* buf[2] = {scratch, scratch + (g.n_pass > 2 ? g.n_in * g.n_elem : 0)};
     const float* src = in_dev;
     for (int q = 0; q < g.n_pass; ++q) {
         const SpsPass ps = sps_pass(g, q);
@@ -3822,17 +3847,12 @@ static void sps_launch(const bbt_sps_plan* p, const SpsGeo& g, const float* in_d
 extern "C" int bbt_sps_execute(bbt_sps_plan* p, const float* in_dev, int64_t n_in, float* out_dev, int64_t n_blocks,
                                bbt_stream stream) {
     ARG_TRY(p && in_dev && out_dev, "bbt_sps_execute: null argument");
-    ARG_TRY((((uintptr_t)in_dev | (uintptr_t)out_dev) & 3) == 0, "bbt_sps_execute: arrays must be 4-byte aligned");
+    ARG_TRY(aligned4(in_dev, out_dev), "bbt_sps_execute: arrays must be 4-byte aligned");
     SpsGeo g = {};
     const char* err = sps_geo(n_in, n_blocks, p->n, p->K, p->n_elem, sps_env_width(), sps_env_fuse(), sps_env_split(), &g);
     ARG_TRY(!err, "bbt_sps_execute: %s (n_in=%lld, n_blocks=%lld, n=%lld)", err ? err : "", (long long)n_in,
             (long long)n_blocks, p->n);
-    if (g.scratch > p->scratch_floats) {
-        if (p->scratch) HIP_TRY(hipFree(p->scratch));          // (waits for the launches that use it)
-        p->scratch = nullptr, p->scratch_floats = 0;
-        HIP_TRY(hipMalloc((void**)&p->scratch, (size_t)g.scratch * sizeof(float)));
-        p->scratch_floats = g.scratch;
-    }
+    if (p->scratch.reserve((size_t)g.scratch * sizeof(float))) return 1;
     hipStream_t st = (hipStream_t)stream;
     switch (g.fuse) {
         case 1: sps_launch<1>(p, g, in_dev, out_dev, st); break;
@@ -3848,19 +3868,17 @@ extern "C" int bbt_sps_execute(bbt_sps_plan* p, const float* in_dev, int64_t n_i
 struct bbt_ffa_plan {
     long long n = 0, p_lo = 0, p_hi = 0, n_elem = 0, max_mp = 0;
     int K = 0;
-    float* scratch = nullptr;        // the running segment sums, the c_k, the two buffers of the passes; grown on demand
-    long long scratch_floats = 0;
+    PlanScratch scratch;             // the running segment sums, the c_k, the two buffers of the passes
 };
 
 // BBT_FFA_FUSE: stages per pass (1, 2, 3); BBT_FFA_WIDTH: columns of an S/N workgroup at most (4, 8, 16,
-// 32).  Read at every call, for measuring and for the tests that walk the tilings; no value of the output
-// depends on either.  Anything else leaves the default.
-static int ffa_env_fuse() { return dmt_env("BBT_FFA_FUSE", {1, 2, 3}); }
-static int ffa_env_width() { return dmt_env("BBT_FFA_WIDTH", {4, 8, 16, 32}); }
+// 32).
+static int ffa_env_fuse() { return env_knob("BBT_FFA_FUSE", {1, 2, 3}); }
+static int ffa_env_width() { return env_knob("BBT_FFA_WIDTH", {4, 8, 16, 32}); }
 
 extern "C" int bbt_ffa_plan_destroy(bbt_ffa_plan* p) {
     if (!p) return 0;
-    if (p->scratch) hipFree(p->scratch);
+    p->scratch.release();
     delete p;
     return 0;
 }
@@ -3885,7 +3903,7 @@ extern "C" int bbt_ffa_plan_info(const bbt_ffa_plan* p, int64_t period, int* fus
     const int f = ffa_env_fuse(), w = ffa_env_width();
     if (fuse) *fuse = f ? f : BBT_FFA_FUSE;
     if (width) *width = w ? w : BBT_FFA_WIDTH;
-    if (scratch_bytes) *scratch_bytes = p ? p->scratch_floats * (long long)sizeof(float) : 0;
+    if (scratch_bytes) *scratch_bytes = p ? (int64_t)p->scratch.bytes : 0;
     if (column_floats) *column_floats = p ? ffa_scratch(p->n, p->max_mp, 1) : 0;
     if (rows) *rows = 0;
     if (padded_rows) *padded_rows = 0;
@@ -3917,7 +3935,7 @@ static void ffa_launch_pass(const FfaGeo& g, const FfaPass& ps, const float* src
 extern "C" int bbt_ffa_execute(bbt_ffa_plan* p, const float* in_dev, float* out_dev, int64_t e0, int64_t ne, int64_t pa,
                                int64_t pb, bbt_stream stream) {
     ARG_TRY(p && in_dev && out_dev, "bbt_ffa_execute: null argument");
-    ARG_TRY((((uintptr_t)in_dev | (uintptr_t)out_dev) & 3) == 0, "bbt_ffa_execute: arrays must be 4-byte aligned");
+    ARG_TRY(aligned4(in_dev, out_dev), "bbt_ffa_execute: arrays must be 4-byte aligned");
     ARG_TRY(pa >= p->p_lo && pa < pb && pb <= p->p_hi, "bbt_ffa_execute: the periods %lld ... %lld are not the plan's",
             (long long)pa, (long long)pb);
     const int fuse = ffa_env_fuse(), width = ffa_env_width();
@@ -3926,16 +3944,10 @@ extern "C" int bbt_ffa_execute(bbt_ffa_plan* p, const float* in_dev, float* out_
         const char* err = ffa_geo(p->n, q, p->K, p->n_elem, e0, ne, fuse, width, &g);
         ARG_TRY(!err, "bbt_ffa_execute: %s (p=%lld, e0=%lld, ne=%lld)", err ? err : "", q, (long long)e0, (long long)ne);
     }
-    const long long need = ffa_scratch(p->n, p->max_mp, ne);
-    if (need > p->scratch_floats) {
-        if (p->scratch) HIP_TRY(hipFree(p->scratch));          // (waits for the launches that use it)
-        p->scratch = nullptr, p->scratch_floats = 0;
-        HIP_TRY(hipMalloc((void**)&p->scratch, (size_t)need * sizeof(float)));
-        p->scratch_floats = need;
-    }
+    if (p->scratch.reserve((size_t)ffa_scratch(p->n, p->max_mp, ne) * sizeof(float))) return 1;
     hipStream_t st = (hipStream_t)stream;
-    double* pre = (double*)p->scratch;                         // (hipMalloc aligns far beyond 8 bytes)
-    float* c = p->scratch + 2 * ffa_prefix(p->n) * ne;
+    double* pre = (double*)p->scratch.ptr;                     // (hipMalloc aligns far beyond 8 bytes)
+    float* c = (float*)p->scratch.ptr + 2 * ffa_prefix(p->n) * ne;
     float* buf[2] = {c + BBT_FFA_MAX_WIDTHS * ne, c + (BBT_FFA_MAX_WIDTHS + p->max_mp) * ne};
     const float* x = in_dev + e0;
     const dim3 block(BBT_FFA_THREADS);
@@ -3971,17 +3983,16 @@ struct bbt_hsum_plan {
 
 // BBT_HSUM_WIDTH: elements of a search workgroup (16, 32, 64); BBT_HSUM_SPLIT: threads that share a
 // (spectrum, block, element) at most (1, 2, 4, 8, 16); BBT_HSUM_ROWS: threads along the segments in Whiten
-// (1, 2, 4, 8, 16).  Read at every call, for measuring and for the tests that walk the tilings; no value
-// of the output depends on any.  Anything else leaves the default.
-static int hsum_env_width() { return dmt_env("BBT_HSUM_WIDTH", {16, 32, 64}); }
-static int hsum_env_split() { return dmt_env("BBT_HSUM_SPLIT", {1, 2, 4, 8, 16}); }
-static int hsum_env_rows() { return dmt_env("BBT_HSUM_ROWS", {1, 2, 4, 8, 16}); }
+// (1, 2, 4, 8, 16).
+static int hsum_env_width() { return env_knob("BBT_HSUM_WIDTH", {16, 32, 64}); }
+static int hsum_env_split() { return env_knob("BBT_HSUM_SPLIT", {1, 2, 4, 8, 16}); }
+static int hsum_env_rows() { return env_knob("BBT_HSUM_ROWS", {1, 2, 4, 8, 16}); }
 
 // out[s][j][e] = x[s][j][e] * (1 / mean of the block of m bins that holds j), +0 for j < skip
 extern "C" int bbt_hsum_whiten(const float* x_dev, float* out_dev, int64_t n_spec, int64_t nbin, int64_t n_elem,
                                int64_t m, int64_t skip, bbt_stream stream) {
     ARG_TRY(x_dev && out_dev, "bbt_hsum_whiten: null argument");
-    ARG_TRY((((uintptr_t)x_dev | (uintptr_t)out_dev) & 3) == 0, "bbt_hsum_whiten: arrays must be 4-byte aligned");
+    ARG_TRY(aligned4(x_dev, out_dev), "bbt_hsum_whiten: arrays must be 4-byte aligned");
     WhitenGeo g = {};
     const char* err = hsum_whiten_geo(n_spec, nbin, n_elem, m, skip, hsum_env_rows(), &g);
     ARG_TRY(!err, "bbt_hsum_whiten: %s (n_spec=%lld, nbin=%lld, n_elem=%lld, m=%lld, skip=%lld)", err ? err : "",
@@ -4030,7 +4041,7 @@ extern "C" int bbt_hsum_plan_info(const bbt_hsum_plan* p, int* width, int* split
 extern "C" int bbt_hsum_execute(bbt_hsum_plan* p, const float* in_dev, int64_t n_spec, float* out_dev,
                                 bbt_stream stream) {
     ARG_TRY(p && in_dev && out_dev, "bbt_hsum_execute: null argument");
-    ARG_TRY((((uintptr_t)in_dev | (uintptr_t)out_dev) & 3) == 0, "bbt_hsum_execute: arrays must be 4-byte aligned");
+    ARG_TRY(aligned4(in_dev, out_dev), "bbt_hsum_execute: arrays must be 4-byte aligned");
     HsumGeo g = {};
     const char* err = hsum_geo(n_spec, p->nbin, p->n, p->K, p->lo, p->n_elem, hsum_env_width(), hsum_env_split(), &g);
     ARG_TRY(!err, "bbt_hsum_execute: %s (n_spec=%lld, nbin=%lld, n=%lld)", err ? err : "", (long long)n_spec, p->nbin,
@@ -4055,15 +4066,13 @@ extern "C" int bbt_hsum_execute(bbt_hsum_plan* p, const float* in_dev, int64_t n
 struct bbt_lspec_plan {
     long long n = 0, stack = 0, n_elem = 0;
     float2 *tw1 = nullptr, *tw2 = nullptr, *tw_hi = nullptr, *tw_lo = nullptr;
-    float2* scratch = nullptr;
-    size_t scratch_bytes = 0;
+    PlanScratch scratch;             // 8 n bytes per column pair of a launch, between the two passes
 };
 
-// BBT_LSPEC_THREADS: threads of a workgroup of both passes (256, 512, 1024).  Read at every call, for
-// measuring; which thread moves which cell changes, no value of the output does.  Anything else leaves
-// the default.
+// BBT_LSPEC_THREADS: threads of a workgroup of both passes (256, 512, 1024): which thread moves which
+// cell changes with it.
 static int lspec_env_threads() {
-    const int t = dmt_env("BBT_LSPEC_THREADS", {256, 512, 1024});
+    const int t = env_knob("BBT_LSPEC_THREADS", {256, 512, 1024});
     return t ? t : BBT_LSPEC_THREADS;
 }
 
@@ -4082,8 +4091,9 @@ static int lspec_table(float2** dst, long long count, long long mult, long long 
 
 extern "C" int bbt_lspec_plan_destroy(bbt_lspec_plan* p) {
     if (!p) return 0;
-    for (float2* t : {p->tw1, p->tw2, p->tw_hi, p->tw_lo, p->scratch})
+    for (float2* t : {p->tw1, p->tw2, p->tw_hi, p->tw_lo})
         if (t) (void)hipFree(t);
+    p->scratch.release();
     delete p;
     return 0;
 }
@@ -4132,7 +4142,7 @@ extern "C" int bbt_lspec_plan_info(const bbt_lspec_plan* p, int64_t budget, int*
 extern "C" int bbt_lspec_execute(bbt_lspec_plan* p, const float* in_dev, int64_t n_in, float* out_dev,
                                  int64_t n_spec, int64_t budget, bbt_stream stream) {
     ARG_TRY(p && in_dev && out_dev, "bbt_lspec_execute: null argument");
-    ARG_TRY((((uintptr_t)in_dev | (uintptr_t)out_dev) & 3) == 0, "bbt_lspec_execute: arrays must be 4-byte aligned");
+    ARG_TRY(aligned4(in_dev, out_dev), "bbt_lspec_execute: arrays must be 4-byte aligned");
     ARG_TRY(n_spec >= 1, "bbt_lspec_execute: no whole transform (n_spec=%lld)", (long long)n_spec);
     ARG_TRY(n_spec <= BBT_LSPEC_MAX_VALUES / (p->n * p->stack * p->n_elem),
             "bbt_lspec_execute: more than 2^40 values in one call");
@@ -4145,13 +4155,8 @@ extern "C" int bbt_lspec_execute(bbt_lspec_plan* p, const float* in_dev, int64_t
         const char* err = lspec_geo(p->n, p->n_elem, per, i, &g);
         ARG_TRY(!err, "bbt_lspec_execute: %s (n=%lld, n_elem=%lld)", err ? err : "", p->n, p->n_elem);
     }
-    const size_t need = (size_t)(8 * p->n * per);
-    if (p->scratch_bytes < need) {
-        if (p->scratch) HIP_TRY(hipFree(p->scratch));
-        p->scratch = nullptr, p->scratch_bytes = 0;
-        HIP_TRY(hipMalloc((void**)&p->scratch, need));
-        p->scratch_bytes = need;
-    }
+    if (p->scratch.reserve((size_t)(8 * p->n * per))) return 1;
+    float2* scratch = (float2*)p->scratch.ptr;
     hipStream_t st = (hipStream_t)stream;
     const float scale = 1.f / (float)p->stack;
     const dim3 block((unsigned)lspec_env_threads());
@@ -4164,8 +4169,8 @@ extern "C" int bbt_lspec_execute(bbt_lspec_plan* p, const float* in_dev, int64_t
             for (long long i = 0; i < n_launch; ++i) {
                 lspec_geo(p->n, p->n_elem, per, i, &g);
                 hipLaunchKernelGGL(k_lspec_first, dim3((unsigned)g.n_wg1), block, 0, st, x,
-                                   p->scratch, p->tw1, p->tw_hi, p->tw_lo, g);
-                hipLaunchKernelGGL(k_lspec_last, dim3((unsigned)g.n_wg2), block, 0, st, p->scratch, o,
+                                   scratch, p->tw1, p->tw_hi, p->tw_lo, g);
+                hipLaunchKernelGGL(k_lspec_last, dim3((unsigned)g.n_wg2), block, 0, st, scratch, o,
                                    p->tw2, g, mode, scale);
             }
         }
@@ -4181,9 +4186,8 @@ struct bbt_accel_plan {
     double* factors = nullptr;       // the k_j on the device, float64
 };
 
-// BBT_ACCEL_ROUTE: 0 automatic, 1 the window wherever it fits, 2 direct.  Read at every call, for
-// measuring and for the tests that walk the routes; no value of the output depends on it.
-static int accel_env_route() { return dmt_env("BBT_ACCEL_ROUTE", {1, 2}); }
+// BBT_ACCEL_ROUTE: 0 automatic, 1 the window wherever it fits, 2 direct.
+static int accel_env_route() { return env_knob("BBT_ACCEL_ROUTE", {1, 2}); }
 
 extern "C" int bbt_accel_plan_destroy(bbt_accel_plan* p) {
     if (!p) return 0;
@@ -4246,7 +4250,7 @@ extern "C" int bbt_accel_plan_info(const bbt_accel_plan* p, int64_t out_first, i
 extern "C" int bbt_accel_execute(bbt_accel_plan* p, const float* in_dev, int64_t in_first, int64_t n_in,
                                  float* out_dev, int64_t out_first, int64_t n_out, bbt_stream stream) {
     ARG_TRY(p && in_dev && out_dev, "bbt_accel_execute: null argument");
-    ARG_TRY((((uintptr_t)in_dev | (uintptr_t)out_dev) & 3) == 0, "bbt_accel_execute: arrays must be 4-byte aligned");
+    ARG_TRY(aligned4(in_dev, out_dev), "bbt_accel_execute: arrays must be 4-byte aligned");
     const bool wide = p->n_elem % 4 == 0 && (((uintptr_t)in_dev | (uintptr_t)out_dev) & 15) == 0;
     AccelGeo g = {};
     const char* err = accel_geo(p->n, p->n_elem, p->n_acc, wide ? 16 : 4, p->k_min, p->k_max, in_first, n_in,
@@ -4275,16 +4279,16 @@ extern "C" int bbt_accel_execute(bbt_accel_plan* p, const float* in_dev, int64_t
 // block median / MAD by selection (rank_kernels.hpp; the tiling is rank_geo.hpp's)
 
 // BBT_RANK_ROUTE: lds (wherever the block fits), global, or auto; BBT_RANK_DIGIT: bits of a radix digit
-// (4, 8); BBT_RANK_WIDTH: elements of a workgroup (16, 32, 64).  Read at every call, for measuring and for
-// the tests that walk the routes; no value of the output depends on any.  Anything else leaves the default.
+// (4, 8); BBT_RANK_WIDTH: elements of a workgroup (16, 32, 64).  The route is a word, so it is read here,
+// under the same contract as `env_knob`.
 static int rank_env_route() {
     const char* e = getenv("BBT_RANK_ROUTE");
     if (e && !strcmp(e, "lds")) return BBT_RANK_ROUTE_LDS;
     if (e && !strcmp(e, "global")) return BBT_RANK_ROUTE_GLOBAL;
     return BBT_RANK_ROUTE_AUTO;
 }
-static int rank_env_digit() { return dmt_env("BBT_RANK_DIGIT", {4, 8}); }
-static int rank_env_width() { return dmt_env("BBT_RANK_WIDTH", {16, 32, 64}); }
+static int rank_env_digit() { return env_knob("BBT_RANK_DIGIT", {4, 8}); }
+static int rank_env_width() { return env_knob("BBT_RANK_WIDTH", {16, 32, 64}); }
 
 static int rank_launch(const RankGeo& g, const float* x, float* out, float* med, float* mad, hipStream_t st) {
     const dim3 grid((unsigned)g.n_wg), block(BBT_RANK_THREADS);
@@ -4309,8 +4313,7 @@ static int rank_launch(const RankGeo& g, const float* x, float* out, float* med,
 extern "C" int bbt_rank_stats(const float* x_dev, float* med_dev, float* mad_dev, int64_t n_spec, int64_t nbin,
                               int64_t n_elem, int64_t m, int64_t skip, bbt_stream stream) {
     ARG_TRY(x_dev && med_dev, "bbt_rank_stats: null argument");
-    ARG_TRY((((uintptr_t)x_dev | (uintptr_t)med_dev | (uintptr_t)mad_dev) & 3) == 0,
-            "bbt_rank_stats: arrays must be 4-byte aligned");
+    ARG_TRY(aligned4(x_dev, med_dev, mad_dev), "bbt_rank_stats: arrays must be 4-byte aligned");
     RankGeo g = {};
     const char* err = rank_geo(n_spec, nbin, n_elem, m, skip, rank_env_width(), rank_env_digit(), rank_env_route(), &g);
     ARG_TRY(!err, "bbt_rank_stats: %s (n_spec=%lld, nbin=%lld, n_elem=%lld, m=%lld, skip=%lld)", err ? err : "",
@@ -4323,7 +4326,7 @@ extern "C" int bbt_rank_stats(const float* x_dev, float* med_dev, float* mad_dev
 extern "C" int bbt_rank_standardize(const float* x_dev, float* out_dev, int64_t n_block, int64_t n, int64_t n_elem,
                                     bbt_stream stream) {
     ARG_TRY(x_dev && out_dev, "bbt_rank_standardize: null argument");
-    ARG_TRY((((uintptr_t)x_dev | (uintptr_t)out_dev) & 3) == 0, "bbt_rank_standardize: arrays must be 4-byte aligned");
+    ARG_TRY(aligned4(x_dev, out_dev), "bbt_rank_standardize: arrays must be 4-byte aligned");
     RankGeo g = {};
     const char* err = rank_std_geo(n_block, n, n_elem, rank_env_width(), rank_env_digit(), rank_env_route(), &g);
     ARG_TRY(!err, "bbt_rank_standardize: %s (n_block=%lld, n=%lld, n_elem=%lld)", err ? err : "", (long long)n_block,
@@ -4336,7 +4339,7 @@ extern "C" int bbt_rank_standardize(const float* x_dev, float* out_dev, int64_t 
 extern "C" int bbt_rank_whiten(const float* x_dev, float* out_dev, int64_t n_spec, int64_t nbin, int64_t n_elem,
                                int64_t m, int64_t skip, double ratio, bbt_stream stream) {
     ARG_TRY(x_dev && out_dev, "bbt_rank_whiten: null argument");
-    ARG_TRY((((uintptr_t)x_dev | (uintptr_t)out_dev) & 3) == 0, "bbt_rank_whiten: arrays must be 4-byte aligned");
+    ARG_TRY(aligned4(x_dev, out_dev), "bbt_rank_whiten: arrays must be 4-byte aligned");
     ARG_TRY(ratio > 0. && ratio < __builtin_inf(), "bbt_rank_whiten: ratio must be finite and > 0");
     RankGeo g = {};
     const char* err = rank_geo(n_spec, nbin, n_elem, m, skip, rank_env_width(), rank_env_digit(), rank_env_route(), &g);

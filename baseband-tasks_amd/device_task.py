@@ -15,7 +15,7 @@ from . import hip
 from . import host_pipeline
 from .hip import DeviceArray
 
-__all__ = ['DeviceTaskMixin', 'fetch_device', 'cache_producer', 'views_to_keep']
+__all__ = ['DeviceTaskMixin', 'ChunkedDeviceTask', 'fetch_device', 'cache_producer', 'views_to_keep']
 
 
 def fetch_device(ih, start, count):
@@ -408,3 +408,55 @@ class DeviceTaskMixin:
 
     def synchronize(self):
         hip.synchronize()
+
+
+class ChunkedDeviceTask(DeviceTaskMixin):
+    """A device task that makes its output chunk by chunk: one `fetch_device` of ``self.ih`` and one
+    launch (or a few) per chunk of output samples.  The subclass provides
+
+    ``_chunk_size()``: the output samples at most per fetch and launch, 1 at least;
+    ``_chunk_input(c0, c1)``: ``(start, count)``, the input samples that output samples ``[c0, c1)``
+    need (default: the same ones);
+    ``_make_plan()``: whatever the launches share, made on the first run of frames and kept in
+    ``self._plan``; ``close`` closes it (default: None);
+    ``_launch(x, start, count, out, c0, c1)``: compute output samples ``[c0, c1)`` into ``out`` from
+    ``x``, the input samples ``[start, start + count)``.
+
+    `_input_span` and the loop of `_compute_frames` are both made from the first two, so what the
+    host prefetch is told and what a run fetches cannot differ."""
+    _plan = None
+    _plan_made = False
+
+    def _chunk_size(self):
+        raise NotImplementedError
+
+    def _chunk_input(self, c0, c1):
+        return c0, c1 - c0
+
+    def _make_plan(self):
+        return None
+
+    def _launch(self, x, start, count, out, c0, c1):
+        raise NotImplementedError
+
+    def _input_span(self, first, last):
+        a, b = self._frame_span(first, last)
+        return (self.ih,) + self._chunk_input(a, b) if b - a <= self._chunk_size() else None    # (one fetch only)
+
+    def _compute_frames(self, first, last, out):
+        if not self._plan_made:
+            self._plan, self._plan_made = self._make_plan(), True
+        a, b = self._frame_span(first, last)
+        per = self._chunk_size()
+        for c0 in range(a, b, per):
+            c1 = min(b, c0 + per)
+            start, count = self._chunk_input(c0, c1)
+            x = fetch_device(self.ih, start, count)
+            self._launch(x, start, count, out[c0 - a:c1 - a], c0, c1)
+
+    def close(self):
+        super().close()
+        self._drop_cache()
+        plan, self._plan, self._plan_made = self._plan, None, False
+        if plan is not None:
+            plan.close()

@@ -16,8 +16,8 @@ import numpy as np
 
 from . import hip
 from .base import BaseTaskBase, _stream_rate
-from .device_task import DeviceTaskMixin, fetch_device
-from .search import _check_plane, _check_plane_stream, _local_maxima, _lone_frequency, _prod
+from .device_task import ChunkedDeviceTask
+from .search import _check_plane, _check_plane_stream, _init_with_band_of, _local_maxima, _prod
 
 __all__ = ['FFASearch', 'ffa_search_samples', 'ffa_transform_samples', 'ffa_shift', 'ffa_scales', 'ffa_period',
            'ffa_rows', 'ffa_candidates', 'ffa_plan', 'SNR', 'SHIFT', 'WIDTH', 'PHASE']
@@ -257,7 +257,7 @@ def ffa_plan(period_min, period_max, sample_rate, bins_min=256):
         start = float(p_hi * factor)
 
 
-class FFASearch(DeviceTaskMixin, BaseTaskBase):
+class FFASearch(ChunkedDeviceTask, BaseTaskBase):
     """The best fold of every block of ``n`` samples at every base period, per element of a sample: a pulsar of
     unknown period and duty cycle is folded coherently at every trial period and its profile matched-filtered
     with circular boxcars of widths 1, 2, 4, ... bins.
@@ -307,13 +307,9 @@ class FFASearch(DeviceTaskMixin, BaseTaskBase):
             raise ValueError(f"the stream has {ih.shape[0]} samples: less than one block of {self.n}.")
         self._n_elem = _prod(ih.shape[1:])
         self._max_mp = max(ffa_rows(self.n, p)[1] * p for p in range(p_lo, p_hi))
-        self._plan = None
-        lone = _lone_frequency(ih)
-        super().__init__(ih, shape=(ih.shape[0] // self.n, p_hi - p_lo, 4) + tuple(ih.shape[1:]),
-                         sample_rate=_stream_rate(ih) / self.n, samples_per_frame=samples_per_frame, dtype=np.float32,
-                         **(dict(sideband=1) if lone else {}))
-        if lone:
-            del self.meta['__attributes__']['sideband']
+        _init_with_band_of(self, ih, shape=(ih.shape[0] // self.n, p_hi - p_lo, 4) + tuple(ih.shape[1:]),
+                           sample_rate=_stream_rate(ih) / self.n, samples_per_frame=samples_per_frame,
+                           dtype=np.float32)
 
     def _chunks(self):
         """The launches of one block: a list of ``(e0, ne, pa, pb)``."""
@@ -330,24 +326,15 @@ class FFASearch(DeviceTaskMixin, BaseTaskBase):
             launches += [(e0, cols, pa, min(p_hi, pa + per)) for pa in range(p_lo, p_hi, per)]
         return launches
 
-    def _input_span(self, first, last):
-        a, b = self._frame_span(first, last)
-        return (self.ih, a * self.n, self.n) if b - a == 1 else None      # (one fetch only)
+    def _chunk_size(self):
+        return 1                                # (one block per fetch; `_chunks` cuts it into launches)
 
-    def _compute_frames(self, first, last, out):
-        if self._plan is None:
-            self._plan = hip.FfaPlan(self.n, self.periods, self.n_widths, self._n_elem)
-        a, b = self._frame_span(first, last)
-        launches = self._chunks()
-        for block in range(a, b):
-            x = fetch_device(self.ih, block * self.n, self.n)
-            cell = out[block - a:block - a + 1]
-            for e0, ne, pa, pb in launches:
-                self._plan.execute(x, cell, e0, ne, pa, pb)
+    def _chunk_input(self, c0, c1):
+        return c0 * self.n, (c1 - c0) * self.n
 
-    def close(self):
-        super().close()
-        self._drop_cache()
-        if self._plan is not None:
-            self._plan.close()
-            self._plan = None
+    def _make_plan(self):
+        return hip.FfaPlan(self.n, self.periods, self.n_widths, self._n_elem)
+
+    def _launch(self, x, start, count, out, c0, c1):
+        for e0, ne, pa, pb in self._chunks():
+            self._plan.execute(x, out, e0, ne, pa, pb)

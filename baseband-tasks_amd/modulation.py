@@ -8,7 +8,7 @@ import numpy as np
 
 from . import hip
 from .base import BaseTaskBase, _stream_rate, check_broadcast_to
-from .device_task import DeviceTaskMixin, fetch_device
+from .device_task import ChunkedDeviceTask
 from .fold_table import PIECE, bin_runs, plan_pieces, polynomial_bins, sample_times, unwrapped_bin
 
 __all__ = ['Modulate', 'modulate_samples']
@@ -45,7 +45,7 @@ def _time_ordered(starts, ks, n_phase, c0):
     return (np.concatenate(starts) - c0).astype(np.int64), (np.concatenate(ks) % n_phase).astype(np.int64)
 
 
-class Modulate(DeviceTaskMixin, BaseTaskBase):
+class Modulate(ChunkedDeviceTask, BaseTaskBase):
     """Multiply a stream by a pulse profile: every sample by the gain of its phase bin.
 
     Parameters
@@ -212,31 +212,20 @@ class Modulate(DeviceTaskMixin, BaseTaskBase):
         return out
 
     # -- frames ---------------------------------------------------------------------
-    def _input_span(self, first, last):
-        a, b = self._frame_span(first, last)
-        return (self.ih, a, b - a) if b - a <= self._chunk_samples() else None      # (one fetch only)
-
-    def _chunk_samples(self):
+    def _chunk_size(self):
         sample_bytes = self._n_elem * np.dtype(self.dtype).itemsize
         return max(1, int(self.modulate_budget) // max(sample_bytes, 1))
 
-    def _compute_frames(self, first, last, out):
-        a, b = self._frame_span(first, last)
+    def _launch(self, x, start, count, out, c0, c1):
         if self._gain is None:
             self._gain = hip.DeviceArray.from_host(self._gain_host)
-        per = self._chunk_samples()
-        on_device = hasattr(self.phase, 'fold_pieces') and self._route() == 'device'
-        for c0 in range(a, b, per):
-            c1 = min(b, c0 + per)
-            x = fetch_device(self.ih, c0, c1 - c0)
-            piece = out[c0 - a:c1 - a]
-            if on_device:
-                edges = self._frame_edges(c0, c1)
-                plan = plan_pieces(edges, self._row_pieces(edges), self.n_phase, c0, c1)[2]
-                hip.modulate_pieces(x, piece, self._n_elem, self._gain, plan)
-            else:
-                run_begin, run_bin = self._runs(c0, c1)
-                hip.modulate_runs(x, piece, self._n_elem, self._gain, run_begin, run_bin)
+        if hasattr(self.phase, 'fold_pieces') and self._route() == 'device':
+            edges = self._frame_edges(c0, c1)
+            plan = plan_pieces(edges, self._row_pieces(edges), self.n_phase, c0, c1)[2]
+            hip.modulate_pieces(x, out, self._n_elem, self._gain, plan)
+        else:
+            run_begin, run_bin = self._runs(c0, c1)
+            hip.modulate_runs(x, out, self._n_elem, self._gain, run_begin, run_bin)
 
     def _repr_item(self, key, default, value=None):
         if key == 'phase':
@@ -245,5 +234,4 @@ class Modulate(DeviceTaskMixin, BaseTaskBase):
 
     def close(self):
         super().close()
-        self._drop_cache()
         self._gain = None

@@ -28,10 +28,11 @@ from . import hip
 from .base import META_ATTRIBUTES, BaseTaskBase, SetAttribute, _stream_rate, check_broadcast_to, simplify_shape
 from .channelize import Channelize
 from .fourier import check_transform_length
-from .device_task import DeviceTaskMixin, fetch_device
+from .device_task import ChunkedDeviceTask
 from .functions import Square
 from .integration import Integrate
-from .search import _block_median, _check_plane, _check_plane_stream, _local_maxima, _local_maxima_3d, _lone_frequency, _prod
+from .search import (_block_median, _check_plane, _check_plane_stream, _init_with_band_of, _local_maxima,
+                     _local_maxima_3d, _lone_frequency, _prod)
 
 __all__ = ['fluctuation_spectra', 'LongSpectra', 'long_spectra_samples', 'Whiten', 'whiten_samples', 'MedianWhiten',
            'median_whiten_samples', 'median_ratio', 'LN2', 'HarmonicSearch', 'harmonic_search_samples',
@@ -543,7 +544,29 @@ def _check_spectra_stream(ih, who):
         raise ValueError(f"{who} needs a bin axis: samples of shape (nbin, ...).")
 
 
-class Whiten(DeviceTaskMixin, BaseTaskBase):
+class _BlockWhiten(ChunkedDeviceTask, BaseTaskBase):
+    """What `Whiten` and `MedianWhiten` share: blocks of ``m`` bins from bin ``skip`` on, chunks of whole
+    spectra.  A subclass launches its kernel."""
+
+    #: input bytes fetched at most per `fetch_device` call and launch (assignable); a chunk is a
+    #: whole number of spectra, one at least
+    whiten_budget = 1 << 29
+
+    def __init__(self, ih, m, skip=1, *, samples_per_frame=None):
+        _check_spectra_stream(ih, type(self).__name__)
+        self.m = _check_m(m)
+        self._nbin = ih.shape[1]
+        self.skip = _check_skip(skip, self._nbin)
+        self._n_elem = _prod(ih.shape[2:])
+        if samples_per_frame is None:
+            samples_per_frame = max(min(operator.index(ih.samples_per_frame), ih.shape[0]), 1)
+        _init_with_band_of(self, ih, samples_per_frame=operator.index(samples_per_frame), dtype=np.float32)
+
+    def _chunk_size(self):
+        return max(1, int(self.whiten_budget) // (self._nbin * self._n_elem * 4))
+
+
+class Whiten(_BlockWhiten):
     """Divide every block of ``m`` frequency bins of every spectrum by its own mean, per element.
 
     Parameters
@@ -565,41 +588,11 @@ class Whiten(DeviceTaskMixin, BaseTaskBase):
     and red noise steeper than a block is not flattened inside it.  `MedianWhiten` is the median-based
     counterpart."""
 
-    #: input bytes fetched at most per `fetch_device` call and launch (assignable); a chunk is a
-    #: whole number of spectra, one at least
-    whiten_budget = 1 << 29
-
-    def __init__(self, ih, m, skip=1, *, samples_per_frame=None):
-        _check_spectra_stream(ih, 'Whiten')
-        self.m = _check_m(m)
-        self._nbin = ih.shape[1]
-        self.skip = _check_skip(skip, self._nbin)
-        self._n_elem = _prod(ih.shape[2:])
-        if samples_per_frame is None:
-            samples_per_frame = max(min(operator.index(ih.samples_per_frame), ih.shape[0]), 1)
-        lone = _lone_frequency(ih)
-        super().__init__(ih, samples_per_frame=operator.index(samples_per_frame), dtype=np.float32,
-                         **(dict(sideband=1) if lone else {}))
-        if lone:
-            del self.meta['__attributes__']['sideband']
-
-    def _chunk_spectra(self):
-        return max(1, int(self.whiten_budget) // (self._nbin * self._n_elem * 4))
-
-    def _input_span(self, first, last):
-        a, b = self._frame_span(first, last)
-        return (self.ih, a, b - a) if b - a <= self._chunk_spectra() else None      # (one fetch only)
-
-    def _compute_frames(self, first, last, out):
-        a, b = self._frame_span(first, last)
-        per = self._chunk_spectra()
-        for c0 in range(a, b, per):
-            c1 = min(b, c0 + per)
-            x = fetch_device(self.ih, c0, c1 - c0)
-            hip.hsum_whiten(x, self._nbin, self._n_elem, self.m, self.skip, out=out[c0 - a:c1 - a])
+    def _launch(self, x, start, count, out, c0, c1):
+        hip.hsum_whiten(x, self._nbin, self._n_elem, self.m, self.skip, out=out)
 
 
-class MedianWhiten(DeviceTaskMixin, BaseTaskBase):
+class MedianWhiten(_BlockWhiten):
     """Divide every block of ``m`` frequency bins of every spectrum by the noise mean its own median
     implies, per element: `Whiten` with an estimate the pulsar's harmonics and birdies cannot raise.
 
@@ -627,43 +620,16 @@ class MedianWhiten(DeviceTaskMixin, BaseTaskBase):
     whose median is not ``> 0`` or denormal, comes out as +0.  There is no running median and no fit: red
     noise steeper than a block is not flattened inside it."""
 
-    #: input bytes fetched at most per `fetch_device` call and launch (assignable); a chunk is a
-    #: whole number of spectra, one at least
-    whiten_budget = 1 << 29
-
     def __init__(self, ih, m, skip=1, *, averaged=1, ratio=None, samples_per_frame=None):
-        _check_spectra_stream(ih, 'MedianWhiten')
-        self.m = _check_m(m)
-        self._nbin = ih.shape[1]
-        self.skip = _check_skip(skip, self._nbin)
+        super().__init__(ih, m, skip, samples_per_frame=samples_per_frame)
         if ratio is not None and averaged != 1:
             raise ValueError("give averaged or ratio, not both: ratio is what averaged stands for.")
         self.ratio = median_ratio(averaged) if ratio is None else _check_ratio(ratio)
         self._ratio_given = ratio is not None
         self.averaged = averaged
-        self._n_elem = _prod(ih.shape[2:])
-        if samples_per_frame is None:
-            samples_per_frame = max(min(operator.index(ih.samples_per_frame), ih.shape[0]), 1)
-        lone = _lone_frequency(ih)
-        super().__init__(ih, samples_per_frame=operator.index(samples_per_frame), dtype=np.float32,
-                         **(dict(sideband=1) if lone else {}))
-        if lone:
-            del self.meta['__attributes__']['sideband']
 
-    def _chunk_spectra(self):
-        return max(1, int(self.whiten_budget) // (self._nbin * self._n_elem * 4))
-
-    def _input_span(self, first, last):
-        a, b = self._frame_span(first, last)
-        return (self.ih, a, b - a) if b - a <= self._chunk_spectra() else None      # (one fetch only)
-
-    def _compute_frames(self, first, last, out):
-        a, b = self._frame_span(first, last)
-        per = self._chunk_spectra()
-        for c0 in range(a, b, per):
-            c1 = min(b, c0 + per)
-            x = fetch_device(self.ih, c0, c1 - c0)
-            hip.rank_whiten(x, self._nbin, self._n_elem, self.m, self.skip, self.ratio, out=out[c0 - a:c1 - a])
+    def _launch(self, x, start, count, out, c0, c1):
+        hip.rank_whiten(x, self._nbin, self._n_elem, self.m, self.skip, self.ratio, out=out)
 
     def _repr_item(self, key, default, value=None):
         if key == 'ratio' and not self._ratio_given:
@@ -671,7 +637,7 @@ class MedianWhiten(DeviceTaskMixin, BaseTaskBase):
         return super()._repr_item(key, default, value)
 
 
-class HarmonicSearch(DeviceTaskMixin, BaseTaskBase):
+class HarmonicSearch(ChunkedDeviceTask, BaseTaskBase):
     """The best harmonic-sum S/N in every block of ``n`` frequency bins, per spectrum and element: a
     pulsar's narrow pulse spreads its power over many harmonics, so sums of 1, 2, 4, ... harmonics are
     formed and the best one kept.
@@ -740,10 +706,8 @@ class HarmonicSearch(DeviceTaskMixin, BaseTaskBase):
                     kept[attr] = simplify_shape(np.asanyarray(full[0]))
         if 'frequency' not in kept:
             kept.pop('sideband', None)
-        self._plan = None
-        super().__init__(ih, shape=(ih.shape[0], self._nb, 3) + rest,
-                         samples_per_frame=operator.index(samples_per_frame), dtype=np.float32,
-                         **(dict(sideband=1) if _lone_frequency(ih) else {}))
+        _init_with_band_of(self, ih, shape=(ih.shape[0], self._nb, 3) + rest,
+                           samples_per_frame=operator.index(samples_per_frame), dtype=np.float32)
         if kept:
             self.meta['__attributes__'] = kept
         else:
@@ -753,33 +717,18 @@ class HarmonicSearch(DeviceTaskMixin, BaseTaskBase):
         # (the inherited metadata describe the bins; they are replaced once the stream is set up)
         return simplify_shape(np.asanyarray(value))
 
-    def _chunk_spectra(self):
+    def _chunk_size(self):
         row = self._n_elem * 4
         return max(1, int(self.hsum_budget) // ((self._nbin + 3 * self._nb) * row))
 
-    def _input_span(self, first, last):
-        a, b = self._frame_span(first, last)
-        return (self.ih, a, b - a) if b - a <= self._chunk_spectra() else None      # (one fetch only)
+    def _make_plan(self):
+        return hip.HsumPlan(self._nbin, self.n, self.n_levels, self.lo, self._n_elem, self.scales)
 
-    def _compute_frames(self, first, last, out):
-        if self._plan is None:
-            self._plan = hip.HsumPlan(self._nbin, self.n, self.n_levels, self.lo, self._n_elem, self.scales)
-        a, b = self._frame_span(first, last)
-        per = self._chunk_spectra()
-        for c0 in range(a, b, per):
-            c1 = min(b, c0 + per)
-            x = fetch_device(self.ih, c0, c1 - c0)
-            self._plan.execute(x, c1 - c0, out[c0 - a:c1 - a])
-
-    def close(self):
-        super().close()
-        self._drop_cache()
-        if self._plan is not None:
-            self._plan.close()
-            self._plan = None
+    def _launch(self, x, start, count, out, c0, c1):
+        self._plan.execute(x, count, out)
 
 
-class LongSpectra(DeviceTaskMixin, BaseTaskBase):
+class LongSpectra(ChunkedDeviceTask, BaseTaskBase):
     """Power spectra of ``n`` = 2^15 ... 2^22 samples of every column of a float32 stream: the whole
     pointing in one coherent transform, where `Channelize` stops at 16384 points.
 
@@ -832,39 +781,27 @@ class LongSpectra(DeviceTaskMixin, BaseTaskBase):
         self._n_elem = _prod(rest)
         if self._n_elem < 1:
             raise ValueError("LongSpectra needs at least one element per sample.")
-        self._plan = None
-        lone = _lone_frequency(ih)
         rate = _stream_rate(ih)
-        super().__init__(ih, shape=(ih.shape[0] // (self.n * self.stack), self.n // 2 + 1) + rest,
-                         sample_rate=rate / (self.n * self.stack), samples_per_frame=operator.index(samples_per_frame),
-                         dtype=np.float32, **(dict(sideband=1) if lone else {}))
-        if lone:
-            del self.meta['__attributes__']['sideband']
+        _init_with_band_of(self, ih, shape=(ih.shape[0] // (self.n * self.stack), self.n // 2 + 1) + rest,
+                           sample_rate=rate / (self.n * self.stack),
+                           samples_per_frame=operator.index(samples_per_frame), dtype=np.float32)
         self.bin_width = rate / self.n
 
-    def _input_span(self, first, last):
-        a, b = self._frame_span(first, last)
+    def _chunk_size(self):
+        return 1                                # (the samples behind one output spectrum are fetched in one piece)
+
+    def _chunk_input(self, c0, c1):
         per = self.n * self.stack
-        return (self.ih, a * per, per) if b - a == 1 else None                     # (one fetch only)
+        return c0 * per, (c1 - c0) * per
 
-    def _compute_frames(self, first, last, out):
-        if self._plan is None:
-            self._plan = hip.LongSpectraPlan(self.n, self.stack, self._n_elem)
-        a, b = self._frame_span(first, last)
-        per = self.n * self.stack
-        for m in range(a, b):
-            x = fetch_device(self.ih, m * per, per)
-            self._plan.execute(x, 1, out[m - a:m - a + 1], max(int(self.spectra_budget), 1))
+    def _make_plan(self):
+        return hip.LongSpectraPlan(self.n, self.stack, self._n_elem)
 
-    def close(self):
-        super().close()
-        self._drop_cache()
-        if self._plan is not None:
-            self._plan.close()
-            self._plan = None
+    def _launch(self, x, start, count, out, c0, c1):
+        self._plan.execute(x, c1 - c0, out, max(int(self.spectra_budget), 1))
 
 
-class Accelerate(DeviceTaskMixin, BaseTaskBase):
+class Accelerate(ChunkedDeviceTask, BaseTaskBase):
     """Acceleration trials: resample every block of ``n`` samples of a dedispersed time series along a
     parabola, once per trial acceleration, so that a pulsar whose apparent spin frequency drifts at that
     rate -- one in a binary -- becomes strictly periodic and `LongSpectra`, `Whiten` and `HarmonicSearch`
@@ -934,39 +871,19 @@ class Accelerate(DeviceTaskMixin, BaseTaskBase):
         length = ih.shape[0] // n * n
         if samples_per_frame is None:
             samples_per_frame = max(min(operator.index(ih.samples_per_frame), length), 1)
-        self._plan = None
-        lone = _lone_frequency(ih)
-        super().__init__(ih, shape=(length, len(self.factors)) + rest, samples_per_frame=operator.index(samples_per_frame),
-                         dtype=np.float32, **(dict(sideband=1) if lone else {}))
-        if lone:
-            del self.meta['__attributes__']['sideband']
+        _init_with_band_of(self, ih, shape=(length, len(self.factors)) + rest,
+                           samples_per_frame=operator.index(samples_per_frame), dtype=np.float32)
 
-    def _chunk_rows(self):
+    def _chunk_size(self):
         return max(1, int(self.accel_budget) // (4 * len(self.factors) * self._n_elem))
 
-    def _window(self, c0, c1):
+    def _chunk_input(self, c0, c1):
         """The input samples output rows [c0, c1) need: (first, count)."""
         lo, hi = _accel_window(self.n, self._k_min, self._k_max, c0, c1 - 1)
         return lo, hi + 1 - lo
 
-    def _input_span(self, first, last):
-        a, b = self._frame_span(first, last)
-        return (self.ih,) + self._window(a, b) if b - a <= self._chunk_rows() else None      # (one fetch only)
+    def _make_plan(self):
+        return hip.AccelPlan(self.n, self._n_elem, self.factors)
 
-    def _compute_frames(self, first, last, out):
-        if self._plan is None:
-            self._plan = hip.AccelPlan(self.n, self._n_elem, self.factors)
-        a, b = self._frame_span(first, last)
-        per = self._chunk_rows()
-        for c0 in range(a, b, per):
-            c1 = min(b, c0 + per)
-            start, n_in = self._window(c0, c1)
-            x = fetch_device(self.ih, start, n_in)
-            self._plan.execute(x, start, n_in, out[c0 - a:c1 - a], c0, c1 - c0, n_rows=self.shape[0])
-
-    def close(self):
-        super().close()
-        self._drop_cache()
-        if self._plan is not None:
-            self._plan.close()
-            self._plan = None
+    def _launch(self, x, start, count, out, c0, c1):
+        self._plan.execute(x, start, count, out, c0, c1 - c0, n_rows=self.shape[0])

@@ -11,7 +11,7 @@ import numpy as np
 
 from . import hip
 from .base import BaseTaskBase, _stream_rate
-from .device_task import DeviceTaskMixin, fetch_device
+from .device_task import ChunkedDeviceTask
 
 __all__ = ['SpectralKurtosis', 'Excise', 'sk_limits', 'spectral_kurtosis', 'excise_flags', 'excise_samples']
 
@@ -167,7 +167,7 @@ def _check_stream(ih, n, who):
     return n
 
 
-class SpectralKurtosis(DeviceTaskMixin, BaseTaskBase):
+class SpectralKurtosis(ChunkedDeviceTask, BaseTaskBase):
     """The spectral kurtosis estimator of every block of ``n`` samples, per element of a sample.
 
     Parameters
@@ -198,24 +198,18 @@ class SpectralKurtosis(DeviceTaskMixin, BaseTaskBase):
                          sample_rate=_stream_rate(ih) / self.n, samples_per_frame=samples_per_frame,
                          dtype=np.float32)
 
-    def _chunk_blocks(self):
+    def _chunk_size(self):
         block_bytes = self.n * self._n_elem * np.dtype(self.ih.dtype).itemsize
         return max(1, int(self.sk_budget) // block_bytes)
 
-    def _input_span(self, first, last):
-        a, b = self._frame_span(first, last)
-        return (self.ih, a * self.n, (b - a) * self.n) if b - a <= self._chunk_blocks() else None
+    def _chunk_input(self, c0, c1):
+        return c0 * self.n, (c1 - c0) * self.n
 
-    def _compute_frames(self, first, last, out):
-        a, b = self._frame_span(first, last)
-        per = self._chunk_blocks()
-        for c0 in range(a, b, per):
-            c1 = min(b, c0 + per)
-            x = fetch_device(self.ih, c0 * self.n, (c1 - c0) * self.n)
-            hip.sk_estimate(x, self.n, self._n_elem, self.averaged, out=out[c0 - a:c1 - a])
+    def _launch(self, x, start, count, out, c0, c1):
+        hip.sk_estimate(x, self.n, self._n_elem, self.averaged, out=out)
 
 
-class Excise(DeviceTaskMixin, BaseTaskBase):
+class Excise(ChunkedDeviceTask, BaseTaskBase):
     """Zero every block of ``n`` samples of an element whose spectral kurtosis is not that of noise.
 
     Parameters
@@ -267,21 +261,12 @@ class Excise(DeviceTaskMixin, BaseTaskBase):
         super().__init__(ih, shape=(ih.shape[0] // n * n,) + tuple(ih.shape[1:]),
                          samples_per_frame=samples_per_frame)
 
-    def _chunk_samples(self):
+    def _chunk_size(self):
         block_bytes = self.n * self._n_elem * np.dtype(self.dtype).itemsize
         return max(1, int(self.excise_budget) // block_bytes) * self.n
 
-    def _input_span(self, first, last):
-        a, b = self._frame_span(first, last)
-        return (self.ih, a, b - a) if b - a <= self._chunk_samples() else None      # (one fetch only)
-
-    def _compute_frames(self, first, last, out):
-        a, b = self._frame_span(first, last)          # (frames and the stream are whole blocks)
-        per = self._chunk_samples()
-        for c0 in range(a, b, per):
-            c1 = min(b, c0 + per)
-            x = fetch_device(self.ih, c0, c1 - c0)
-            hip.sk_excise(x, out[c0 - a:c1 - a], self.n, self._n_elem, self.limits, self.averaged, self._group)
+    def _launch(self, x, start, count, out, c0, c1):
+        hip.sk_excise(x, out, self.n, self._n_elem, self.limits, self.averaged, self._group)
 
     def _repr_item(self, key, default, value=None):
         if key == 'limits':

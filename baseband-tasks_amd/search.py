@@ -20,7 +20,7 @@ import numpy as np
 
 from . import hip
 from .base import BaseTaskBase, _stream_rate, _stream_start, check_broadcast_to, simplify_shape
-from .device_task import DeviceTaskMixin, fetch_device
+from .device_task import ChunkedDeviceTask
 from .dispersion import dispersion_sample_delays, with_band
 from .dm import DispersionMeasure
 
@@ -115,7 +115,7 @@ def dm_trials_samples(data, shifts):
     return out
 
 
-class DMTrials(DeviceTaskMixin, BaseTaskBase):
+class DMTrials(ChunkedDeviceTask, BaseTaskBase):
     """Dedisperse a detected stream incoherently at many trial DMs and sum over frequency.
 
     Parameters
@@ -192,7 +192,6 @@ class DMTrials(DeviceTaskMixin, BaseTaskBase):
         if samples_per_frame is None:
             # (that of `ih`; never more than the stream holds, which tasks on top would refuse)
             samples_per_frame = min(max(int(ih.samples_per_frame), 1), ih.shape[0] - span)
-        self._plan = None
         super().__init__(ih, shape=(ih.shape[0] - span, len(self.dm)) + rest,
                          start_time=_stream_start(ih) + hi / _stream_rate(ih),
                          samples_per_frame=samples_per_frame, dtype=np.float32)
@@ -206,25 +205,19 @@ class DMTrials(DeviceTaskMixin, BaseTaskBase):
         # (the inherited metadata describe the channels; they are replaced once the stream is set up)
         return simplify_shape(np.asanyarray(value))
 
-    def _chunk_samples(self):
+    def _chunk_size(self):
         row_in = self.shifts.shape[1] * self._n_rest * 4
         row_out = self.shifts.shape[0] * self._n_rest * 4
         return max(1, (int(self.dmt_budget) - self._span * row_in) // (row_in + row_out))
 
-    def _input_span(self, first, last):
-        a, b = self._frame_span(first, last)
-        return (self.ih, a, b - a + self._span) if b - a <= self._chunk_samples() else None     # (one fetch only)
+    def _chunk_input(self, c0, c1):
+        return c0, c1 - c0 + self._span
 
-    def _compute_frames(self, first, last, out):
-        if self._plan is None:
-            self._plan = hip.DmtPlan(self._offsets, self._n_rest)
-        a, b = self._frame_span(first, last)
-        per = self._chunk_samples()
-        for c0 in range(a, b, per):
-            c1 = min(b, c0 + per)
-            n_in = c1 - c0 + self._span
-            x = fetch_device(self.ih, c0, n_in)
-            self._plan.execute(x, n_in, out[c0 - a:c1 - a], c1 - c0)
+    def _make_plan(self):
+        return hip.DmtPlan(self._offsets, self._n_rest)
+
+    def _launch(self, x, start, count, out, c0, c1):
+        self._plan.execute(x, count, out, c1 - c0)
 
     def _repr_item(self, key, default, value=None):
         if key == 'dms':
@@ -233,13 +226,6 @@ class DMTrials(DeviceTaskMixin, BaseTaskBase):
             given = self._band_given[key]
             return None if given is None else f"{key}={given}".replace('\n', ',')
         return super()._repr_item(key, default, value)
-
-    def close(self):
-        super().close()
-        self._drop_cache()
-        if self._plan is not None:
-            self._plan.close()
-            self._plan = None
 
 
 # -- the single-pulse search on the plane ------------------------------------------------------------------
@@ -526,7 +512,46 @@ def _lone_frequency(ih):
     return getattr(ih, 'frequency', None) is not None and getattr(ih, 'sideband', None) is None
 
 
-class Standardize(DeviceTaskMixin, BaseTaskBase):
+def _init_with_band_of(task, ih, **kwargs):
+    """``BaseTaskBase.__init__(task, ih, **kwargs)`` for a task that passes the metadata of ``ih`` on,
+    a lone frequency included (`_lone_frequency`)."""
+    lone = _lone_frequency(ih)
+    BaseTaskBase.__init__(task, ih, **kwargs, **(dict(sideband=1) if lone else {}))
+    if lone:
+        del task.meta['__attributes__']['sideband']
+
+
+class _BlockStandardize(ChunkedDeviceTask, BaseTaskBase):
+    """What `Standardize` and `RobustStandardize` share: blocks of ``n`` samples, frames and chunks of
+    whole blocks.  A subclass names its budget attribute (``_budget``) and launches its kernel."""
+    _budget = None
+
+    def __init__(self, ih, n, *, samples_per_frame=None):
+        _check_plane_stream(ih, type(self).__name__)
+        self.n = n = _check_block(n, 2)
+        if ih.shape[0] < n:
+            raise ValueError(f"the stream has {ih.shape[0]} samples: less than one block of {n}.")
+        self._n_elem = _prod(ih.shape[1:])
+        length = ih.shape[0] // n * n
+        if samples_per_frame is None:
+            samples_per_frame = min(-(-operator.index(ih.samples_per_frame) // n) * n, length)
+        samples_per_frame = operator.index(samples_per_frame)
+        if samples_per_frame < n or samples_per_frame % n:
+            raise ValueError(f"samples_per_frame must be a multiple of the block, {n}; got {samples_per_frame}.")
+        _init_with_band_of(self, ih, shape=(length,) + tuple(ih.shape[1:]), samples_per_frame=samples_per_frame,
+                           dtype=np.float32)
+
+    def _chunk_size(self):
+        block_bytes = self.n * self._n_elem * 4
+        return max(1, int(getattr(self, self._budget)) // block_bytes) * self.n
+
+    def _repr_item(self, key, default, value=None):
+        if key == 'samples_per_frame' and default is None:
+            default = min(-(-self._ih_samples_per_frame // self.n) * self.n, self.shape[0])
+        return super()._repr_item(key, default, value)
+
+
+class Standardize(_BlockStandardize):
     """Bring every block of ``n`` samples to zero mean and unit variance, per element of a sample.
 
     Parameters
@@ -551,48 +576,13 @@ class Standardize(DeviceTaskMixin, BaseTaskBase):
     #: input bytes fetched at most per `fetch_device` call and launch (assignable); a chunk is a
     #: whole number of blocks
     standardize_budget = 1 << 29
+    _budget = 'standardize_budget'
 
-    def __init__(self, ih, n, *, samples_per_frame=None):
-        _check_plane_stream(ih, 'Standardize')
-        self.n = n = _check_block(n, 2)
-        if ih.shape[0] < n:
-            raise ValueError(f"the stream has {ih.shape[0]} samples: less than one block of {n}.")
-        self._n_elem = _prod(ih.shape[1:])
-        length = ih.shape[0] // n * n
-        if samples_per_frame is None:
-            samples_per_frame = min(-(-operator.index(ih.samples_per_frame) // n) * n, length)
-        samples_per_frame = operator.index(samples_per_frame)
-        if samples_per_frame < n or samples_per_frame % n:
-            raise ValueError(f"samples_per_frame must be a multiple of the block, {n}; got {samples_per_frame}.")
-        lone = _lone_frequency(ih)
-        super().__init__(ih, shape=(length,) + tuple(ih.shape[1:]), samples_per_frame=samples_per_frame,
-                         dtype=np.float32, **(dict(sideband=1) if lone else {}))
-        if lone:
-            del self.meta['__attributes__']['sideband']
-
-    def _chunk_samples(self):
-        block_bytes = self.n * self._n_elem * 4
-        return max(1, int(self.standardize_budget) // block_bytes) * self.n
-
-    def _input_span(self, first, last):
-        a, b = self._frame_span(first, last)
-        return (self.ih, a, b - a) if b - a <= self._chunk_samples() else None      # (one fetch only)
-
-    def _compute_frames(self, first, last, out):
-        a, b = self._frame_span(first, last)          # (frames and the stream are whole blocks)
-        per = self._chunk_samples()
-        for c0 in range(a, b, per):
-            c1 = min(b, c0 + per)
-            x = fetch_device(self.ih, c0, c1 - c0)
-            hip.sps_standardize(x, self.n, self._n_elem, out=out[c0 - a:c1 - a])
-
-    def _repr_item(self, key, default, value=None):
-        if key == 'samples_per_frame' and default is None:
-            default = min(-(-self._ih_samples_per_frame // self.n) * self.n, self.shape[0])
-        return super()._repr_item(key, default, value)
+    def _launch(self, x, start, count, out, c0, c1):
+        hip.sps_standardize(x, self.n, self._n_elem, out=out)
 
 
-class RobustStandardize(DeviceTaskMixin, BaseTaskBase):
+class RobustStandardize(_BlockStandardize):
     """Bring every block of ``n`` samples to zero median and unit robust scale (1.4826 MAD), per element
     of a sample: `Standardize` with statistics a bright pulse or residual RFI in the block cannot move.
 
@@ -619,48 +609,13 @@ class RobustStandardize(DeviceTaskMixin, BaseTaskBase):
     #: input bytes fetched at most per `fetch_device` call and launch (assignable); a chunk is a
     #: whole number of blocks
     robust_budget = 1 << 29
+    _budget = 'robust_budget'
 
-    def __init__(self, ih, n, *, samples_per_frame=None):
-        _check_plane_stream(ih, 'RobustStandardize')
-        self.n = n = _check_block(n, 2)
-        if ih.shape[0] < n:
-            raise ValueError(f"the stream has {ih.shape[0]} samples: less than one block of {n}.")
-        self._n_elem = _prod(ih.shape[1:])
-        length = ih.shape[0] // n * n
-        if samples_per_frame is None:
-            samples_per_frame = min(-(-operator.index(ih.samples_per_frame) // n) * n, length)
-        samples_per_frame = operator.index(samples_per_frame)
-        if samples_per_frame < n or samples_per_frame % n:
-            raise ValueError(f"samples_per_frame must be a multiple of the block, {n}; got {samples_per_frame}.")
-        lone = _lone_frequency(ih)
-        super().__init__(ih, shape=(length,) + tuple(ih.shape[1:]), samples_per_frame=samples_per_frame,
-                         dtype=np.float32, **(dict(sideband=1) if lone else {}))
-        if lone:
-            del self.meta['__attributes__']['sideband']
-
-    def _chunk_samples(self):
-        block_bytes = self.n * self._n_elem * 4
-        return max(1, int(self.robust_budget) // block_bytes) * self.n
-
-    def _input_span(self, first, last):
-        a, b = self._frame_span(first, last)
-        return (self.ih, a, b - a) if b - a <= self._chunk_samples() else None      # (one fetch only)
-
-    def _compute_frames(self, first, last, out):
-        a, b = self._frame_span(first, last)          # (frames and the stream are whole blocks)
-        per = self._chunk_samples()
-        for c0 in range(a, b, per):
-            c1 = min(b, c0 + per)
-            x = fetch_device(self.ih, c0, c1 - c0)
-            hip.rank_standardize(x, self.n, self._n_elem, out=out[c0 - a:c1 - a])
-
-    def _repr_item(self, key, default, value=None):
-        if key == 'samples_per_frame' and default is None:
-            default = min(-(-self._ih_samples_per_frame // self.n) * self.n, self.shape[0])
-        return super()._repr_item(key, default, value)
+    def _launch(self, x, start, count, out, c0, c1):
+        hip.rank_standardize(x, self.n, self._n_elem, out=out)
 
 
-class BoxcarSearch(DeviceTaskMixin, BaseTaskBase):
+class BoxcarSearch(ChunkedDeviceTask, BaseTaskBase):
     """The best boxcar S/N in every block of ``n`` start times, per element of a sample: a pulse of
     unknown width is matched-filtered with boxcars of widths 1, 2, 4, ... and the best one kept.
 
@@ -701,15 +656,10 @@ class BoxcarSearch(DeviceTaskMixin, BaseTaskBase):
             raise ValueError(f"the stream has {ih.shape[0]} samples: less than one block of {n}.")
         self._n_elem = _prod(ih.shape[1:])
         self._halo = (1 << (self.n_widths - 1)) - 1
-        self._plan = None
-        lone = _lone_frequency(ih)
-        super().__init__(ih, shape=(ih.shape[0] // n, 3) + tuple(ih.shape[1:]), sample_rate=_stream_rate(ih) / n,
-                         samples_per_frame=samples_per_frame, dtype=np.float32,
-                         **(dict(sideband=1) if lone else {}))
-        if lone:
-            del self.meta['__attributes__']['sideband']
+        _init_with_band_of(self, ih, shape=(ih.shape[0] // n, 3) + tuple(ih.shape[1:]),
+                           sample_rate=_stream_rate(ih) / n, samples_per_frame=samples_per_frame, dtype=np.float32)
 
-    def _chunk_blocks(self):
+    def _chunk_size(self):
         row = self._n_elem * 4
         return max(1, (int(self.sps_budget) - 3 * self._halo * row) // (3 * self.n * row + 3 * row))
 
@@ -718,24 +668,8 @@ class BoxcarSearch(DeviceTaskMixin, BaseTaskBase):
         start = b0 * self.n
         return start, min(self.ih.shape[0], b1 * self.n + self._halo) - start
 
-    def _input_span(self, first, last):
-        a, b = self._frame_span(first, last)
-        return (self.ih,) + self._chunk_input(a, b) if b - a <= self._chunk_blocks() else None    # (one fetch only)
+    def _make_plan(self):
+        return hip.SpsPlan(self.n, self.n_widths, self._n_elem)
 
-    def _compute_frames(self, first, last, out):
-        if self._plan is None:
-            self._plan = hip.SpsPlan(self.n, self.n_widths, self._n_elem)
-        a, b = self._frame_span(first, last)
-        per = self._chunk_blocks()
-        for c0 in range(a, b, per):
-            c1 = min(b, c0 + per)
-            start, n_in = self._chunk_input(c0, c1)
-            x = fetch_device(self.ih, start, n_in)
-            self._plan.execute(x, n_in, out[c0 - a:c1 - a], c1 - c0)
-
-    def close(self):
-        super().close()
-        self._drop_cache()
-        if self._plan is not None:
-            self._plan.close()
-            self._plan = None
+    def _launch(self, x, start, count, out, c0, c1):
+        self._plan.execute(x, count, out, c1 - c0)

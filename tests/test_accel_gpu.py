@@ -103,7 +103,7 @@ def test_no_value_depends_on_the_budget_the_framing_or_a_seek(name):
     for per in (1, 37, 3 * n // 4):
         task = _task(case, x, bt.DeviceStream, samples_per_frame=rows)
         task.accel_budget = per * row_bytes
-        assert task._chunk_rows() == per
+        assert task._chunk_size() == per
         assert same_words(task.read(), want), per
         task.close()
     for spf in (1, 7, n):

@@ -196,9 +196,9 @@ def test_input_span_is_the_window():
         assert span[0] is src and span[1:] == (lo, hi + 1 - lo), (first, last)
     # more rows than a chunk holds: no single fetch
     task.accel_budget = 17 * 5 * 3 * 4
-    assert task._chunk_rows() == 17 and task._input_span(0, 2) is None and task._input_span(0, 1) is not None
+    assert task._chunk_size() == 17 and task._input_span(0, 2) is None and task._input_span(0, 1) is not None
     task.accel_budget = 1
-    assert task._chunk_rows() == 1
+    assert task._chunk_size() == 1
 
 
 def test_what_the_task_refuses():

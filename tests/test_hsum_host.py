@@ -372,7 +372,7 @@ def test_search_stream_surface(case):
     assert text.startswith('HarmonicSearch(ih') and 'ih: HostStream' in text
     assert hs._input_span(0, 1) == (sh, 0, case.N)
     hs.hsum_budget = 1                                         # (never less than a spectrum)
-    assert hs._chunk_spectra() == 1 and (hs._input_span(0, 1) is None) == (case.N > 1)
+    assert hs._chunk_size() == 1 and (hs._input_span(0, 1) is None) == (case.N > 1)
     hs.close()
     assert hs.closed
     default = bt.HarmonicSearch(sh, case.n)
@@ -391,7 +391,7 @@ def test_whiten_stream_surface():
     assert wh.samples_per_frame == 3 and wh.skip == 5
     assert wh._input_span(0, 1) == (sh, 0, 3)
     wh.whiten_budget = 2 * 2100 * 67 * 4
-    assert wh._chunk_spectra() == 2 and wh._input_span(0, 1) is None
+    assert wh._chunk_size() == 2 and wh._input_span(0, 1) is None
 
 
 def test_metadata():

@@ -245,9 +245,9 @@ def test_robust_standardize_surface():
     assert rs._input_span(0, 1) == (sh, 0, 150) and rs._input_span(1, 3) == (sh, 150, 300)
     assert bt.RobustStandardize.robust_budget == 1 << 29
     rs.robust_budget = 3 * 50 * 67 * 4
-    assert rs._chunk_samples() == 150 and rs._input_span(0, 1) == (sh, 0, 150) and rs._input_span(0, 2) is None
+    assert rs._chunk_size() == 150 and rs._input_span(0, 1) == (sh, 0, 150) and rs._input_span(0, 2) is None
     rs.robust_budget = 1
-    assert rs._chunk_samples() == 50
+    assert rs._chunk_size() == 50
     flat = bt.RobustStandardize(rank_cases.stream(x[:, 0].copy()), 64)
     assert flat.shape == (2048,)
 
@@ -266,7 +266,7 @@ def test_median_whiten_surface():
     assert 'averaged=8' in repr(wh) and 'ratio' not in repr(wh)
     assert wh._input_span(0, 1) == (sh, 0, 3)
     wh.whiten_budget = 2 * 1501 * 7 * 4
-    assert wh._chunk_spectra() == 2 and wh._input_span(0, 1) is None
+    assert wh._chunk_size() == 2 and wh._input_span(0, 1) is None
     wh = bt.MedianWhiten(sh, 50, 0, ratio=0.9)
     assert wh.ratio == 0.9 and 'ratio=0.9' in repr(wh)
     for kwargs in (dict(averaged=2, ratio=0.8), dict(averaged=1.5), dict(averaged=0), dict(ratio=0.), dict(ratio=-1.),

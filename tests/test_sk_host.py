@@ -193,9 +193,9 @@ def test_excise_construction_framing_and_repr():
     assert bt.Excise(sh, 200).samples_per_frame == 200 and bt.Excise(sh, 1000).samples_per_frame == 1000
     # a byte budget makes chunks of whole blocks
     e2.excise_budget = 250 * 64
-    assert e2._chunk_samples() == 200
+    assert e2._chunk_size() == 200
     e2.excise_budget = 1
-    assert e2._chunk_samples() == 100
+    assert e2._chunk_size() == 100
     assert e2._input_span(0, 1) is None
     e2.excise_budget = 1 << 20
     assert e2._input_span(1, 3) == (sh, 500, 1000)

@@ -89,12 +89,12 @@ def run_row(name, reps):
 
     wh = bt.Whiten(stack, WHITEN_BLOCK)
     line['whiten_ms_min'], line['whiten_ms_med'] = timed(wh)
-    line['whiten_launches'] = -(-N_SPEC // wh._chunk_spectra())
+    line['whiten_launches'] = -(-N_SPEC // wh._chunk_size())
     wh.close()
     for k in row.get('levels', LEVELS):
         hs = bt.HarmonicSearch(stack, BLOCK, k)
         line[f'k{k}_ms_min'], line[f'k{k}_ms_med'] = timed(hs)
-        line[f'k{k}_launches'] = -(-N_SPEC // hs._chunk_spectra())
+        line[f'k{k}_launches'] = -(-N_SPEC // hs._chunk_size())
         hs.close()
     if row.get('yardsticks', True):
         words = N_SPEC * NBIN * NDM

@@ -93,7 +93,7 @@ def run_row(name, reps):
     for k in row.get('widths', WIDTHS):
         bs = bt.BoxcarSearch(plane, BLOCK, k, samples_per_frame=n // BLOCK)
         line[f'k{k}_ms_min'], line[f'k{k}_ms_med'] = timed(bs)
-        line[f'k{k}_launches'] = -(-bs.shape[0] // bs._chunk_blocks())
+        line[f'k{k}_launches'] = -(-bs.shape[0] // bs._chunk_size())
         line[f'k{k}_scratch_bytes'] = bs._plan.info()['scratch_bytes']
         bs.close()
     if row.get('yardsticks', True):
