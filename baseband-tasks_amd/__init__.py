@@ -25,7 +25,8 @@ from .modulation import Modulate, modulate_samples
 from .rfi import SpectralKurtosis, Excise, sk_limits, spectral_kurtosis, excise_flags, excise_samples
 from .search import (DMTrials, dm_trial_shifts, dm_trials_samples, Standardize, standardize_samples,
                      BoxcarSearch, boxcar_search_samples, boxcar_candidates, RobustStandardize,
-                     robust_standardize_samples, block_median_mad_samples)
+                     robust_standardize_samples, block_median_mad_samples, RunningMedian, Detrend,
+                     running_median_samples, detrend_samples)
 from . import search
 from .periodicity import (fluctuation_spectra, Whiten, whiten_samples, HarmonicSearch, harmonic_search_samples,
                           harmonic_scales, harmonic_candidates, LongSpectra, long_spectra_samples, Accelerate,

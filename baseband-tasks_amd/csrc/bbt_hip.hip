@@ -40,6 +40,7 @@
 #include "lspec_kernels.hpp"
 #include "accel_kernels.hpp"
 #include "rank_kernels.hpp"
+#include "rmed_kernels.hpp"
 #include "r2c_kernels.hpp"
 #include "gather_kernels.hpp"
 #include "pack_kernels.hpp"
@@ -49,7 +50,7 @@
 
 using namespace bbt;
 
-#define BBT_VERSION 169
+#define BBT_VERSION 170
 
 // ---------------------------------------------------------------------------
 // errors
@@ -3642,7 +3643,7 @@ extern "C" int bbt_shift_execute(bbt_shift_plan* p, const void* in_dev, void* ou
 }
 
 // ---------------------------------------------------------------------------
-// what the sections of the search chain share (dmt, sps, ffa, hsum, lspec, accel, rank)
+// what the sections of the search chain share (dmt, sps, ffa, hsum, lspec, accel, rank, rmed)
 
 // A tiling or routing knob from the environment: the value of `name` if it is one of `allowed`, else 0,
 // which stands for the section's default.  The contract of every knob below: it is read at every call,
@@ -4365,6 +4366,111 @@ extern "C" int bbt_rank_info(int64_t n_spec, int64_t nbin, int64_t n_elem, int64
         const int d = rank_env_digit() ? rank_env_digit() : BBT_RANK_DIGIT_LDS;
         lds_rows[0] = rank_lds_rows(16, d), lds_rows[1] = rank_lds_rows(32, d), lds_rows[2] = rank_lds_rows(64, d);
     }
+    return 0;
+}
+
+// ---------------------------------------------------------------------------
+// sliding-median baseline: RunningMedian, Detrend (rmed_kernels.hpp; the tiling is rmed_geo.hpp's)
+struct bbt_rmed_plan {
+    long long width = 0, scrunch = 0, n_elem = 0;
+    PlanScratch scratch;             // c[c0 ... c1) and m[m0 ... m1) of a call (scrunch > 1); the flags travel in them
+};
+
+// BBT_RMED_TILE: elements of a workgroup (16, 32, 64); BBT_RMED_ROWS: medians of a workgroup at most (16 ...
+// 1024); BBT_RMED_SELECT: 1 a fresh radix descent per median, 2 the walk from median to median.
+static int rmed_env_tile() { return env_knob("BBT_RMED_TILE", {16, 32, 64}); }
+static int rmed_env_rows() { return env_knob("BBT_RMED_ROWS", {16, 32, 64, 128, 256, 512, 1024}); }
+static int rmed_env_select() { return env_knob("BBT_RMED_SELECT", {BBT_RMED_SELECT_RADIX, BBT_RMED_SELECT_WALK}); }
+
+extern "C" int bbt_rmed_plan_destroy(bbt_rmed_plan* p) {
+    if (!p) return 0;
+    p->scratch.release();
+    delete p;
+    return 0;
+}
+
+extern "C" int bbt_rmed_plan_create(bbt_rmed_plan** plan, int64_t width, int64_t scrunch, int64_t n_elem) {
+    ARG_TRY(plan, "bbt_rmed_plan_create: null argument");
+    *plan = nullptr;
+    const char* err = rmed_sizes(width, scrunch, n_elem);
+    ARG_TRY(!err, "bbt_rmed_plan_create: %s (width=%lld, scrunch=%lld, n_elem=%lld)", err ? err : "", (long long)width,
+            (long long)scrunch, (long long)n_elem);
+    bbt_rmed_plan* p = new bbt_rmed_plan;
+    p->width = width, p->scrunch = scrunch, p->n_elem = n_elem;
+    *plan = p;
+    return 0;
+}
+
+// For the call that makes output samples [out_first, out_first + n_out) of a stream of n_rows scrunch rows:
+// the method (1 radix, 2 walk), the tile width, the medians of a workgroup, the LDS bytes of a workgroup, the
+// scratch bytes of the call, and the input samples it needs (first, count).  No device.
+extern "C" int bbt_rmed_info(int64_t width, int64_t scrunch, int64_t n_elem, int64_t n_rows, int64_t out_first,
+                             int64_t n_out, int* method, int* tile, int* rows, int64_t* lds_bytes,
+                             int64_t* scratch_bytes, int64_t* in_first, int64_t* in_count) {
+    RmedGeo g = {};
+    const char* err = rmed_sizes(width, scrunch, n_elem);
+    if (!err && (n_rows < 1 || n_rows > BBT_RMED_MAX_ROWS / scrunch)) err = "the stream must have 1 ... 2^40 / scrunch rows";
+    long long first = 0, count = 0;
+    if (!err && out_first >= 0 && n_out >= scrunch) {
+        long long m0, m1, c0, c1;
+        rmed_need(scrunch, width / 2, n_rows, out_first / scrunch, (out_first + n_out) / scrunch, &m0, &m1, &c0, &c1);
+        first = c0 * scrunch, count = (c1 - c0) * scrunch;
+    }
+    if (!err)
+        err = rmed_geo(width, scrunch, n_elem, n_rows, first, count, out_first, n_out, rmed_env_tile(), rmed_env_rows(),
+                       rmed_env_select(), &g);
+    ARG_TRY(!err, "bbt_rmed_info: %s (width=%lld, scrunch=%lld, n_elem=%lld, n_rows=%lld, out_first=%lld, n_out=%lld)",
+            err ? err : "", (long long)width, (long long)scrunch, (long long)n_elem, (long long)n_rows,
+            (long long)out_first, (long long)n_out);
+    if (method) *method = g.method;
+    if (tile) *tile = g.nx;
+    if (rows) *rows = g.run;
+    if (lds_bytes) *lds_bytes = g.lds_bytes;
+    if (scratch_bytes) *scratch_bytes = g.scratch_bytes;
+    if (in_first) *in_first = first;
+    if (in_count) *in_count = count;
+    return 0;
+}
+
+// out[i - out_first][e], out_first <= i < out_first + n_out, the baseline (mode 0) or x minus it (mode 1), from
+// in[i - in_first][e], in_first <= i < in_first + n_in, of a stream of n_rows scrunch rows.  One plan serves one
+// stream at a time: the scratch is the plan's.
+extern "C" int bbt_rmed_execute(bbt_rmed_plan* p, const float* in_dev, int64_t in_first, int64_t n_in, float* out_dev,
+                                int64_t out_first, int64_t n_out, int64_t n_rows, int mode, bbt_stream stream) {
+    ARG_TRY(p && in_dev && out_dev, "bbt_rmed_execute: null argument");
+    ARG_TRY(aligned4(in_dev, out_dev), "bbt_rmed_execute: arrays must be 4-byte aligned");
+    ARG_TRY(mode == BBT_RMED_BASELINE || mode == BBT_RMED_DETREND, "bbt_rmed_execute: mode must be 0 (baseline) or 1 (detrend)");
+    RmedGeo g = {};
+    const char* err = rmed_geo(p->width, p->scrunch, p->n_elem, n_rows, in_first, n_in, out_first, n_out, rmed_env_tile(),
+                               rmed_env_rows(), rmed_env_select(), &g);
+    ARG_TRY(!err, "bbt_rmed_execute: %s (n_rows=%lld, in_first=%lld, n_in=%lld, out_first=%lld, n_out=%lld)",
+            err ? err : "", (long long)n_rows, (long long)in_first, (long long)n_in, (long long)out_first, (long long)n_out);
+    g.mode = mode;
+    const long long n_c = g.c1 - g.c0, E = g.n_elem;
+    const long long wg_scrunch = (n_c * E + BBT_RMED_THREADS - 1) / BBT_RMED_THREADS;
+    const long long wg_apply = (g.n_out * E + BBT_RMED_THREADS - 1) / BBT_RMED_THREADS;
+    ARG_TRY(wg_scrunch < (1ll << 31) && wg_apply < (1ll << 31), "bbt_rmed_execute: too many values for one launch");
+    hipStream_t st = (hipStream_t)stream;
+    const dim3 grid((unsigned)g.n_wg), block(BBT_RMED_THREADS);
+    const size_t lds = (size_t)g.lds_bytes;
+    const float* x_c0 = in_dev + (g.c0 * g.S - g.in_first) * E;               // the first sample of scrunch row c0
+    if (g.S == 1) {
+        if (ensure_dyn_lds((const void*)k_rmed_select<true>, BBT_RANK_LDS_BYTES)) return 1;
+        hipLaunchKernelGGL((k_rmed_select<true>), grid, block, lds, st, (const unsigned*)x_c0, g.c0, out_dev, g);
+        HIP_TRY(hipGetLastError());
+        return 0;
+    }
+    if (ensure_dyn_lds((const void*)k_rmed_select<false>, BBT_RANK_LDS_BYTES)) return 1;
+    if (p->scratch.reserve((size_t)g.scratch_bytes)) return 1;
+    unsigned* c = (unsigned*)p->scratch.ptr;
+    unsigned* m = c + n_c * E;
+    hipLaunchKernelGGL(k_rmed_scrunch, dim3((unsigned)wg_scrunch), block, 0, st, x_c0, c, n_c, E, (int)g.S);
+    HIP_TRY(hipGetLastError());
+    hipLaunchKernelGGL((k_rmed_select<false>), grid, block, lds, st, (const unsigned*)c, g.c0, (float*)m, g);
+    HIP_TRY(hipGetLastError());
+    const float* x_out = in_dev + (g.out_first - g.in_first) * E;
+    hipLaunchKernelGGL(k_rmed_apply, dim3((unsigned)wg_apply), block, 0, st, x_out, (const unsigned*)m, out_dev, g);
+    HIP_TRY(hipGetLastError());
     return 0;
 }
 

@@ -140,6 +140,11 @@ SIGNATURES = {
     'bbt_rank_standardize': [_vp, _vp, _i64, _i64, _i64, _vp],
     'bbt_rank_whiten': [_vp, _vp, _i64, _i64, _i64, _i64, _i64, C.c_double, _vp],
     'bbt_rank_info': [_i64, _i64, _i64, _i64, _i64, C.POINTER(_int), C.POINTER(_int), C.POINTER(_int), _pi64, _pi64],
+    'bbt_rmed_plan_create': [_pvp, _i64, _i64, _i64],
+    'bbt_rmed_plan_destroy': [_vp],
+    'bbt_rmed_info': [_i64, _i64, _i64, _i64, _i64, _i64, C.POINTER(_int), C.POINTER(_int), C.POINTER(_int), _pi64, _pi64,
+                      _pi64, _pi64],
+    'bbt_rmed_execute': [_vp, _vp, _i64, _i64, _vp, _i64, _i64, _i64, _int, _vp],
     'bbt_fir_plan_create': [_pvp, _int, _int, _vp],
     'bbt_fir_plan_destroy': [_vp],
     'bbt_fir_execute': [_vp, _vp, _vp, _i64, _vp],
@@ -174,7 +179,7 @@ SIGNATURES = {
 }
 
 #: oldest libbbt_hip.so whose entry points and argument meanings this binding assumes
-MIN_LIB_VERSION = 169
+MIN_LIB_VERSION = 170
 
 _lib = None
 _lock = threading.Lock()
@@ -2063,6 +2068,60 @@ def rank_whiten(x, nbin, n_elem, m, skip=1, ratio=0.6931471805599453, out=None):
         raise ValueError(f"rank_whiten: out must be a float32 DeviceArray of {x.size} values")
     check(lib().bbt_rank_whiten(x.ptr_to_read(), out.ptr, n_spec, nbin, n_elem, m, skip, ratio, _stream))
     return out
+
+
+#: bounds of the sliding median (csrc/rmed_geo.hpp)
+RMED_MIN_WIDTH, RMED_MAX_WIDTH, RMED_MAX_SCRUNCH = 3, 1023, 4096
+RMED_METHODS = {1: 'radix', 2: 'walk'}
+RMED_BASELINE, RMED_DETREND = 0, 1
+
+
+def rmed_info(width, scrunch=1, n_elem=1, n_rows=1, out_first=0, n_out=None):
+    """For the call that makes output samples ``[out_first, out_first + n_out)`` (default: one scrunch row) of
+    a stream of ``n_rows`` scrunch rows: the selection method it takes now (BBT_RMED_SELECT; 'radix' or 'walk'),
+    the elements and the medians of a workgroup (BBT_RMED_TILE, BBT_RMED_ROWS), the LDS bytes of a workgroup,
+    the scratch bytes of the call and the input samples it needs, ``(in_first, in_count)``.  No device is
+    needed."""
+    method, tile, rows = _int(0), _int(0), _int(0)
+    lds, scratch, first, count = _i64(0), _i64(0), _i64(0), _i64(0)
+    n_out = int(scrunch) if n_out is None else int(n_out)
+    check(lib().bbt_rmed_info(int(width), int(scrunch), int(n_elem), int(n_rows), int(out_first), n_out, C.byref(method),
+                              C.byref(tile), C.byref(rows), C.byref(lds), C.byref(scratch), C.byref(first),
+                              C.byref(count)))
+    return dict(method=RMED_METHODS[method.value], tile=tile.value, rows=rows.value, lds_bytes=lds.value,
+                scratch_bytes=scratch.value, in_first=first.value, in_count=count.value)
+
+
+class RmedPlan(_Plan):
+    """The sliding-median baseline of a float32 stream of samples of ``n_elem`` elements: the median over
+    ``width`` points of the series scrunched by ``scrunch``, interpolated back to the samples, or the stream
+    minus it (bbt_rmed_* in include/bbt_hip.h; `search.running_median_samples` and `search.detrend_samples`
+    are the NumPy twins).  The plan owns the scratch of the scrunched series and its medians."""
+    _destroy = 'bbt_rmed_plan_destroy'
+
+    def __init__(self, width, scrunch=1, n_elem=1):
+        super().__init__()
+        self.width, self.scrunch, self.n_elem = int(width), int(scrunch), int(n_elem)
+        check(lib().bbt_rmed_plan_create(C.byref(self._h), self.width, self.scrunch, self.n_elem))
+
+    def info(self, n_rows=1, out_first=0, n_out=None):
+        """`rmed_info` for a call of this plan."""
+        return rmed_info(self.width, self.scrunch, self.n_elem, n_rows, out_first, n_out)
+
+    def execute(self, in_dev, in_first, n_in, out_dev, out_first, n_out, n_rows, detrend=True):
+        """``in_dev``: float32, at least ``n_in * n_elem`` values, samples ``[in_first, in_first + n_in)`` of the
+        stream; ``out_dev``: float32, at least ``n_out * n_elem``, for samples ``[out_first, out_first + n_out)``,
+        whole scrunch rows; ``n_rows``: the scrunch rows of the whole stream, at whose ends alone the windows
+        are clipped.  ``detrend``: the stream minus the baseline, else the baseline."""
+        in_first, n_in, out_first, n_out, n_rows = int(in_first), int(n_in), int(out_first), int(n_out), int(n_rows)
+        if in_dev.dtype != np.float32 or out_dev.dtype != np.float32:
+            raise TypeError("RmedPlan.execute: float32 DeviceArrays are needed")
+        if (n_in < 1 or n_out < 1 or in_first < 0 or out_first < 0 or in_dev.size < n_in * self.n_elem
+                or out_dev.size < n_out * self.n_elem):
+            raise ValueError("RmedPlan.execute: float32 DeviceArrays of n_in * n_elem and n_out * n_elem values are "
+                             "needed, n_in >= 1, n_out >= 1")
+        check(lib().bbt_rmed_execute(self._h, in_dev.ptr_to_read(), in_first, n_in, out_dev.ptr, out_first, n_out,
+                                     n_rows, RMED_DETREND if detrend else RMED_BASELINE, _stream))
 
 
 COMM_ID_BYTES = 128

@@ -13,7 +13,13 @@ channels added in ascending index; a boxcar sum is a fixed binary tree over its 
 
 `RobustStandardize` is `Standardize` with the block median and the median absolute deviation, both
 exact selections (csrc/rank_kernels.hpp; the twins are `block_median_mad_samples` and
-`robust_standardize_samples`): a bright pulse does not lower its own S/N."""
+`robust_standardize_samples`): a bright pulse does not lower its own S/N.
+
+`Detrend` subtracts a running baseline -- the sliding median over ``width`` points of the series
+scrunched by ``scrunch``, interpolated back to the samples -- and `RunningMedian` is that baseline
+(csrc/rmed_kernels.hpp; the twins are `detrend_samples` and `running_median_samples`): on red data a
+block baseline leaves a step at every block edge, which `FFASearch` folds and `BoxcarSearch` reads
+as a wide pulse."""
 import operator
 
 import numpy as np
@@ -26,6 +32,7 @@ from .dm import DispersionMeasure
 
 __all__ = ['DMTrials', 'dm_trial_shifts', 'dm_trials_samples', 'Standardize', 'standardize_samples',
            'RobustStandardize', 'robust_standardize_samples', 'block_median_mad_samples',
+           'RunningMedian', 'Detrend', 'running_median_samples', 'detrend_samples',
            'BoxcarSearch', 'boxcar_search_samples', 'boxcar_candidates', 'SNR', 'OFFSET', 'WIDTH']
 
 MAX_NCHAN, MAX_NDM = hip.DMT_MAX_NCHAN, hip.DMT_MAX_NDM
@@ -388,6 +395,126 @@ def robust_standardize_samples(data, n):
     return z.reshape((nb * n,) + data.shape[1:])
 
 
+# -- the sliding-median baseline -------------------------------------------------------------------------------
+MIN_WIDTH, MAX_WIDTH, MAX_SCRUNCH = hip.RMED_MIN_WIDTH, hip.RMED_MAX_WIDTH, hip.RMED_MAX_SCRUNCH
+
+
+def _check_window(width, scrunch):
+    width, scrunch = operator.index(width), operator.index(scrunch)
+    if not MIN_WIDTH <= width <= MAX_WIDTH or not width & 1:
+        raise ValueError(f"the width must be odd, {MIN_WIDTH} ... {MAX_WIDTH} points of the scrunched series, not {width}.")
+    if not 1 <= scrunch <= MAX_SCRUNCH:
+        raise ValueError(f"scrunch must be 1 ... {MAX_SCRUNCH}, not {scrunch}.")
+    return width, scrunch
+
+
+def _scrunch(x, scrunch):
+    """``x``: float32 ``(R * scrunch,) + s``: ``(c, bad)``, the scrunched series float32 ``(R,) + s`` and its bad
+    rows."""
+    rows = x.reshape((x.shape[0] // scrunch, scrunch) + x.shape[1:])
+    bad = (rows.view(np.uint32) & np.uint32(0x7f800000) == np.uint32(0x7f800000)).any(axis=1)
+    if scrunch == 1:
+        return rows[:, 0], bad
+    total = np.zeros((rows.shape[0],) + x.shape[1:], np.float64)
+    with np.errstate(all='ignore'):
+        for t0 in range(0, scrunch, SEGMENT):
+            a = np.zeros_like(total)
+            for t in range(t0, min(t0 + SEGMENT, scrunch)):
+                a = a + rows[:, t].astype(np.float64)
+            total = total + a
+        return (total / np.float64(scrunch)).astype(np.float32), bad
+
+
+def _running_median(c, bad, width):
+    """``(m, flagged)`` of the scrunched series ``c``, float32 ``(R,) + s``, with bad rows ``bad``."""
+    nrow, h = c.shape[0], width // 2
+    m = np.empty_like(c)
+    first_full, end_full = h, nrow - h                            # rows [h, R - h) have the whole window
+    if end_full > first_full:
+        keys = _rank_keys(c)
+        windows = np.lib.stride_tricks.sliding_window_view(keys, width, axis=0)         # (R - 2 h,) + s + (width,)
+        per = max(1, (1 << 26) // (width * max(_prod(c.shape[1:]), 1) * 4))
+        for r0 in range(0, windows.shape[0], per):
+            mid = np.partition(windows[r0:r0 + per], h, axis=-1)[..., h]
+            value = _rank_values(mid)
+            m[first_full + r0:first_full + r0 + value.shape[0]] = _block_median(np.stack([value, value], axis=1))
+    for r in list(range(min(first_full, nrow))) + list(range(max(end_full, first_full, 0), nrow)):
+        m[r] = _block_median(c[np.newaxis, max(0, r - h):r + h + 1])[0]
+    count = np.concatenate([np.zeros((1,) + bad.shape[1:], np.int64), np.cumsum(bad, axis=0, dtype=np.int64)])
+    rows = np.arange(nrow)
+    flagged = count[np.minimum(rows + h + 1, nrow)] - count[np.maximum(rows - h, 0)] > 0
+    return m, flagged
+
+
+def _baseline(data, width, scrunch, who):
+    """``(x, b, flagged)``: the samples that count, their baseline and where it is flagged."""
+    data = _check_plane(data, who)
+    width, scrunch = _check_window(width, scrunch)
+    nrow = data.shape[0] // scrunch
+    if nrow < 1:
+        raise ValueError(f"{who}: {data.shape[0]} samples are less than one scrunch row of {scrunch}.")
+    x = np.ascontiguousarray(data[:nrow * scrunch])
+    c, bad = _scrunch(x, scrunch)
+    m, flagged = _running_median(c, bad, width)
+    if nrow == 1:
+        r0 = np.zeros(scrunch, np.int64)
+        q = np.zeros(scrunch, np.int64)
+        r1 = r0
+    else:
+        j = 2 * np.arange(nrow * scrunch, dtype=np.int64) + 1 - scrunch
+        r0 = np.clip(j // (2 * scrunch), 0, nrow - 2)
+        q = j - 2 * scrunch * r0
+        r1 = r0 + 1
+    f = (q.astype(np.float64) / np.float64(2 * scrunch)).astype(np.float32)
+    shape = (-1,) + (1,) * (x.ndim - 1)
+    below, above = (q <= 0).reshape(shape), (q >= 2 * scrunch).reshape(shape)
+    lo, hi = m[r0], m[r1]
+    with np.errstate(all='ignore'):
+        d = hi - lo
+        p = d * f.reshape(shape)
+        between = lo + p
+    assert between.dtype == np.float32
+    b = np.where(below, lo, np.where(above, hi, between))
+    flagged = np.where(below, flagged[r0], np.where(above, flagged[r1], flagged[r0] | flagged[r1]))
+    return x, b, flagged
+
+
+def running_median_samples(data, width, scrunch=1):
+    """NumPy restatement of the `RunningMedian` kernels: the sliding-median baseline of every element.
+
+    ``data``: float32 ``(N,) + s``.  With ``S = scrunch``, ``w = width`` (odd), ``h = w // 2`` and ``R = N // S`` (the
+    tail of ``N % S`` samples is dropped):
+
+    1. ``c[r] = x[r]`` for ``S = 1``; else ``c[r] = float32(T / S)`` with ``T`` the float64 sum of ``x[r S ... r S + S -
+       1]`` in the two-level order of `standardize_samples` (segments of 32 summed in order, the segment sums
+       added in order).  Row ``r`` is bad if one of its samples is a NaN or an Inf.
+    2. ``m[r]`` is the median, by the rule of `block_median_mad_samples`, of ``c[max(0, r - h) ... min(R - 1, r +
+       h)]``: clipped at the two ends of the stream, where it is shorter and can be even.  It is flagged if the
+       window holds a bad row.
+    3. With ``j = 2 i + 1 - S``: ``b[i] = m[0]`` if ``R = 1``; else ``r0 = clip(j // 2 S, 0, R - 2)``, ``q = j - 2 S r0``, and
+       ``b[i] = m[r0]`` if ``q <= 0``, ``m[r0 + 1]`` if ``q >= 2 S``, else ``m[r0] + (m[r0 + 1] - m[r0]) * float32(float64(q) /
+       float64(2 S))``, three rounded float32 operations: the medians stand at the centres of their rows
+       and are joined by straight lines; before the first centre and after the last the baseline is flat.
+       ``b[i]`` is flagged if an ``m`` it used is.
+
+    Returns ``b``, float32 ``(R S,) + s``, +0 where flagged."""
+    x, b, flagged = _baseline(data, width, scrunch, 'running_median_samples')
+    b[flagged] = 0.
+    return b
+
+
+def detrend_samples(data, width, scrunch=1):
+    """NumPy restatement of the `Detrend` kernels: ``x[i] - b[i]`` with the baseline of `running_median_samples`
+    before its flags are applied, one rounded float32 subtract; +0 where the baseline is flagged.  Returns
+    float32 ``((N // scrunch) * scrunch,) + s``."""
+    x, b, flagged = _baseline(data, width, scrunch, 'detrend_samples')
+    with np.errstate(all='ignore'):
+        z = x - b
+    assert z.dtype == np.float32
+    z[flagged] = 0.
+    return z
+
+
 def boxcar_search_samples(data, n, n_widths=MAX_WIDTHS):
     """NumPy restatement of the `BoxcarSearch` kernels.
 
@@ -571,7 +698,7 @@ class Standardize(_BlockStandardize):
     `Excise` leaves) or holds a NaN or an Inf comes out as +0.  There is no median / MAD, no running
     baseline, and a pulse's own power is not clipped from the estimate: a bright pulse in a short
     block lowers its own S/N.  Choose blocks much longer than the widest boxcar.  `RobustStandardize` is
-    the median / MAD counterpart."""
+    the median / MAD counterpart.  Where the baseline drifts within a block, put `Detrend` in front."""
 
     #: input bytes fetched at most per `fetch_device` call and launch (assignable); a chunk is a
     #: whole number of blocks
@@ -604,7 +731,7 @@ class RobustStandardize(_BlockStandardize):
     route, the tiling or the chunking.  A block that holds a NaN or an Inf, or in which more than half
     of the values are equal (``mad = 0``: constant, all zero, what `Excise` leaves) comes out as +0.  The
     scale is that of normal noise; there is no clipping and re-estimation, no running median, and no
-    percentile other than the median."""
+    percentile other than the median.  The running median is `Detrend`, which goes in front of this task."""
 
     #: input bytes fetched at most per `fetch_device` call and launch (assignable); a chunk is a
     #: whole number of blocks
@@ -613,6 +740,118 @@ class RobustStandardize(_BlockStandardize):
 
     def _launch(self, x, start, count, out, c0, c1):
         hip.rank_standardize(x, self.n, self._n_elem, out=out)
+
+
+class _SlidingMedian(ChunkedDeviceTask, BaseTaskBase):
+    """What `RunningMedian` and `Detrend` share, which differ in what the last kernel writes (``_detrend``):
+    frames and chunks of whole scrunch rows, and per chunk the rows of the stream its windows reach."""
+    _detrend = None
+
+    #: bytes of input, scratch and output at most per `fetch_device` call and launch (assignable); a chunk
+    #: is a whole number of scrunch rows
+    detrend_budget = 1 << 29
+
+    def __init__(self, ih, width, scrunch=1, *, samples_per_frame=None):
+        _check_plane_stream(ih, type(self).__name__)
+        self.width, self.scrunch = width, scrunch = _check_window(width, scrunch)
+        if ih.shape[0] < scrunch:
+            raise ValueError(f"the stream has {ih.shape[0]} samples: less than one scrunch row of {scrunch}.")
+        self._n_elem = _prod(ih.shape[1:])
+        self._n_rows = ih.shape[0] // scrunch
+        length = self._n_rows * scrunch
+        if samples_per_frame is None:
+            samples_per_frame = min(-(-operator.index(ih.samples_per_frame) // scrunch) * scrunch, length)
+        samples_per_frame = operator.index(samples_per_frame)
+        if samples_per_frame < scrunch or samples_per_frame % scrunch:
+            raise ValueError(f"samples_per_frame must be a multiple of scrunch, {scrunch}; got {samples_per_frame}.")
+        _init_with_band_of(self, ih, shape=(length,) + tuple(ih.shape[1:]), samples_per_frame=samples_per_frame,
+                           dtype=np.float32)
+
+    def _chunk_size(self):
+        s, row = self.scrunch, self._n_elem * 4
+        per_row = 2 * s * row + (2 * row if s > 1 else 0)             # input and output; c and m
+        halo = (self.width + 1) * (s * row + (row if s > 1 else 0))   # the w - 1 rows the windows reach, the 2 neighbours
+        return max(1, (int(self.detrend_budget) - halo) // per_row) * s
+
+    def _chunk_input(self, c0, c1):
+        """The input samples output samples [c0, c1) need (whole scrunch rows): (first, count) -- the rows
+        the windows of their medians reach, the interpolation's neighbours included (rmed_need in
+        csrc/rmed_geo.hpp)."""
+        s, h, rows = self.scrunch, self.width // 2, self._n_rows
+        near = 1 if s > 1 else 0
+        first = max(0, max(0, c0 // s - near) - h)
+        last = min(rows, min(rows, c1 // s + near) + h)
+        return first * s, (last - first) * s
+
+    def _make_plan(self):
+        return hip.RmedPlan(self.width, self.scrunch, self._n_elem)
+
+    def _launch(self, x, start, count, out, c0, c1):
+        self._plan.execute(x, start, count, out, c0, c1 - c0, self._n_rows, detrend=self._detrend)
+
+    def _repr_item(self, key, default, value=None):
+        if key == 'samples_per_frame' and default is None:
+            default = min(-(-self._ih_samples_per_frame // self.scrunch) * self.scrunch, self.shape[0])
+        return super()._repr_item(key, default, value)
+
+
+class RunningMedian(_SlidingMedian):
+    """The running baseline of a stream: the sliding median over ``width`` points of the series scrunched by
+    ``scrunch``, interpolated back to the samples, per element of a sample.  `Detrend` is the stream minus it.
+
+    Parameters
+    ----------
+    ih : stream
+        float32, any sample shape -- usually the (time, DM) plane of `DMTrials`.
+    width : int
+        Points of the scrunched series in a window: odd, 3 ... 1023.  The window spans ``width * scrunch``
+        samples; choose it a few times longer than the widest pulse that is to survive.
+    scrunch : int, optional
+        Samples averaged into one point of the series the median runs over, 1 ... 4096, counted from sample
+        0 of ``ih``; a tail shorter than ``scrunch`` is dropped.  The cost grows with ``width`` per scrunched
+        point, so a long window is a moderate ``width`` on a scrunched series: 2 s at 1 ms sampling is
+        ``width=125, scrunch=16``, not a width of 2001.  Default 1.
+    samples_per_frame : int, optional
+        A multiple of ``scrunch``.  Default: the smallest one that is at least ``ih.samples_per_frame``, at
+        most the length of the output.
+
+    Sample rate, start time and metadata are those of ``ih``; the length is ``(len // scrunch) * scrunch``.
+    The windows are clipped at the two ends of the stream (never at a frame or a chunk), the medians stand
+    at the centres of their scrunch rows and are joined by straight lines, flat before the first centre and
+    after the last.  A NaN or an Inf makes +0 of every output whose baseline has it in a window.  The rule
+    is stated in full in `running_median_samples`; a median is an exact selection and the scrunch and the
+    interpolation fix their order, so the values equal that function bit for bit, whatever the selection
+    method, the tiling, the budget, the framing or the seek.  There are no reflected or extrapolated ends,
+    no clipping of a pulse out of the window, no running MAD, and no percentile other than the median."""
+    _detrend = False
+
+
+class Detrend(_SlidingMedian):
+    """Subtract the running baseline of `RunningMedian` from a stream, per element of a sample: what goes in
+    front of `Standardize` and the searches where the data are red -- a block baseline leaves a step at
+    every block edge and the drift inside a block, which `FFASearch` folds coherently and `BoxcarSearch` reads
+    as a wide pulse.
+
+    Parameters
+    ----------
+    ih : stream
+        float32, any sample shape -- usually the (time, DM) plane of `DMTrials`.
+    width : int
+        Points of the scrunched series in a window: odd, 3 ... 1023.
+    scrunch : int, optional
+        Samples averaged into one point of the series the median runs over, 1 ... 4096; a tail shorter
+        than ``scrunch`` is dropped.  Default 1.
+    samples_per_frame : int, optional
+        A multiple of ``scrunch``.  Default: the smallest one that is at least ``ih.samples_per_frame``, at
+        most the length of the output.
+
+    ``out[i] = ih[i] - b[i]`` with ``b`` the baseline of `RunningMedian` (see there for the parameters and the
+    ends), one rounded float32 subtract, and +0 where the baseline is flagged.  Sample rate, start time and
+    metadata are those of ``ih``.  The values equal `detrend_samples` bit for bit, whatever the selection
+    method, the tiling, the budget, the framing or the seek.  For ``scrunch=1`` one kernel reads ``ih`` once and
+    writes the result once; otherwise the scrunched series and its medians pass through a scratch the plan
+    owns.  The scale is left alone: ``Standardize(Detrend(plane, 65, scrunch=16), 4096)``."""
+    _detrend = True
 
 
 class BoxcarSearch(ChunkedDeviceTask, BaseTaskBase):

@@ -52,6 +52,7 @@ typedef struct bbt_ffa_plan bbt_ffa_plan;
 typedef struct bbt_hsum_plan bbt_hsum_plan;
 typedef struct bbt_lspec_plan bbt_lspec_plan;
 typedef struct bbt_accel_plan bbt_accel_plan;
+typedef struct bbt_rmed_plan bbt_rmed_plan;
 typedef struct bbt_fir_plan bbt_fir_plan;
 typedef struct bbt_r2c_plan bbt_r2c_plan;
 typedef struct bbt_gather_plan bbt_gather_plan;
@@ -747,6 +748,50 @@ int bbt_rank_whiten(const float* x_dev, float* out_dev, int64_t n_spec, int64_t 
                     int64_t skip, double ratio, bbt_stream stream);
 int bbt_rank_info(int64_t n_spec, int64_t nbin, int64_t n_elem, int64_t m, int64_t skip, int* route, int* digit,
                   int* width, int64_t* lds_bytes, int64_t* lds_rows);
+
+/* ---- sliding-median baseline: RunningMedian, Detrend ----------------------------
+ * The stream is x[i][e], i < N, e < n_elem, float32, element fastest.  S = scrunch (1 ... 4096), w = width
+ * (odd, 3 ... 1023, in points of the scrunched series), h = w / 2, R = N / S = n_rows; the tail of N % S
+ * samples belongs to no row.  Everything is per element.
+ *
+ * 1. Scrunch: c[r] = x[r] for S = 1, the 32 bits copied; for S > 1 c[r] = (float)(T / S), T the double sum of
+ *    x[r S ... r S + S - 1] in the two-level order of bbt_sps_standardize: segments of 32 summed in order,
+ *    the segment sums added in order.  Row r is bad if one of its S samples is a NaN or an Inf, by the
+ *    bit test (bits & 0x7f800000) == 0x7f800000.
+ * 2. Running median: window r holds c[max(0, r - h) ... min(R - 1, r + h)]: clipped at the two ends of the
+ *    STREAM (shorter there, possibly even), never at the edge of a call.  With L its length, lo the value
+ *    of rank (L - 1) / 2 and hi of rank L / 2 in the order of the block median's key (above), m[r] =
+ *    (float)(((double)lo + (double)hi) * 0.5).  m[r] is flagged if the window holds a bad row.
+ * 3. Back to samples: for sample i, j = 2 i + 1 - S.  If R = 1, b = m[0].  Otherwise r0 = clamp(floor(j /
+ *    2 S), 0, R - 2), q = j - 2 S r0; b = m[r0] if q <= 0, b = m[r0 + 1] if q >= 2 S, else f = (float)((double)q
+ *    / (double)(2 S)) and b = m[r0] + (m[r0 + 1] - m[r0]) * f: three float32 operations, each rounded once, no
+ *    fused multiply-add.  For S = 1 this is b[i] = m[i].  b is flagged if an m it used is flagged.
+ * 4. mode 0 (RunningMedian): out = b; mode 1 (Detrend): out = x[i] - b, one rounded float32 subtract; +0
+ *    where flagged.
+ *
+ * bbt_rmed_execute makes output samples [out_first, out_first + n_out) -- both multiples of S, inside [0,
+ * R S) -- from in_dev, which holds samples [in_first, in_first + n_in) of the stream, in_first a multiple
+ * of S.  Output scrunch rows [ro0, ro1) read medians [max(0, ro0 - 1), min(R, ro1 + 1)) for S > 1 and [ro0,
+ * ro1) for S = 1; medians [m0, m1) read scrunch rows [max(0, m0 - h), min(R, m1 + h)): the input must hold
+ * these whole, and a call that lacks them is refused.  out may not overlap in.
+ *
+ * A selection is exact and steps 1 and 3 fix their order, so results do not depend on the call, the tiling
+ * or the method: BBT_RMED_TILE = 16, 32 or 64 elements per workgroup, BBT_RMED_ROWS = 16 ... 1024 medians
+ * per workgroup at most, BBT_RMED_SELECT = 1 (a fresh radix descent per median) or 2 (the median walked
+ * from window to window), read from the environment at every call, only change the speed.  The plan owns
+ * c and m of a call (S > 1; a bad row and a flagged median are stored as NaN, so the flags need no array
+ * of their own); S = 1 needs no scratch.  bbt_rmed_info, for such a call: the method, the tile width, the
+ * medians of a workgroup, the LDS bytes of a workgroup (72 KiB at most), the scratch bytes, and the input
+ * samples the call needs (first, count).  It needs no device.  Every refusal -- a null or misaligned
+ * pointer, a size out of range, an input that does not cover the windows -- comes before anything is
+ * launched.  Asynchronous on `stream`. */
+int bbt_rmed_plan_create(bbt_rmed_plan** plan, int64_t width, int64_t scrunch, int64_t n_elem);
+int bbt_rmed_plan_destroy(bbt_rmed_plan* plan);
+int bbt_rmed_info(int64_t width, int64_t scrunch, int64_t n_elem, int64_t n_rows, int64_t out_first, int64_t n_out,
+                  int* method, int* tile, int* rows, int64_t* lds_bytes, int64_t* scratch_bytes, int64_t* in_first,
+                  int64_t* in_count);
+int bbt_rmed_execute(bbt_rmed_plan* plan, const float* in_dev, int64_t in_first, int64_t n_in, float* out_dev,
+                     int64_t out_first, int64_t n_out, int64_t n_rows, int mode, bbt_stream stream);
 
 /* ---- real-valued streams ------------------------------------------------------
  * float32 streams run through the complex kernels (the reference's rfft/irfft
