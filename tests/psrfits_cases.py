@@ -5,44 +5,6 @@ test_psrfits_search_host.py feed every one of them, without a GPU, through the l
 tests/psrsearch_geo_check.cpp) and prove with the ledgers below that together they launch every
 template instantiation of the kernels and reach every ragged edge of the tiling.  A case list that
 stops covering a path fails there, on any machine, and the ledger names the path."""
-import json
-import os
-import subprocess
-from concurrent.futures import ThreadPoolExecutor
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CSRC = os.path.join(ROOT, 'baseband-tasks_amd', 'csrc')
-
-
-def compile_check(name, where):
-    """tests/<name>.cpp as a stand-alone program under ASan and UBSan; its path."""
-    exe = os.path.join(str(where), name)
-    subprocess.check_call(['g++', '-O1', '-g', '-std=c++17', '-fsanitize=address,undefined',
-                           '-fno-sanitize-recover=undefined', '-I', CSRC,
-                           os.path.join(ROOT, 'tests', name + '.cpp'), '-o', exe])
-    return exe
-
-
-def run_check(exe, shapes, through_stdin=False):
-    """The program's JSON line for each of `shapes` (tuples of integers), given as arguments or, a
-    long list, on the standard input of four copies of the program, a quarter each; the walks must
-    pass."""
-    lines = [' '.join(str(int(v)) for v in shape) for shape in shapes]
-    keys = dict(stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True)
-    if through_stdin:
-        step = -(-len(lines) // 4)
-        with ThreadPoolExecutor(4) as pool:
-            outs = list(pool.map(lambda start: subprocess.run([exe], input='\n'.join(lines[start:start + step]), **keys),
-                                 range(0, len(lines), step)))
-    else:
-        outs = [subprocess.run([exe] + ' '.join(lines).split(), **keys)]
-    done = [(out.stdout, out.stderr, out.returncode) for out in outs]
-    for stdout, stderr, code in done:
-        assert code == 0, stdout[-2000:] + stderr[-4000:]
-    plans = [json.loads(line) for stdout, _, _ in done for line in stdout.splitlines()]
-    assert len(plans) == len(shapes)
-    return plans
-
 
 # -- search mode -----------------------------------------------------------------------------------
 #: ((nrow, nsblk, nchan, npol), nbits): one tile of 64 columns at every width (the 1-bit rows leave as

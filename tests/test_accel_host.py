@@ -5,7 +5,6 @@ walked on the host under the sanitizers and compared with the NumPy rule (tests/
 import json
 import os
 import re
-import subprocess
 
 import numpy as np
 import pytest
@@ -16,6 +15,7 @@ from baseband_tasks_amd.periodicity import LEVEL, OFFSET, SNR
 
 import accel_cases
 from accel_cases import CASES, IDS, RATE, T0, same_words, words
+from geo_check import compile_check, run_check, run_raw
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CSRC = os.path.join(ROOT, 'baseband-tasks_amd', 'csrc')
@@ -359,11 +359,7 @@ def test_library_exports_and_limits():
 # -- the index maps -----------------------------------------------------------------------------------------
 @pytest.fixture(scope='module')
 def geo_check(tmp_path_factory):
-    exe = str(tmp_path_factory.mktemp('accel') / 'accel_geo_check')
-    subprocess.check_call(['g++', '-O2', '-g', '-std=c++17', '-fsanitize=address,undefined',
-                           '-fno-sanitize-recover=undefined', '-I', CSRC,
-                           os.path.join(ROOT, 'tests', 'accel_geo_check.cpp'), '-o', exe])
-    return exe
+    return compile_check('accel_geo_check', tmp_path_factory.mktemp('accel'), opt='-O2')
 
 
 def _walk_groups():
@@ -392,11 +388,13 @@ def _walk_groups():
     return groups
 
 
+def _hex(factors):
+    return tuple(float(k).hex() for k in factors)
+
+
 def _walk_args(groups):
-    args = []
-    for n_rows, n, n_elem, unit, route, chunk, factors in groups:
-        args += [str(v) for v in (n_rows, n, n_elem, unit, route, chunk, len(factors))] + [float(k).hex() for k in factors]
-    return args
+    return [(n_rows, n, n_elem, unit, route, chunk, len(factors)) + _hex(factors)
+            for n_rows, n, n_elem, unit, route, chunk, factors in groups]
 
 
 def test_kernel_indexing_on_the_host(geo_check):
@@ -405,11 +403,7 @@ def test_kernel_indexing_on_the_host(geo_check):
     declares, and every tile lies in one block: the program reports otherwise, and the sanitizers abort it
     on a wild index or an overflow of its own."""
     groups = _walk_groups()
-    out = subprocess.run([geo_check, 'walk'] + _walk_args(groups), stdout=subprocess.PIPE, stderr=subprocess.PIPE,
-                         text=True)
-    assert out.returncode == 0, out.stdout[-2000:] + out.stderr[-2000:]
-    lines = [json.loads(line) for line in out.stdout.splitlines()]
-    assert len(lines) == len(groups)
+    lines = run_check(geo_check, _walk_args(groups), word='walk')
     past = 0
     for (n_rows, n, n_elem, unit, route, chunk, factors), g in zip(groups, lines):
         assert g.get('walk') == 0, g
@@ -435,8 +429,8 @@ def test_kernel_indexing_on_the_host(geo_check):
     assert [(seen[key]['n_seg'], seen[key]['ws'], seen[key]['rows']) for key in sorted(seen)] == [
         (2, 16384, 1), (4, 16384, 1), (1, 16384, 1), (5, 16384, 1), (2, 16384, 1)]
     # what the library refuses
-    bad = subprocess.run([geo_check, 'walk'] + '64 1 1 4 0 8 1 0  64 64 0 4 0 8 1 0  64 64 1 4 0 8 0  64 64 1 4 0 8 1 0.004'
-                         '  64 64 2 16 0 8 1 0  10 64 1 4 0 8 1 0'.split(), stdout=subprocess.PIPE, text=True)
+    bad = run_raw(geo_check, '64 1 1 4 0 8 1 0  64 64 0 4 0 8 1 0  64 64 1 4 0 8 0  64 64 1 4 0 8 1 0.004'
+                  '  64 64 2 16 0 8 1 0  10 64 1 4 0 8 1 0', word='walk')
     assert bad.returncode == 0
     errors = [json.loads(line)['error'] for line in bad.stdout.splitlines()]
     assert len(errors) == 6 and '2^24' in errors[0] and 'elements' in errors[1] and 'trials' in errors[2]
@@ -447,7 +441,7 @@ def test_kernel_indexing_on_the_host(geo_check):
 def test_the_rule_in_the_header_is_the_rule_in_numpy(case, geo_check, tmp_path):
     """accel_src of csrc/accel_geo.hpp -- what the launcher and the kernel call -- against `accelerate_rows`."""
     path = str(tmp_path / 'src.i64')
-    subprocess.check_call([geo_check, 'maps', str(case.n), path] + [float(k).hex() for k in case.factors])
+    assert run_raw(geo_check, [(case.n, path) + _hex(case.factors)], word='maps').returncode == 0
     got = np.fromfile(path, dtype=np.int64).reshape(len(case.factors), case.n)
     assert np.array_equal(got, periodicity.accelerate_rows(case.n, case.factors))
 
@@ -456,7 +450,7 @@ def test_the_rule_in_the_header_at_the_bound(geo_check, tmp_path):
     for n in (3, 1000, 1 << 22):
         k = [.25 / n, -.25 / n, .1 / n]
         path = str(tmp_path / f'src{n}.i64')
-        subprocess.check_call([geo_check, 'maps', str(n), path] + [float(v).hex() for v in k])
+        assert run_raw(geo_check, [(n, path) + _hex(k)], word='maps').returncode == 0
         assert np.array_equal(np.fromfile(path, dtype=np.int64).reshape(3, n), periodicity.accelerate_rows(n, k))
 
 

@@ -5,7 +5,6 @@ framing and the argument checks of both tasks, and the kernels' tiling (csrc/sps
 the host by a stand-alone program under sanitizers."""
 import json
 import os
-import subprocess
 
 import numpy as np
 import pytest
@@ -16,6 +15,7 @@ from baseband_tasks_amd.search import OFFSET, SNR, WIDTH
 
 import sps_cases
 from sps_cases import CASES, IDS, RATE, T0
+from geo_check import compile_check, run_check, run_raw
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CSRC = os.path.join(ROOT, 'baseband-tasks_amd', 'csrc')
@@ -418,16 +418,9 @@ def test_kernel_tiling_on_the_host(tmp_path):
     inside [0, n_in) of the chunk and inside what the pass before stored, every level stored on exactly
     the rows it is defined on, the limits and refusals: the program exits non-zero otherwise, and the
     sanitizers abort it on a wild index or an overflow of its own."""
-    exe = str(tmp_path / 'sps_geo_check')
-    subprocess.check_call(['g++', '-O1', '-g', '-std=c++17', '-fsanitize=address,undefined',
-                           '-fno-sanitize-recover=undefined', '-I', CSRC,
-                           os.path.join(ROOT, 'tests', 'sps_geo_check.cpp'), '-o', exe])
+    exe = compile_check('sps_geo_check', tmp_path)
     shapes = _geo_shapes()
-    out = subprocess.run([exe] + [str(v) for shape in shapes for v in shape], stdout=subprocess.PIPE,
-                         stderr=subprocess.PIPE, text=True)
-    assert out.returncode == 0, out.stdout + out.stderr
-    plans = [json.loads(line) for line in out.stdout.splitlines()]
-    assert len(plans) == len(shapes)
+    plans = run_check(exe, shapes)
     scales = search.BOXCAR_SCALES.view(np.uint32).tolist()
     for shape, g in zip(shapes, plans):
         assert g['walk'] == 0, (shape, g)
@@ -446,10 +439,10 @@ def test_kernel_tiling_on_the_host(tmp_path):
     big = [g for s, g in zip(shapes, plans) if s[0] == 0 and s[1] * s[5] > 2 ** 31]
     assert len(big) == 2 and all(g['scratch'] > 2 ** 32 for g in big)
     # what the library refuses: one sample short, no blocks, n_widths 0 and 14, a block of 0 and of 65537, bad tilings
-    bad = subprocess.run([exe] + ('0 99 10 10 1 3 0 0 0  0 100 0 10 1 3 0 0 0  0 100 10 10 0 3 0 0 0  0 100 10 10 14 3 0 0 0 '
-                                  '0 100 10 0 1 3 0 0 0  0 99999 1 65537 1 3 0 0 0  0 100 10 10 1 3 48 0 0 '
-                                  '0 100 10 10 1 3 0 4 0  0 100 10 10 1 3 0 0 3  1 3 1 5 0 0 0 0 0  1 0 2 5 0 0 0 0 0 '
-                                  '1 3 2 5 3 0 0 0 0').split(), stdout=subprocess.PIPE, text=True)
+    bad = run_raw(exe, '0 99 10 10 1 3 0 0 0  0 100 0 10 1 3 0 0 0  0 100 10 10 0 3 0 0 0  0 100 10 10 14 3 0 0 0 '
+                       '0 100 10 0 1 3 0 0 0  0 99999 1 65537 1 3 0 0 0  0 100 10 10 1 3 48 0 0 '
+                       '0 100 10 10 1 3 0 4 0  0 100 10 10 1 3 0 0 3  1 3 1 5 0 0 0 0 0  1 0 2 5 0 0 0 0 0 '
+                       '1 3 2 5 3 0 0 0 0')
     assert bad.returncode == 0
     errors = [json.loads(line)['error'] for line in bad.stdout.splitlines()]
     assert len(errors) == 12

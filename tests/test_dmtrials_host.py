@@ -5,7 +5,6 @@ argument checks, and the kernels' tiling (csrc/dmt_geo.hpp) walked on the host b
 program under sanitizers."""
 import json
 import os
-import subprocess
 import warnings
 
 import numpy as np
@@ -17,6 +16,7 @@ from baseband_tasks_amd.dm import DispersionMeasure
 
 import dmt_cases
 from dmt_cases import CASES, IDS, RATE, T0
+from geo_check import compile_check, run_check, run_raw
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CSRC = os.path.join(ROOT, 'baseband-tasks_amd', 'csrc')
@@ -278,16 +278,9 @@ def test_kernel_tiling_on_the_host(tmp_path):
     """Every (time, trial, r) of the result owned by exactly one wave, every read inside [0, n_in)
     of its row, the table validation refusing what it must: the program exits non-zero otherwise,
     and the sanitizers abort it on a wild index or an overflow of its own."""
-    exe = str(tmp_path / 'dmt_geo_check')
-    subprocess.check_call(['g++', '-O1', '-g', '-std=c++17', '-fsanitize=address,undefined',
-                           '-fno-sanitize-recover=undefined', '-I', CSRC,
-                           os.path.join(ROOT, 'tests', 'dmt_geo_check.cpp'), '-o', exe])
+    exe = compile_check('dmt_geo_check', tmp_path)
     shapes = _geo_shapes()
-    out = subprocess.run([exe] + [str(v) for shape in shapes for v in shape], stdout=subprocess.PIPE,
-                         stderr=subprocess.PIPE, text=True)
-    assert out.returncode == 0, out.stdout + out.stderr
-    plans = [json.loads(line) for line in out.stdout.splitlines()]
-    assert len(plans) == len(shapes)
+    plans = run_check(exe, shapes)
     for (n_in, n_out, nchan, rest, ndm, span, tile_t, db), g in zip(shapes, plans):
         assert g['walk'] == 0, (n_in, n_out, nchan, rest, ndm, span, tile_t, db, g)
         assert g['tile_t'] == (tile_t or 256) and g['db'] == (db or 8)
@@ -297,9 +290,8 @@ def test_kernel_tiling_on_the_host(tmp_path):
     big = [g for s, g in zip(shapes, plans) if s[0] * s[2] * s[3] > 2 ** 31]
     assert len(big) >= 2 and all(g['scratch'] > 2 ** 31 for g in big)
     # what the library refuses: one sample short, a bad tile, a bad trial block, beyond the limits
-    bad = subprocess.run([exe] + ('106 100 3 1 2 7 0 0  107 100 3 1 2 7 96 0  107 100 3 1 2 7 0 3  107 100 16385 1 2 7 0 0 '
-                                  '107 100 3 65 2 7 0 0  107 100 3 1 4097 7 0 0  16777317 100 3 1 2 16777217 0 0').split(),
-                         stdout=subprocess.PIPE, text=True)
+    bad = run_raw(exe, '106 100 3 1 2 7 0 0  107 100 3 1 2 7 96 0  107 100 3 1 2 7 0 3  107 100 16385 1 2 7 0 0 '
+                       '107 100 3 65 2 7 0 0  107 100 3 1 4097 7 0 0  16777317 100 3 1 2 16777217 0 0')
     assert bad.returncode == 0
     errors = [json.loads(line)['error'] for line in bad.stdout.splitlines()]
     assert len(errors) == 7

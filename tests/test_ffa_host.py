@@ -5,7 +5,6 @@ the bound on the shifts, the scales, hand-made ties, special values, the candida
 kernels' tiling (csrc/ffa_geo.hpp) walked on the host by a stand-alone program under sanitizers."""
 import json
 import os
-import subprocess
 
 import numpy as np
 import pytest
@@ -16,6 +15,7 @@ from baseband_tasks_amd.ffa import PHASE, SHIFT, SNR, WIDTH
 
 import ffa_cases
 from ffa_cases import CASES, IDS, RATE, T0
+from geo_check import compile_check, run_check, run_raw
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CSRC = os.path.join(ROOT, 'baseband-tasks_amd', 'csrc')
@@ -544,16 +544,9 @@ def test_kernel_tiling_on_the_host(tmp_path):
     rotations composing to the closed-form shifts, every (row, column) of the S/N pass held once inside the
     LDS buffer, the partial winners inside the spare buffer, the result cells inside the result: the program
     exits non-zero otherwise, and the sanitizers abort it on a wild index or an overflow of its own."""
-    exe = str(tmp_path / 'ffa_geo_check')
-    subprocess.check_call(['g++', '-O1', '-g', '-std=c++17', '-fsanitize=address,undefined',
-                           '-fno-sanitize-recover=undefined', '-I', CSRC,
-                           os.path.join(ROOT, 'tests', 'ffa_geo_check.cpp'), '-o', exe])
+    exe = compile_check('ffa_geo_check', tmp_path)
     shapes = _geo_shapes()
-    out = subprocess.run([exe] + [str(v) for shape in shapes for v in shape], stdout=subprocess.PIPE,
-                         stderr=subprocess.PIPE, text=True)
-    assert out.returncode == 0, out.stdout + out.stderr
-    plans = [json.loads(line) for line in out.stdout.splitlines()]
-    assert len(plans) == len(shapes)
+    plans = run_check(exe, shapes)
     for shape, g in zip(shapes, plans):
         assert g.get('walk') == 0, (shape, g)
         n, p_lo, p_hi, p, K, pitch, e0, ne, fuse, width = shape
@@ -566,10 +559,10 @@ def test_kernel_tiling_on_the_host(tmp_path):
     big = [g for g in plans if g['buf'] > 2 ** 31]
     assert len(big) >= 2
     # what the library refuses
-    bad = subprocess.run([exe] + ('100 3 9 8 1 3 0 3 0 0  100 8 52 8 1 3 0 3 0 0  100 8 9 8 11 3 0 3 0 0  100 8 9 8 5 3 0 3 0 0 '
-                                  '100 8 9 9 1 3 0 3 0 0  100 8 9 8 1 3 1 3 0 0  100 8 9 8 1 3 0 0 0 0  100 8 9 8 1 3 -1 2 0 0 '
-                                  '100 8 9 8 1 3 0 3 4 0  100 8 9 8 1 3 0 3 0 5  2048 1000 1025 1024 1 2000000 0 1048576 0 0 '
-                                  '262148 4 5 4 1 3 0 3 0 0  262144 256 512 511 6 20000 100 16500 2 16').split(), stdout=subprocess.PIPE, text=True)
+    bad = run_raw(exe, '100 3 9 8 1 3 0 3 0 0  100 8 52 8 1 3 0 3 0 0  100 8 9 8 11 3 0 3 0 0  100 8 9 8 5 3 0 3 0 0 '
+                       '100 8 9 9 1 3 0 3 0 0  100 8 9 8 1 3 1 3 0 0  100 8 9 8 1 3 0 0 0 0  100 8 9 8 1 3 -1 2 0 0 '
+                       '100 8 9 8 1 3 0 3 4 0  100 8 9 8 1 3 0 3 0 5  2048 1000 1025 1024 1 2000000 0 1048576 0 0 '
+                       '262148 4 5 4 1 3 0 3 0 0  262144 256 512 511 6 20000 100 16500 2 16')
     assert bad.returncode == 0
     errors = [json.loads(line)['error'] for line in bad.stdout.splitlines()]
     assert len(errors) == 13

@@ -5,7 +5,6 @@ rule on a hand-made plane, construction, metadata and the argument checks of the
 kernels' tiling (csrc/hsum_geo.hpp) walked on the host by a stand-alone program under sanitizers."""
 import json
 import os
-import subprocess
 
 import numpy as np
 import pytest
@@ -16,6 +15,7 @@ from baseband_tasks_amd.periodicity import LEVEL, OFFSET, SNR
 
 import hsum_cases
 from hsum_cases import CASES, IDS, RATE, T0
+from geo_check import compile_check, run_check, run_raw
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CSRC = os.path.join(ROOT, 'baseband-tasks_amd', 'csrc')
@@ -568,16 +568,9 @@ def test_kernel_tiling_on_the_host(tmp_path):
     index inside its spectrum, the whitening blocks tiling the bins, the limits and refusals: the
     program exits non-zero otherwise, and the sanitizers abort it on a wild index or an overflow of its
     own."""
-    exe = str(tmp_path / 'hsum_geo_check')
-    subprocess.check_call(['g++', '-O1', '-g', '-std=c++17', '-fsanitize=address,undefined',
-                           '-fno-sanitize-recover=undefined', '-I', CSRC,
-                           os.path.join(ROOT, 'tests', 'hsum_geo_check.cpp'), '-o', exe])
+    exe = compile_check('hsum_geo_check', tmp_path)
     shapes = _geo_shapes()
-    out = subprocess.run([exe] + [str(v) for shape in shapes for v in shape], stdout=subprocess.PIPE,
-                         stderr=subprocess.PIPE, text=True)
-    assert out.returncode == 0, out.stdout + out.stderr
-    plans = [json.loads(line) for line in out.stdout.splitlines()]
-    assert len(plans) == len(shapes)
+    plans = run_check(exe, shapes)
     for shape, g in zip(shapes, plans):
         assert g['walk'] == 0, (shape, g)
         if shape[0] == 0:
@@ -594,11 +587,11 @@ def test_kernel_tiling_on_the_host(tmp_path):
     assert sum(1 for s in shapes if s[0] == 0 and s[2] == 1 << 24) == 3
     # what the library refuses: no spectra, too many bins, a block of 0 and of 65537, n_levels 0 and 7, lo = nbin,
     # no elements, bad tilings; whiten: m = 1, skip = nbin, no spectra, bad rows
-    bad = subprocess.run([exe] + ('0 0 100 10 1 1 3 0 0  0 1 16777217 10 1 1 3 0 0  0 2 100 0 1 1 3 0 0 '
-                                  '0 2 100 65537 1 1 3 0 0  0 2 100 10 0 1 3 0 0  0 2 100 10 7 1 3 0 0 '
-                                  '0 2 100 10 1 100 3 0 0  0 2 100 10 1 1 0 0 0  0 2 100 10 1 1 3 48 0 '
-                                  '0 2 100 10 1 1 3 0 3  1 3 100 5 1 1 0 0 0  1 3 100 5 2 100 0 0 0 '
-                                  '1 0 100 5 2 1 0 0 0  1 3 100 5 2 1 3 0 0').split(), stdout=subprocess.PIPE, text=True)
+    bad = run_raw(exe, '0 0 100 10 1 1 3 0 0  0 1 16777217 10 1 1 3 0 0  0 2 100 0 1 1 3 0 0 '
+                       '0 2 100 65537 1 1 3 0 0  0 2 100 10 0 1 3 0 0  0 2 100 10 7 1 3 0 0 '
+                       '0 2 100 10 1 100 3 0 0  0 2 100 10 1 1 0 0 0  0 2 100 10 1 1 3 48 0 '
+                       '0 2 100 10 1 1 3 0 3  1 3 100 5 1 1 0 0 0  1 3 100 5 2 100 0 0 0 '
+                       '1 0 100 5 2 1 0 0 0  1 3 100 5 2 1 3 0 0')
     assert bad.returncode == 0
     errors = [json.loads(line)['error'] for line in bad.stdout.splitlines()]
     assert len(errors) == 14

@@ -4,7 +4,6 @@ decomposition driven by the very index maps the kernels use (tests/lspec_geo_che
 from csrc/lspec_geo.hpp), and the walk of those maps under the sanitizers."""
 import json
 import os
-import subprocess
 
 import numpy as np
 import pytest
@@ -14,6 +13,7 @@ from baseband_tasks_amd import hip, periodicity
 
 import lspec_cases
 from lspec_cases import RATE, T0
+from geo_check import compile_check, run_check, run_raw
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CSRC = os.path.join(ROOT, 'baseband-tasks_amd', 'csrc')
@@ -180,11 +180,7 @@ def test_library_exports_and_limits():
 # -- the index maps -------------------------------------------------------------------------------------
 @pytest.fixture(scope='module')
 def geo_check(tmp_path_factory):
-    exe = str(tmp_path_factory.mktemp('lspec') / 'lspec_geo_check')
-    subprocess.check_call(['g++', '-O2', '-g', '-std=c++17', '-fsanitize=address,undefined',
-                           '-fno-sanitize-recover=undefined', '-I', CSRC,
-                           os.path.join(ROOT, 'tests', 'lspec_geo_check.cpp'), '-o', exe])
-    return exe
+    return compile_check('lspec_geo_check', tmp_path_factory.mktemp('lspec'), opt='-O2')
 
 
 def _walk_shapes():
@@ -208,11 +204,7 @@ def test_kernel_indexing_on_the_host(geo_check):
     partner n - k, nothing addressed outside its buffer: the program reports otherwise, and the sanitizers
     abort it on a wild index or an overflow of its own."""
     shapes = _walk_shapes()
-    out = subprocess.run([geo_check, 'walk'] + [str(v) for shape in shapes for v in shape], stdout=subprocess.PIPE,
-                         stderr=subprocess.PIPE, text=True)
-    assert out.returncode == 0, out.stdout + out.stderr
-    plans = [json.loads(line) for line in out.stdout.splitlines()]
-    assert len(plans) == len(shapes)
+    plans = run_check(geo_check, shapes, word='walk')
     past = 0
     for (n, n_elem, per), g in zip(shapes, plans):
         assert g['walk'] == 0, g
@@ -228,8 +220,7 @@ def test_kernel_indexing_on_the_host(geo_check):
         past += g['max_in'] >= 1 << 31
     assert past >= len(LENGTHS)
     # what the library refuses
-    bad = subprocess.run([geo_check, 'walk'] + '16384 2 1  8388608 2 1  24576 2 1  32768 0 1  32768 2 0'.split(),
-                         stdout=subprocess.PIPE, text=True)
+    bad = run_raw(geo_check, '16384 2 1  8388608 2 1  24576 2 1  32768 0 1  32768 2 0', word='walk')
     assert bad.returncode == 0
     errors = [json.loads(line)['error'] for line in bad.stdout.splitlines()]
     assert len(errors) == 5 and all('2^15' in e for e in errors[:3]) and 'elements' in errors[3]
@@ -246,10 +237,7 @@ def test_model_of_the_decomposition(n, geo_check, tmp_path):
     the kernels: two columns as one complex stream, n1-point transforms over a, the twiddles W_n^m with
     the printed exponents, the scratch cells, n2-point transforms over b, the partner map, the untangling.
     Against rfft of each column, within the GPU tests' tolerance."""
-    out = subprocess.run([geo_check, 'maps', str(n), str(tmp_path)], stdout=subprocess.PIPE, stderr=subprocess.PIPE,
-                         text=True)
-    assert out.returncode == 0, out.stdout + out.stderr
-    info = json.loads(out.stdout)
+    info, = run_check(geo_check, [(n, str(tmp_path))], word='maps')
     n1, n2 = info['n1'], info['n2']
     assert n1 * n2 == n
     nk, nh = n2 // 2 + 1, n1 // 2

@@ -6,7 +6,6 @@ walked on the host by a stand-alone program under sanitizers, and the ledger of 
 and edges of that tiling the GPU cases of tests/psrfits_cases.py reach."""
 import json
 import os
-import subprocess
 
 import numpy as np
 import pytest
@@ -15,6 +14,7 @@ import baseband_tasks_amd as bt
 from baseband_tasks_amd import psrfits
 from baseband_tasks_amd import units as u
 import psrfits_cases as pc
+from geo_check import compile_check, run_check, run_raw
 from test_psrfits_host import WIDTHS, walk
 
 F32 = np.float32
@@ -348,18 +348,13 @@ GEO_SHAPES += [shape for _, shape in pc.search_runs() if shape not in GEO_SHAPES
 
 @pytest.fixture(scope='module')
 def geo_check(tmp_path_factory):
-    return pc.compile_check('psrsearch_geo_check', tmp_path_factory.mktemp('psrsearch_geo'))
+    return compile_check('psrsearch_geo_check', tmp_path_factory.mktemp('psrsearch_geo'))
 
 
 def test_kernel_tiling_on_the_host(geo_check):
     """Every LDS index inside the tile, every column and every stored byte owned once: the
     program exits non-zero otherwise, and the sanitizers abort it on a wild index of its own."""
-    exe = geo_check
-    args = [str(v) for shape in GEO_SHAPES for v in shape]
-    out = subprocess.run([exe] + args, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True)
-    assert out.returncode == 0, out.stdout + out.stderr
-    plans = [json.loads(line) for line in out.stdout.splitlines()]
-    assert len(plans) == len(GEO_SHAPES)
+    plans = run_check(geo_check, GEO_SHAPES)
     for (nsblk, nchan, npol, nbits, aligned), g in zip(GEO_SHAPES, plans):
         assert g['walk'] == 0, (nsblk, nchan, npol, nbits, g)
         assert g['ct'] * npol <= 256 and g['ts'] * npol * g['pol_pitch'] <= 8192
@@ -368,8 +363,7 @@ def test_kernel_tiling_on_the_host(geo_check):
         assert g['unit'] == (32 if g['vec'] else 8) // nbits
     assert plans[10] == {'ct': 64, 'unit': 4, 'vec': 1, 'ny': 1, 'pol_pitch': 72, 'ts': 28, 'n_tile': 16, 'walk': 0}
     # what the library refuses
-    bad = subprocess.run([exe, '8', '16', '4', '3', '1', '8', '4', '2', '1', '1', '8', '8', '33', '8', '1'],
-                         stdout=subprocess.PIPE, text=True)
+    bad = run_raw(geo_check, '8 16 4 3 1  8 4 2 1 1  8 8 33 8 1')
     assert bad.returncode == 0
     errors = [json.loads(line)['error'] for line in bad.stdout.splitlines()]
     assert 'nbits' in errors[0] and 'multiple of 8' in errors[1] and 'polarizations' in errors[2]
@@ -381,7 +375,7 @@ def geo(geo_check):
     """(nsblk, nchan, npol, nbits, aligned) -> the launcher's geometry, for every GPU run and its
     aligned twin."""
     shapes = sorted({s[:4] + (a,) for _, s in pc.search_runs() for a in (s[4], 1)})
-    plans = dict(zip(shapes, pc.run_check(geo_check, shapes)))
+    plans = dict(zip(shapes, run_check(geo_check, shapes)))
     assert all(g['walk'] == 0 for g in plans.values())
     return plans.__getitem__
 

@@ -6,7 +6,6 @@ digit descent of the kernels walked by a sanitized host program.  No GPU."""
 import json
 import math
 import os
-import subprocess
 
 import numpy as np
 import pytest
@@ -16,6 +15,7 @@ from baseband_tasks_amd import hip, periodicity, search
 
 import rank_cases
 from rank_cases import RATE, T0, same_bits
+from geo_check import compile_check, run_check, run_raw
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CSRC = os.path.join(ROOT, 'baseband-tasks_amd', 'csrc')
@@ -411,16 +411,9 @@ def test_kernel_tiling_and_descent_on_the_host(tmp_path):
     blocks (65536 equal values among them), and for every shape every (block, element tile) owned once,
     every row inside its spectrum, the skip rows zeroed once, the LDS within the budget: the program
     exits non-zero otherwise, and the sanitizers abort it on a wild index or an overflow of its own."""
-    exe = str(tmp_path / 'rank_geo_check')
-    subprocess.check_call(['g++', '-O1', '-g', '-std=c++17', '-fsanitize=address,undefined',
-                           '-fno-sanitize-recover=undefined', '-I', CSRC,
-                           os.path.join(ROOT, 'tests', 'rank_geo_check.cpp'), '-o', exe])
+    exe = compile_check('rank_geo_check', tmp_path)
     shapes = _geo_shapes()
-    out = subprocess.run([exe] + [str(v) for shape in shapes for v in shape], stdout=subprocess.PIPE,
-                         stderr=subprocess.PIPE, text=True)
-    assert out.returncode == 0, out.stdout + out.stderr
-    plans = [json.loads(line) for line in out.stdout.splitlines()]
-    assert len(plans) == len(shapes)
+    plans = run_check(exe, shapes)
     seen_routes = set()
     for shape, g in zip(shapes, plans):
         n_spec, nbin, e, m, skip, width, digit, route = shape
@@ -442,10 +435,9 @@ def test_kernel_tiling_and_descent_on_the_host(tmp_path):
     assert len(seen_routes) == 12                                  # both routes, both digits, every width
     # what the library refuses: a block of 1 and of 65537, no rows, no elements, a skip of nbin, 2^40 rows and
     # one, too many tiles, and bad tilings
-    bad = subprocess.run([exe] + ('1 100 3 1 0 0 0 0  1 100 3 65537 0 0 0 0  0 100 3 4 0 0 0 0  1 100 0 4 0 0 0 0 '
-                                  '1 100 3 4 100 0 0 0  1 1099511627777 3 4 0 0 0 0  1 1099511627776 3 2 0 0 0 0 '
-                                  '1 100 3 4 0 48 0 0  1 100 3 4 0 0 5 0  1 100 3 4 0 0 0 3').split(),
-                         stdout=subprocess.PIPE, text=True)
+    bad = run_raw(exe, '1 100 3 1 0 0 0 0  1 100 3 65537 0 0 0 0  0 100 3 4 0 0 0 0  1 100 0 4 0 0 0 0 '
+                       '1 100 3 4 100 0 0 0  1 1099511627777 3 4 0 0 0 0  1 1099511627776 3 2 0 0 0 0 '
+                       '1 100 3 4 0 48 0 0  1 100 3 4 0 0 5 0  1 100 3 4 0 0 0 3')
     assert bad.returncode == 0
     errors = [json.loads(line)['error'] for line in bad.stdout.splitlines()]
     assert len(errors) == 10

@@ -5,7 +5,6 @@ exports, and the tiling and the two selection methods of the kernels walked by a
 No GPU."""
 import json
 import os
-import subprocess
 
 import numpy as np
 import pytest
@@ -15,6 +14,7 @@ from baseband_tasks_amd import device_task, hip, search
 
 import rmed_cases
 from rmed_cases import RATE, T0, same_bits
+from geo_check import compile_check, run_check, run_raw
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CSRC = os.path.join(ROOT, 'baseband-tasks_amd', 'csrc')
@@ -437,16 +437,9 @@ def test_kernel_tiling_and_selection_on_the_host(tmp_path):
     every median owned once, every staged row inside the stream and the input, every window inside the
     staged rows, the LDS within the budget, the input span per call as stated: the program exits non-zero
     otherwise, and the sanitizers abort it on a wild index or an overflow of its own."""
-    exe = str(tmp_path / 'rmed_geo_check')
-    subprocess.check_call(['g++', '-O1', '-g', '-std=c++17', '-fsanitize=address,undefined',
-                           '-fno-sanitize-recover=undefined', '-I', CSRC,
-                           os.path.join(ROOT, 'tests', 'rmed_geo_check.cpp'), '-o', exe])
+    exe = compile_check('rmed_geo_check', tmp_path)
     shapes = rmed_cases.geo_shapes()
-    out = subprocess.run([exe] + [str(v) for shape in shapes for v in shape], stdout=subprocess.PIPE,
-                         stderr=subprocess.PIPE, text=True)
-    assert out.returncode == 0, out.stdout + out.stderr
-    plans = [json.loads(line) for line in out.stdout.splitlines()]
-    assert len(plans) == len(shapes)
+    plans = run_check(exe, shapes)
     seen = set()
     for shape, g in zip(shapes, plans):
         w, s, e, n, tile, rows, method, chunk = shape
@@ -460,8 +453,8 @@ def test_kernel_tiling_and_selection_on_the_host(tmp_path):
         assert g['lds_bytes'] == (g['run'] + w - 1) * g['nx'] * 4 <= hip.RANK_LDS_BYTES
         seen.add((g['method'], g['nx']))
     assert len(seen) == 6                                            # both methods, every tile width
-    bad = subprocess.run([exe] + ('4 1 1 10 0 0 0 0  1025 1 1 10 0 0 0 0  3 0 1 10 0 0 0 0  3 4097 1 10 0 0 0 0  3 1 0 10 0 0 0 0 '
-                                  '3 4 1 3 0 0 0 0  3 1 1 10 48 0 0 0  3 1 1 10 0 0 3 0').split(), stdout=subprocess.PIPE, text=True)
+    bad = run_raw(exe, '4 1 1 10 0 0 0 0  1025 1 1 10 0 0 0 0  3 0 1 10 0 0 0 0  3 4097 1 10 0 0 0 0  3 1 0 10 0 0 0 0 '
+                       '3 4 1 3 0 0 0 0  3 1 1 10 48 0 0 0  3 1 1 10 0 0 3 0')
     assert bad.returncode == 0
     errors = [json.loads(line)['error'] for line in bad.stdout.splitlines()]
     assert len(errors) == 8

@@ -4,8 +4,6 @@ framing and repr, the argument checks of the wrappers and the two C entry points
 tiling (csrc/sk_geo.hpp) walked on the host by a stand-alone program under sanitizers, and a guard
 on the shared cases of sk_cases.py."""
 import json
-import os
-import subprocess
 
 import numpy as np
 import pytest
@@ -15,9 +13,8 @@ from baseband_tasks_amd import hip, rfi
 
 import sk_cases
 from sk_cases import CASES, IDS
+from geo_check import compile_check, run_check, run_raw
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CSRC = os.path.join(ROOT, 'baseband-tasks_amd', 'csrc')
 T0 = bt.Time('2010-11-12T13:14:15')
 RATE = 1e4
 
@@ -322,16 +319,9 @@ def test_kernel_tiling_on_the_host(tmp_path):
     """Every access read once and stored once, every LDS index inside its array, every sk and flag
     written once, segments added in order: the program exits non-zero otherwise, and the
     sanitizers abort it on a wild index of its own."""
-    exe = str(tmp_path / 'sk_geo_check')
-    subprocess.check_call(['g++', '-O1', '-g', '-std=c++17', '-fsanitize=address,undefined',
-                           '-fno-sanitize-recover=undefined', '-I', CSRC,
-                           os.path.join(ROOT, 'tests', 'sk_geo_check.cpp'), '-o', exe])
+    exe = compile_check('sk_geo_check', tmp_path)
     shapes = _geo_shapes()
-    out = subprocess.run([exe] + [str(v) for shape in shapes for v in shape], stdout=subprocess.PIPE,
-                         stderr=subprocess.PIPE, text=True)
-    assert out.returncode == 0, out.stdout + out.stderr
-    plans = [json.loads(line) for line in out.stdout.splitlines()]
-    assert len(plans) == len(shapes)
+    plans = run_check(exe, shapes)
     for (n_block, n, n_elem, cplx, group, aligned, slab), g in zip(shapes, plans):
         assert g['walk'] == 0, (n_block, n, n_elem, cplx, group, aligned, slab, g)
         wide = 2 if cplx else 4
@@ -353,8 +343,7 @@ def test_kernel_tiling_on_the_host(tmp_path):
     at = shapes.index((16, 4096, 2048, 1, 1, 1, 0))
     assert plans[at]['w'] == 32 and plans[at]['ny'] == 16 and plans[at]['n_tile'] * plans[at]['n_zgroup'] == 1024
     # what the library refuses
-    bad = subprocess.run([exe] + '1 1 4 1 1 1 0  1 16 4 1 3 1 0  1 16 130 0 65 1 0  0 16 4 1 1 1 0'.split(),
-                         stdout=subprocess.PIPE, text=True)
+    bad = run_raw(exe, '1 1 4 1 1 1 0  1 16 4 1 3 1 0  1 16 130 0 65 1 0  0 16 4 1 1 1 0')
     assert bad.returncode == 0
     errors = [json.loads(line)['error'] for line in bad.stdout.splitlines()]
     assert '65536' in errors[0] and 'divide' in errors[1] and '64' in errors[2] and 'empty' in errors[3]

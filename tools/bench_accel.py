@@ -22,14 +22,13 @@ first series of a process ran up to 12 % slower than the same route measured lat
       and =2 (global memory only); `auto_ms` under the automatic rule.
   `copy_ms`: a device-to-device copy of the output's bytes; `*_over_copy` the ratios.  A gather that writes
       each byte once has nothing else to be held against."""
-import argparse
-import json
 import os
-import subprocess
 import sys
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
+import bench_rows
+from bench_rows import events_ms, reread
+
+sys.path.insert(0, bench_rows.ROOT)
 
 ROWS = {
     'n20x8_a64': dict(length=1 << 20, ndm=8, n_acc=64),
@@ -41,21 +40,6 @@ ROW_LIMIT = 400          # seconds a row may take
 RATE = 1e3
 REACH = 1e-3             # |k| n at the outermost trials
 BURN_IN = 4              # rounds over all routes and the copy before the timed ones
-
-
-def events_ms(step, warm, reps):
-    from baseband_tasks_amd import hip
-    for _ in range(warm):
-        step()
-    hip.synchronize()
-    times = []
-    for _ in range(reps):
-        a = hip.Event().record()
-        step()
-        b = hip.Event().record()
-        b.synchronize()
-        times.append(a.elapsed_ms(b))
-    return times
 
 
 def run_row(name, reps):
@@ -108,17 +92,12 @@ def run_row(name, reps):
     src, dst = hip.DeviceArray((values,), np.float32), hip.DeviceArray((values,), np.float32)
     hip.check(hip.lib().bbt_memset(src.ptr, 0, src.nbytes, None))
 
-    def read():
-        acc.invalidate_cache()
-        acc.seek(0)
-        acc.read_device()
-
     turns = (('auto', '0'), ('window', '1'), ('direct', '2'), ('copy', '0'))
     times = {key: [] for key, _ in turns}
     for r in range(BURN_IN + reps):
         for key, route in turns:
             os.environ['BBT_ACCEL_ROUTE'] = route
-            step = (lambda: dst.copy_from_device(src)) if key == 'copy' else read
+            step = (lambda: dst.copy_from_device(src)) if key == 'copy' else (lambda: reread(acc))
             t = events_ms(step, 2 if r == 0 else 0, 1)
             if r >= BURN_IN:
                 times[key] += t
@@ -133,37 +112,5 @@ def run_row(name, reps):
     return line
 
 
-def main():
-    ap = argparse.ArgumentParser(description=__doc__.split('\n')[0])
-    ap.add_argument('--out', default=os.path.join(ROOT, 'profiles', 'accel_bench.jsonl'))
-    ap.add_argument('--reps', type=int, default=7)
-    ap.add_argument('--child', action='store_true', help=argparse.SUPPRESS)
-    ap.add_argument('rows', nargs='*', default=list(ROWS))
-    args = ap.parse_args()
-    if args.child:
-        print(json.dumps(run_row(args.rows[0], args.reps)), flush=True)
-        return 0
-    os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
-    with open(args.out, 'a') as out:
-        for name in args.rows:
-            if name not in ROWS:
-                ap.error(f'unknown row {name}; one of {", ".join(ROWS)}')
-            try:
-                done = subprocess.run([sys.executable, os.path.abspath(__file__), '--child', '--reps', str(args.reps), name],
-                                      stdout=subprocess.PIPE, text=True, timeout=ROW_LIMIT)
-            except subprocess.TimeoutExpired:
-                print(f'{name}: no result within {ROW_LIMIT} s; stopping', file=sys.stderr)
-                return 1
-            if done.returncode != 0:
-                print(f'{name}: exit status {done.returncode}; stopping', file=sys.stderr)
-                return 1
-            line = done.stdout.strip().splitlines()[-1]
-            json.loads(line)
-            print(line, flush=True)
-            out.write(line + '\n')
-            out.flush()
-    return 0
-
-
 if __name__ == '__main__':
-    sys.exit(main())
+    sys.exit(bench_rows.main(__file__, __doc__, ROWS, run_row, ROW_LIMIT, 'accel_bench.jsonl'))

@@ -21,15 +21,15 @@ repeat): 2 warm-up reads, then ``--reps`` timed ones; the minimum and the median
 
 The split between the fold passes and the S/N pass is not taken here: `bash tools/gpu_job.sh ffa` runs one row
 under a kernel trace and tools/rocprof_db.py sums the kernels."""
-import argparse
 import json
 import os
-import subprocess
 import sys
 import time
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
+import bench_rows
+from bench_rows import events_ms, reread
+
+sys.path.insert(0, bench_rows.ROOT)
 
 PERIODS, K = (256, 512), 6
 SHAPES = {'n18_d512': dict(n=1 << 18, ndm=512), 'n20_d64': dict(n=1 << 20, ndm=64)}
@@ -79,21 +79,6 @@ def cpu_seconds(n, ndm):
         return time.perf_counter() - t0
 
 
-def events_ms(step, warm, reps):
-    from baseband_tasks_amd import hip
-    for _ in range(warm):
-        step()
-    hip.synchronize()
-    times = []
-    for _ in range(reps):
-        a = hip.Event().record()
-        step()
-        b = hip.Event().record()
-        b.synchronize()
-        times.append(a.elapsed_ms(b))
-    return times
-
-
 def run_row(name, reps):
     import numpy as np
     import baseband_tasks_amd as bt
@@ -110,12 +95,7 @@ def run_row(name, reps):
     fs = bt.FFASearch(stream, n, PERIODS, K)
     fs.ffa_budget = BUDGET
     line['launches'] = len(fs._chunks())
-
-    def read():
-        fs.invalidate_cache()
-        fs.seek(0)
-        fs.read_device()
-    times = events_ms(read, 2, reps)
+    times = events_ms(lambda: reread(fs), 2, reps)
     line['ffa_ms_min'], line['ffa_ms_med'] = round(min(times), 3), round(float(np.median(times)), 3)
     line['gadds_per_s'] = round(line['adds'] / min(times) / 1e6, 1)
     line['scratch_bytes'] = fs._plan.info()['scratch_bytes']
@@ -131,13 +111,9 @@ def run_row(name, reps):
 
 
 def main():
-    ap = argparse.ArgumentParser(description=__doc__.split('\n')[0])
-    ap.add_argument('--out', default=os.path.join(ROOT, 'profiles', 'ffa_bench.jsonl'))
-    ap.add_argument('--reps', type=int, default=7)
+    ap = bench_rows.parser(__doc__, 'ffa_bench.jsonl', [])
     ap.add_argument('--turns', type=int, default=2, help='how often the fuse rows of a shape take turns')
     ap.add_argument('--no-cpu', action='store_true', help='skip the NumPy twin on the CPU')
-    ap.add_argument('--child', action='store_true', help=argparse.SUPPRESS)
-    ap.add_argument('rows', nargs='*')
     args = ap.parse_args()
     if args.child:
         print(json.dumps(run_row(args.rows[0], args.reps)), flush=True)
@@ -146,9 +122,7 @@ def main():
     if not rows:
         for shape in SHAPES:
             rows += [shape] + [f'{shape}_fuse{f}' for _ in range(args.turns) for f in (1, 2, 3)]
-    for name in rows:
-        if name not in ROWS:
-            ap.error(f'unknown row {name}; one of {", ".join(ROWS)}')
+    bench_rows.check_rows(ap, rows, ROWS)
     cpu = {}
     if not args.no_cpu:
         for name in rows:
@@ -158,27 +132,14 @@ def main():
                 cpu[name] = dict(cpu_s=round(seconds, 2), cpu_columns=CPU_COLUMNS, cpu_workers=CPU_WORKERS,
                                  cpu_plane_s=round(seconds * ndm / CPU_COLUMNS, 1))
                 print(f'{name}: twin on {CPU_COLUMNS} columns: {seconds:.2f} s', file=sys.stderr, flush=True)
-    os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
-    with open(args.out, 'a') as out:
-        for name in rows:
-            try:
-                done = subprocess.run([sys.executable, os.path.abspath(__file__), '--child', '--reps', str(args.reps), name],
-                                      stdout=subprocess.PIPE, text=True, timeout=ROW_LIMIT)
-            except subprocess.TimeoutExpired:
-                print(f'{name}: no result within {ROW_LIMIT} s; stopping', file=sys.stderr)
-                return 1
-            if done.returncode != 0:
-                print(f'{name}: exit status {done.returncode}; stopping', file=sys.stderr)
-                return 1
-            line = json.loads(done.stdout.strip().splitlines()[-1])
-            if name in cpu:
-                line.update(cpu[name])
-                line['cpu_plane_over_ffa'] = round(line['cpu_plane_s'] * 1e3 / line['ffa_ms_min'], 1)
-            line = json.dumps(line)
-            print(line, flush=True)
-            out.write(line + '\n')
-            out.flush()
-    return 0
+
+    def with_twin(name, line):
+        if name in cpu:
+            line.update(cpu[name])
+            line['cpu_plane_over_ffa'] = round(line['cpu_plane_s'] * 1e3 / line['ffa_ms_min'], 1)
+        return line
+
+    return bench_rows.run_rows(__file__, rows, args.reps, ROW_LIMIT, args.out, edit=with_twin)
 
 
 if __name__ == '__main__':

@@ -19,7 +19,7 @@ import numpy as np
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from baseband_tasks_amd import hip                                  # noqa: E402
 from baseband_tasks_amd.shaping import index_map                    # noqa: E402
-from bench_real2complex import timed                                # noqa: E402
+from bench_rows import copy_rate, timed                             # noqa: E402
 
 CF = 8          # complex64
 
@@ -35,14 +35,6 @@ CASES = [
     ('transpose_(1024,2)_direct', [(1024, 2)], CF, lambda d: d.transpose(0, 2, 1), False, 'direct'),
     ('stack2_last_direct', [()] * 2, CF, lambda d: np.stack(d, -1), True, 'direct'),
 ]
-
-
-def copy_rate(nbytes, reps):
-    a = hip.DeviceArray((nbytes,), np.uint8)
-    b = hip.DeviceArray((nbytes,), np.uint8)
-    a.fill_bytes(1)
-    t = timed(lambda: b.copy_from_device(a), reps)
-    return 2 * nbytes / t
 
 
 def case(name, shapes, eb, task, combine, route, mib, reps, copy):

@@ -19,14 +19,13 @@ every repeat): 2 warm-up reads, then ``--reps`` timed ones; the minimum and the 
 rows repeat the 5-level search under other tilings (BBT_HSUM_WIDTH elements per workgroup,
 BBT_HSUM_SPLIT threads per spectrum, block and element), and the `rows_*` rows `Whiten` under
 BBT_HSUM_ROWS."""
-import argparse
-import json
 import os
-import subprocess
 import sys
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
+import bench_rows
+from bench_rows import events_ms, reread
+
+sys.path.insert(0, bench_rows.ROOT)
 
 ROWS = {
     'stack': dict(spectra=True),
@@ -44,21 +43,6 @@ N_SPEC, N_FFT, NDM = 64, 16384, 512
 NBIN = N_FFT // 2 + 1
 BLOCK, WHITEN_BLOCK = 64, 128
 LEVELS = (1, 3, 5, 6)
-
-
-def events_ms(step, warm, reps):
-    from baseband_tasks_amd import hip
-    for _ in range(warm):
-        step()
-    hip.synchronize()
-    times = []
-    for _ in range(reps):
-        a = hip.Event().record()
-        step()
-        b = hip.Event().record()
-        b.synchronize()
-        times.append(a.elapsed_ms(b))
-    return times
 
 
 def run_row(name, reps):
@@ -80,11 +64,7 @@ def run_row(name, reps):
                 split=info['split'], rows=info['rows'])
 
     def timed(task):
-        def read():
-            task.invalidate_cache()
-            task.seek(0)
-            task.read_device()
-        times = events_ms(read, 2, reps)
+        times = events_ms(lambda: reread(task), 2, reps)
         return round(min(times), 3), round(float(np.median(times)), 3)
 
     wh = bt.Whiten(stack, WHITEN_BLOCK)
@@ -122,37 +102,5 @@ def run_row(name, reps):
     return line
 
 
-def main():
-    ap = argparse.ArgumentParser(description=__doc__.split('\n')[0])
-    ap.add_argument('--out', default=os.path.join(ROOT, 'profiles', 'hsum_bench.jsonl'))
-    ap.add_argument('--reps', type=int, default=7)
-    ap.add_argument('--child', action='store_true', help=argparse.SUPPRESS)
-    ap.add_argument('rows', nargs='*', default=list(ROWS))
-    args = ap.parse_args()
-    if args.child:
-        print(json.dumps(run_row(args.rows[0], args.reps)), flush=True)
-        return 0
-    os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
-    with open(args.out, 'a') as out:
-        for name in args.rows:
-            if name not in ROWS:
-                ap.error(f'unknown row {name}; one of {", ".join(ROWS)}')
-            try:
-                done = subprocess.run([sys.executable, os.path.abspath(__file__), '--child', '--reps', str(args.reps), name],
-                                      stdout=subprocess.PIPE, text=True, timeout=ROW_LIMIT)
-            except subprocess.TimeoutExpired:
-                print(f'{name}: no result within {ROW_LIMIT} s; stopping', file=sys.stderr)
-                return 1
-            if done.returncode != 0:
-                print(f'{name}: exit status {done.returncode}; stopping', file=sys.stderr)
-                return 1
-            line = done.stdout.strip().splitlines()[-1]
-            json.loads(line)
-            print(line, flush=True)
-            out.write(line + '\n')
-            out.flush()
-    return 0
-
-
 if __name__ == '__main__':
-    sys.exit(main())
+    sys.exit(bench_rows.main(__file__, __doc__, ROWS, run_row, ROW_LIMIT, 'hsum_bench.jsonl'))

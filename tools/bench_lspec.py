@@ -23,14 +23,13 @@ without the yardsticks.
 
 `bytes_model` is 14 bytes per input value (4 read, 4 + 4 through the scratch, 2 written) and
 `fraction_of_copy_rate` that traffic's rate over the copy's (which moves 8 bytes per value)."""
-import argparse
-import json
 import os
-import subprocess
 import sys
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
+import bench_rows
+from bench_rows import events_ms, reread
+
+sys.path.insert(0, bench_rows.ROOT)
 
 ROWS = {
     'n20': dict(length=1 << 20, ndm=512, n=1 << 20, stack=1),
@@ -47,21 +46,6 @@ ROWS = {
 ROW_LIMIT = 400          # seconds a row may take
 RATE = 1e3
 SHORT = 16384
-
-
-def events_ms(step, warm, reps):
-    from baseband_tasks_amd import hip
-    for _ in range(warm):
-        step()
-    hip.synchronize()
-    times = []
-    for _ in range(reps):
-        a = hip.Event().record()
-        step()
-        b = hip.Event().record()
-        b.synchronize()
-        times.append(a.elapsed_ms(b))
-    return times
 
 
 def run_row(name, reps):
@@ -83,11 +67,7 @@ def run_row(name, reps):
                 plane_bytes=values * 4, bytes_model=values * 14)
 
     def timed(task):
-        def read():
-            task.invalidate_cache()
-            task.seek(0)
-            task.read_device()
-        times = events_ms(read, 2, reps)
+        times = events_ms(lambda: reread(task), 2, reps)
         return round(min(times), 3), round(float(np.median(times)), 3)
 
     sp = bt.LongSpectra(plane, n, stack)
@@ -115,37 +95,5 @@ def run_row(name, reps):
     return line
 
 
-def main():
-    ap = argparse.ArgumentParser(description=__doc__.split('\n')[0])
-    ap.add_argument('--out', default=os.path.join(ROOT, 'profiles', 'lspec_bench.jsonl'))
-    ap.add_argument('--reps', type=int, default=7)
-    ap.add_argument('--child', action='store_true', help=argparse.SUPPRESS)
-    ap.add_argument('rows', nargs='*', default=list(ROWS))
-    args = ap.parse_args()
-    if args.child:
-        print(json.dumps(run_row(args.rows[0], args.reps)), flush=True)
-        return 0
-    os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
-    with open(args.out, 'a') as out:
-        for name in args.rows:
-            if name not in ROWS:
-                ap.error(f'unknown row {name}; one of {", ".join(ROWS)}')
-            try:
-                done = subprocess.run([sys.executable, os.path.abspath(__file__), '--child', '--reps', str(args.reps), name],
-                                      stdout=subprocess.PIPE, text=True, timeout=ROW_LIMIT)
-            except subprocess.TimeoutExpired:
-                print(f'{name}: no result within {ROW_LIMIT} s; stopping', file=sys.stderr)
-                return 1
-            if done.returncode != 0:
-                print(f'{name}: exit status {done.returncode}; stopping', file=sys.stderr)
-                return 1
-            line = done.stdout.strip().splitlines()[-1]
-            json.loads(line)
-            print(line, flush=True)
-            out.write(line + '\n')
-            out.flush()
-    return 0
-
-
 if __name__ == '__main__':
-    sys.exit(main())
+    sys.exit(bench_rows.main(__file__, __doc__, ROWS, run_row, ROW_LIMIT, 'lspec_bench.jsonl'))

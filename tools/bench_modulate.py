@@ -28,8 +28,7 @@ sys.path.insert(0, ROOT)
 import baseband_tasks_amd as bt                                     # noqa: E402
 from baseband_tasks_amd import hip                                  # noqa: E402
 from baseband_tasks_amd.fold_table import plan_pieces               # noqa: E402
-from bench_real2complex import timed                                # noqa: E402
-from bench_gather import copy_rate                                  # noqa: E402
+from bench_rows import copy_rate, timed                             # noqa: E402
 
 POLYCO = os.path.join(ROOT, 'tests', 'golden', 'B1937_polyco.dat')
 T0 = bt.Time('2018-05-06T22:20:00')

@@ -29,8 +29,7 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import baseband_tasks_amd as bt                                     # noqa: E402
 from baseband_tasks_amd import hip, psrfits                         # noqa: E402
 from baseband_tasks_amd import units as u                           # noqa: E402
-from bench_real2complex import timed                                # noqa: E402
-from bench_gather import copy_rate                                  # noqa: E402
+from bench_rows import copy_rate, timed                             # noqa: E402
 
 
 def kernels(rows, dims, reps, copy):

@@ -15,14 +15,13 @@ automatic route, on the other route where both can run (BBT_RANK_ROUTE is read a
 the global route with 64-wide tiles -- two warm-up turns, then ``--reps`` timed ones; the minimum of
 each is reported, with its ratio to the mean-based task (`*_over_plain`) and to the copy
 (`*_over_copy`).  `route`, `digit` and `width` say what the automatic rule took."""
-import argparse
-import json
 import os
-import subprocess
 import sys
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
+import bench_rows
+from bench_rows import reread, take_turns
+
+sys.path.insert(0, bench_rows.ROOT)
 
 ROWS = {
     'std_256': dict(kind='std', shape=(1 << 16, 512), block=256),
@@ -68,25 +67,14 @@ def run_row(name, reps):
             for key in ('BBT_RANK_ROUTE', 'BBT_RANK_WIDTH'):
                 os.environ.pop(key, None)
             os.environ.update(env)
-            task.invalidate_cache()
-            task.seek(0)
-            task.read_device()
+            reread(task)
         return step
 
     candidates = {'copy': lambda: dst.copy_from_device(src), 'plain': read(plain, {}), 'auto': read(robust, {})}
     if info['route'] == 'lds':
         candidates['global'] = read(robust, dict(BBT_RANK_ROUTE='global'))
     candidates['global_w64'] = read(robust, dict(BBT_RANK_ROUTE='global', BBT_RANK_WIDTH='64'))
-    times = {key: [] for key in candidates}
-    for turn in range(WARM + reps):
-        for key, step in candidates.items():
-            hip.synchronize()
-            a = hip.Event().record()
-            step()
-            b = hip.Event().record()
-            b.synchronize()
-            if turn >= WARM:
-                times[key].append(a.elapsed_ms(b))
+    times = take_turns(candidates, WARM, reps)
     line = dict(row=name, device=hip.device_name(), shape=list(shape), block=block, reps=reps, bytes=words * 4,
                 route=info['route'], digit=info['digit'], width=info['width'], lds_bytes=info['lds_bytes'])
     for key, values in times.items():
@@ -100,37 +88,5 @@ def run_row(name, reps):
     return line
 
 
-def main():
-    ap = argparse.ArgumentParser(description=__doc__.split('\n')[0])
-    ap.add_argument('--out', default=os.path.join(ROOT, 'profiles', 'rank_bench.jsonl'))
-    ap.add_argument('--reps', type=int, default=7)
-    ap.add_argument('--child', action='store_true', help=argparse.SUPPRESS)
-    ap.add_argument('rows', nargs='*', default=list(ROWS))
-    args = ap.parse_args()
-    if args.child:
-        print(json.dumps(run_row(args.rows[0], args.reps)), flush=True)
-        return 0
-    os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
-    with open(args.out, 'a') as out:
-        for name in args.rows:
-            if name not in ROWS:
-                ap.error(f'unknown row {name}; one of {", ".join(ROWS)}')
-            try:
-                done = subprocess.run([sys.executable, os.path.abspath(__file__), '--child', '--reps', str(args.reps), name],
-                                      stdout=subprocess.PIPE, text=True, timeout=ROW_LIMIT)
-            except subprocess.TimeoutExpired:
-                print(f'{name}: no result within {ROW_LIMIT} s; stopping', file=sys.stderr)
-                return 1
-            if done.returncode != 0:
-                print(f'{name}: exit status {done.returncode}; stopping', file=sys.stderr)
-                return 1
-            line = done.stdout.strip().splitlines()[-1]
-            json.loads(line)
-            print(line, flush=True)
-            out.write(line + '\n')
-            out.flush()
-    return 0
-
-
 if __name__ == '__main__':
-    sys.exit(main())
+    sys.exit(bench_rows.main(__file__, __doc__, ROWS, run_row, ROW_LIMIT, 'rank_bench.jsonl'))

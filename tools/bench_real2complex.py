@@ -10,7 +10,6 @@ the same bytes: the overlap-save plan with n_fft = M on S complex64 streams (max
 per frame (hop M, nothing dropped: the same transforms per pair), and Channelize(M) where it runs.
 """
 import argparse
-import ctypes as C
 import json
 import os
 import sys
@@ -19,29 +18,9 @@ import numpy as np
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from baseband_tasks_amd import hip          # noqa: E402
+from bench_rows import timed                # noqa: E402
 
 HBM = 8e12
-
-
-def timed(fn, reps):
-    """Device time per call (s) of ``fn()`` on the package's stream, after one warm-up call."""
-    lib = hip.lib()
-    fn()
-    hip.synchronize()
-    e0, e1 = C.c_void_p(), C.c_void_p()
-    hip.check(lib.bbt_event_create(C.byref(e0)))
-    hip.check(lib.bbt_event_create(C.byref(e1)))
-    st = hip._stream
-    hip.check(lib.bbt_event_record(e0, st))
-    for _ in range(reps):
-        fn()
-    hip.check(lib.bbt_event_record(e1, st))
-    hip.check(lib.bbt_event_sync(e1))
-    ms = C.c_float()
-    hip.check(lib.bbt_event_elapsed_ms(e0, e1, C.byref(ms)))
-    lib.bbt_event_destroy(e0)
-    lib.bbt_event_destroy(e1)
-    return ms.value / 1e3 / reps
 
 
 def case(m, s, mib, reps):

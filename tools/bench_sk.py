@@ -27,8 +27,7 @@ import numpy as np
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 from baseband_tasks_amd import hip                                  # noqa: E402
-from bench_real2complex import timed                                # noqa: E402
-from bench_gather import copy_rate                                  # noqa: E402
+from bench_rows import copy_rate, timed                             # noqa: E402
 
 LIMITS = (-0.5, 0.5)
 
