@@ -25,6 +25,7 @@
 #include "gen2_host.hpp"
 #include "gen_host.hpp"
 #include "osm_geo.hpp"
+#include "osm_launch.hpp"
 #include "chan_geo.hpp"
 #include "pfb_geo.hpp"
 #include "tune.hpp"
@@ -751,6 +752,9 @@ struct bbt_osm_plan {
     float2* seam = nullptr;     // [blocks][2][npair][n_chan] float4 (the turn in use)
     float2* seam_buf[2] = {nullptr, nullptr};
     size_t seam_bytes[2] = {0, 0};
+    // the launches of the chunk being run (osm_launch.hpp; reused: no allocation in steady state)
+    OsmKnobs knobs;
+    std::vector<OsmLaunch> chunk_launches;
 
     // timing
     bool timing = false;
@@ -764,96 +768,6 @@ struct bbt_osm_plan {
     double acc_ms[3] = {0, 0, 0};
     int64_t launches = 0;
 };
-
-template <int N2, int NCH>
-static void launch_rowpass_t(bbt_osm_plan* p, float2* work, const OsmChunk& ch, hipStream_t st,
-                             int y0 = 0, int ny = -1) {
-    // two-level plans: a flat grid, the workgroups that share a response row on one XCD (k_osm_rowpass)
-    const bool flat = p->outer == 1 && ch.nblk * p->npair > 1 &&
-                      (long long)p->n1 * ch.nblk * p->npair < (1ll << 31);
-    // (three-level plans may launch a range [y0, y0 + ny) of the outer rows)
-    const int rows = ny >= 0 ? ny : ch.nblk * p->npair * p->outer;
-    hipLaunchKernelGGL((k_osm_rowpass<N2, NCH>),
-                       flat ? dim3(p->n1 * ch.nblk * p->npair, 1) : dim3(p->n1, rows),
-                       dim3(N2 / 16), 0,
-                       st, work, p->n1, p->resp, p->resp_index, p->npair, p->tab2.tw0, p->tab2.tw1,
-                       p->wroot, ch, p->outer, y0, p->tw4row, p->tw4base,
-                       p->tw_col ? (NCH ? 1 : 3) : 0, p->tw4o, p->tw4u);
-}
-
-// (row length, channels) -> instantiation; nch == 0 is the plain row pass.
-static int launch_rowpass(bbt_osm_plan* p, float2* work, const OsmChunk& ch, int nch,
-                          hipStream_t st, int y0 = 0, int ny = -1) {
-#define BBT_RP(N2_, NCH_)                                       \
-    if (p->n2 == N2_ && nch == NCH_) {                          \
-        launch_rowpass_t<N2_, NCH_>(p, work, ch, st, y0, ny);   \
-        return 0;                                               \
-    }
-    BBT_RP(256, 0) BBT_RP(512, 0) BBT_RP(1024, 0) BBT_RP(2048, 0) BBT_RP(4096, 0)
-    BBT_RP(256, 2) BBT_RP(256, 4) BBT_RP(256, 8) BBT_RP(512, 2) BBT_RP(512, 4) BBT_RP(512, 8)
-    BBT_RP(1024, 2) BBT_RP(1024, 4) BBT_RP(1024, 8) BBT_RP(2048, 2) BBT_RP(2048, 4) BBT_RP(2048, 8)
-    BBT_RP(4096, 2) BBT_RP(4096, 4) BBT_RP(4096, 8)
-    BBT_RP(256, 16) BBT_RP(256, 32) BBT_RP(256, 64) BBT_RP(256, 128)
-    BBT_RP(512, 16) BBT_RP(512, 32) BBT_RP(512, 64) BBT_RP(512, 128)
-    BBT_RP(1024, 16) BBT_RP(1024, 32) BBT_RP(1024, 64) BBT_RP(1024, 128)
-    BBT_RP(2048, 16) BBT_RP(2048, 32) BBT_RP(2048, 64) BBT_RP(2048, 128)
-    BBT_RP(4096, 16) BBT_RP(4096, 32) BBT_RP(4096, 64) BBT_RP(4096, 128)
-    BBT_RP(256, 256)
-    BBT_RP(512, 256) BBT_RP(512, 512)
-    BBT_RP(1024, 256) BBT_RP(1024, 512) BBT_RP(1024, 1024)
-    BBT_RP(2048, 256) BBT_RP(2048, 512) BBT_RP(2048, 1024) BBT_RP(2048, 2048)
-    BBT_RP(4096, 256) BBT_RP(4096, 512) BBT_RP(4096, 1024) BBT_RP(4096, 2048) BBT_RP(4096, 4096)
-#undef BBT_RP
-    return fail("osm: no row pass for row length %d with %d channels", p->n2, nch);
-}
-
-// pairs per workgroup of the one-kernel plans at most (round 4's rule; BBT_SMALL_CAP overrides: dev)
-#define BBT_SMALL_CAP(N_) ((N_) <= 512 ? 8 : ((N_) <= 2048 ? 4 : 2))
-template <int N>
-static int launch_small(bbt_osm_plan* p, const float2* in, float2* out, const OsmChunk& ch,
-                        hipStream_t st) {
-    // lanes over groups of pairs when there are many (see k_osm_small): the largest of 8, 4, 2 pairs
-    // that divides the pair count and fits a workgroup (1024 threads; the interleaved exchange buffer
-    // is dynamic LDS, up to 136 KiB)
-    constexpr size_t lds1 = FftGeo<N>::LDS_ELEMS * sizeof(v2);
-    const int nblk = ch.reg_count ? ch.reg_count : ch.nblk;
-    if (p->single) {
-        hipLaunchKernelGGL((k_osm_small<N, 1, true>), dim3((nblk + 1) / 2), dim3(N / 16), lds1, st, in,
-                           out, ch, 1, p->resp, p->resp_index, p->tab2.tw0, p->tab2.tw1);
-        return 0;
-    }
-    constexpr int CAP = BBT_SMALL_CAP(N);
-    const int cap = getenv("BBT_SMALL_CAP") ? atoi(getenv("BBT_SMALL_CAP")) : CAP;         // (dev)
-#define BBT_SMALL_PP(PP_)                                                                                    \
-    if ((PP_ * N / 16 <= 1024 && lds1 * PP_ <= 160 * 1024) && PP_ <= cap && p->npair % PP_ == 0) {          \
-        constexpr int Q = (PP_ * N / 16 <= 1024 && lds1 * PP_ <= 160 * 1024) ? PP_ : 1;                      \
-        if (ensure_dyn_lds((const void*)k_osm_small<N, Q>, lds1 * Q)) return 1;                              \
-        hipLaunchKernelGGL((k_osm_small<N, Q>), dim3(nblk * (p->npair / Q)), dim3(Q * N / 16), lds1 * Q,   \
-                           st, in, out, ch, p->S, p->resp, p->resp_index, p->tab2.tw0, p->tab2.tw1);        \
-        return 0;                                                                                            \
-    }
-    BBT_SMALL_PP(8) BBT_SMALL_PP(4) BBT_SMALL_PP(2)
-#undef BBT_SMALL_PP
-    hipLaunchKernelGGL((k_osm_small<N, 1>), dim3(nblk * p->npair), dim3(N / 16), lds1, st, in, out,
-                       ch, p->S, p->resp, p->resp_index, p->tab2.tw0, p->tab2.tw1);
-    return 0;
-}
-
-template <int N>
-static int launch_small_big(bbt_osm_plan* p, const float2* in, float2* out, const OsmChunk& ch, hipStream_t st) {
-    constexpr size_t lds = BigGeo<N>::LDS_ELEMS * sizeof(v2);
-    const int nblk = ch.reg_count ? ch.reg_count : ch.nblk;
-    if (p->single) {
-        if (ensure_dyn_lds((const void*)k_osm_small_big<N, true>, lds)) return 1;
-        hipLaunchKernelGGL((k_osm_small_big<N, true>), dim3((nblk + 1) / 2), dim3(N / 16), lds, st, in, out, ch,
-                           1, p->resp, p->resp_index, p->big_tw);
-        return 0;
-    }
-    if (ensure_dyn_lds((const void*)k_osm_small_big<N>, lds)) return 1;
-    hipLaunchKernelGGL((k_osm_small_big<N>), dim3(nblk * p->npair), dim3(N / 16), lds, st, in, out, ch, p->S,
-                       p->resp, p->resp_index, p->big_tw);
-    return 0;
-}
 
 static int osm_flush_timing(bbt_osm_plan* p) {
     for (size_t i = 0; i + 3 < p->ev.size(); i += 4) {
@@ -873,162 +787,133 @@ static int osm_flush_timing(bbt_osm_plan* p) {
     return 0;
 }
 
-template <bool FIRST, bool SPEC, int N1>
-static int launch_col_long(bbt_osm_plan* p, const float2* in, float2* out, float2* work,
-                           const OsmChunk& ch, int row_len, const SpecOut& so, hipStream_t st) {
-    constexpr int F = 8;
-    constexpr size_t lds = FftGeo<N1>::LDS_ELEMS * sizeof(v2) * F;
-    if (p->single) {
-        if (ensure_dyn_lds((const void*)k_osm_col256<FIRST, SPEC, F, false, 1, true, N1>, lds)) return 1;
-        hipLaunchKernelGGL((k_osm_col256<FIRST, SPEC, F, false, 1, true, N1>),
-                           dim3(row_len / F, (ch.nblk + 1) / 2), dim3(F * (N1 / 16)), lds, st, in, out, work,
-                           ch, 1, row_len, p->tab1.tw0, so, p->tab1.tw1);
-    } else {
-        if (ensure_dyn_lds((const void*)k_osm_col256<FIRST, SPEC, F, false, 1, false, N1>, lds)) return 1;
-        hipLaunchKernelGGL((k_osm_col256<FIRST, SPEC, F, false, 1, false, N1>),
-                           dim3(row_len / F * p->npair, ch.nblk), dim3(F * (N1 / 16)), lds, st, in, out, work,
-                           ch, p->S, row_len, p->tab1.tw0, so, p->tab1.tw1);
-    }
-    return 0;
-}
+// ---- running a chunk: the launches osm_launch.hpp lists ------------------------------------------
+static_assert(fft_lds_elems(256) == FftGeo<256>::LDS_ELEMS && fft_lds_elems(512) == FftGeo<512>::LDS_ELEMS &&
+                  fft_lds_elems(1024) == FftGeo<1024>::LDS_ELEMS && fft_lds_elems(2048) == FftGeo<2048>::LDS_ELEMS &&
+                  fft_lds_elems(4096) == FftGeo<4096>::LDS_ELEMS && big_lds_elems(8192) == BigGeo<8192>::LDS_ELEMS &&
+                  big_lds_elems(16384) == BigGeo<16384>::LDS_ELEMS && sizeof(v2) == 8 && sizeof(f4) == 16,
+              "osm_launch.hpp: the exchange areas are not the templates'");
 
-template <bool FIRST, bool SPEC>
-static int launch_col256(bbt_osm_plan* p, const float2* in, float2* out, float2* work,
-                          const OsmChunk& ch, int row_len, const SpecOut& so_arg, hipStream_t st) {
-    constexpr size_t lds1 = FftGeo<256>::LDS_ELEMS * sizeof(v2);     // per column of a tile
-    SpecOut so = so_arg;
-    // (the row pass then leaves the four-step twiddles to this pass: the forward ones always, the
-    // inverse ones unless the fused channelizer's transform stands between them and this pass)
-    if (p->tw_col && p->outer == 1 && (FIRST || !SPEC)) {
-        so.twa = p->twa;
-        so.twg = p->twg;
+// One launch of the list: the only place that names the kernels of a chunk.  `chw`: the chunk as
+// the row pass counts it (one stream: pairs of blocks).  A combination of parameters that has no
+// instantiation is an error.
+static int osm_dispatch(bbt_osm_plan* p, const OsmLaunch& l, const float2* in, float2* out, float2* work,
+                        const OsmChunk& ch, const OsmChunk& chw, const SpecOut& so, hipStream_t st) {
+    const dim3 grid(l.gx, l.gy), block(l.threads);
+    const int S = l.single ? 1 : p->S;
+#define BBT_GO(KERNEL_, ...)                                                      \
+    {                                                                             \
+        if (l.raise_lds && ensure_dyn_lds((const void*)KERNEL_, l.lds)) return 1; \
+        hipLaunchKernelGGL(KERNEL_, grid, block, l.lds, st, __VA_ARGS__);         \
+        return 0;                                                                 \
     }
-    if (p->n1 == 512 || p->n1 == 1024) {
-        // 512- / 1024-point columns (2^21- / 2^22-sample blocks): 8 columns per workgroup, 128-byte runs
-        if (so.det) return fail("osm: fused detection needs 256-point columns");
-        return p->n1 == 512 ? launch_col_long<FIRST, SPEC, 512>(p, in, out, work, ch, row_len, so, st)
-                            : launch_col_long<FIRST, SPEC, 1024>(p, in, out, work, ch, row_len, so, st);
-    }
-    if (p->single) {
-        if (so.det) return fail("osm: one-stream plans have no fused detection");
-        hipLaunchKernelGGL((k_osm_col256<FIRST, SPEC, 16, false, 1, true>),
-                           dim3(row_len / 16, (ch.nblk + 1) / 2), dim3(256), 16 * lds1, st, in, out, work,
-                           ch, 1, row_len, p->tab1.tw0, so);
-        return 0;
-    }
-    if constexpr (SPEC && !FIRST) {
-        if (so.det) {
-            hipLaunchKernelGGL((k_osm_col256<false, true, 16, true>),
-                               dim3(row_len / 16 * p->npair, ch.nblk), dim3(256), 16 * lds1, st, in, out,
-                               work, ch, p->S, row_len, p->tab1.tw0, so);
-            return 0;
+    switch (l.family) {
+        case OSM_COL16:
+#define BBT_COL16(FIRST_, SPEC_, SINGLE_, PP_)                                      \
+    if (l.first == FIRST_ && l.spec == SPEC_ && l.single == SINGLE_ && l.pp == PP_) \
+        BBT_GO((k_osm_col16<FIRST_, SPEC_, SINGLE_, PP_>), in, out, work, ch, S, p->n2, so)
+            BBT_COL16(true, false, true, 1) BBT_COL16(true, false, false, 8) BBT_COL16(true, false, false, 1)
+            BBT_COL16(false, true, true, 1) BBT_COL16(false, false, true, 1) BBT_COL16(false, true, false, 8)
+            BBT_COL16(false, false, false, 8) BBT_COL16(false, true, false, 1) BBT_COL16(false, false, false, 1)
+#undef BBT_COL16
+            break;
+        case OSM_COL256: {
+            SpecOut so_tw = so;
+            if (l.tw) {
+                so_tw.twa = p->twa;
+                so_tw.twg = p->twg;
+            }
+            // (forward, spectra out, columns, detection, pairs, one stream, column length) -> instantiation
+#define BBT_COL256(FIRST_, SPEC_, F_, DET_, PP_, SINGLE_, N1_)                                                           \
+    if (l.first == FIRST_ && l.spec == SPEC_ && l.F == F_ && l.det == DET_ && l.pp == PP_ && l.single == SINGLE_ &&      \
+        l.n == N1_)                                                                                                      \
+        BBT_GO((k_osm_col256<FIRST_, SPEC_, F_, DET_, PP_, SINGLE_, N1_>), in, out, work, ch, S, l.row_len, p->tab1.tw0, \
+               so_tw, N1_ == 256 ? nullptr : p->tab1.tw1)
+#define BBT_COL256_PASS(FIRST_, SPEC_)                                                                     \
+    BBT_COL256(FIRST_, SPEC_, 8, false, 1, true, 512) BBT_COL256(FIRST_, SPEC_, 8, false, 1, false, 512)   \
+    BBT_COL256(FIRST_, SPEC_, 8, false, 1, true, 1024) BBT_COL256(FIRST_, SPEC_, 8, false, 1, false, 1024) \
+    BBT_COL256(FIRST_, SPEC_, 16, false, 1, true, 256) BBT_COL256(FIRST_, SPEC_, 16, false, 1, false, 256) \
+    BBT_COL256(FIRST_, SPEC_, (FIRST_ ? 64 : 32), false, 8, false, 256)
+            BBT_COL256_PASS(true, false) BBT_COL256_PASS(false, true) BBT_COL256_PASS(false, false)
+            BBT_COL256(false, true, 16, true, 1, false, 256)
+            BBT_COL256(true, false, 64, false, 4, false, 256)
+            BBT_COL256(false, true, 16, false, 4, false, 256) BBT_COL256(false, false, 16, false, 4, false, 256)
+#undef BBT_COL256_PASS
+#undef BBT_COL256
+            break;
         }
+        case OSM_ROWPASS:
+            // (row length, channels) -> instantiation; nch == 0 is the plain row pass.
+#define BBT_RP(N2_, NCH_)                                                                                           \
+    if (l.n == N2_ && l.nch == NCH_)                                                                                \
+        BBT_GO((k_osm_rowpass<N2_, NCH_>), work, p->n1, p->resp, p->resp_index, p->npair, p->tab2.tw0, p->tab2.tw1, \
+               p->wroot, chw, p->outer, l.y0, p->tw4row, p->tw4base, p->tw_col ? (NCH_ ? 1 : 3) : 0, p->tw4o, p->tw4u)
+            BBT_RP(256, 0) BBT_RP(512, 0) BBT_RP(1024, 0) BBT_RP(2048, 0) BBT_RP(4096, 0)
+            BBT_RP(256, 2) BBT_RP(256, 4) BBT_RP(256, 8) BBT_RP(512, 2) BBT_RP(512, 4) BBT_RP(512, 8)
+            BBT_RP(1024, 2) BBT_RP(1024, 4) BBT_RP(1024, 8) BBT_RP(2048, 2) BBT_RP(2048, 4) BBT_RP(2048, 8)
+            BBT_RP(4096, 2) BBT_RP(4096, 4) BBT_RP(4096, 8)
+            BBT_RP(256, 16) BBT_RP(256, 32) BBT_RP(256, 64) BBT_RP(256, 128)
+            BBT_RP(512, 16) BBT_RP(512, 32) BBT_RP(512, 64) BBT_RP(512, 128)
+            BBT_RP(1024, 16) BBT_RP(1024, 32) BBT_RP(1024, 64) BBT_RP(1024, 128)
+            BBT_RP(2048, 16) BBT_RP(2048, 32) BBT_RP(2048, 64) BBT_RP(2048, 128)
+            BBT_RP(4096, 16) BBT_RP(4096, 32) BBT_RP(4096, 64) BBT_RP(4096, 128)
+            BBT_RP(256, 256)
+            BBT_RP(512, 256) BBT_RP(512, 512)
+            BBT_RP(1024, 256) BBT_RP(1024, 512) BBT_RP(1024, 1024)
+            BBT_RP(2048, 256) BBT_RP(2048, 512) BBT_RP(2048, 1024) BBT_RP(2048, 2048)
+            BBT_RP(4096, 256) BBT_RP(4096, 512) BBT_RP(4096, 1024) BBT_RP(4096, 2048) BBT_RP(4096, 4096)
+#undef BBT_RP
+            return fail("osm: no row pass for row length %d with %d channels", l.n, l.nch);
+        case OSM_MID16:
+            if (l.first) BBT_GO((k_osm_mid16<true>), work, p->n2, (int)p->n, p->wroot, l.mid_mode, l.y0)
+            BBT_GO((k_osm_mid16<false>), work, p->n2, (int)p->n, p->wroot, l.mid_mode, l.y0)
+        case OSM_SMALL:
+#define BBT_SM(N_, PP_, SINGLE_)                         \
+    if (l.n == N_ && l.pp == PP_ && l.single == SINGLE_) \
+        BBT_GO((k_osm_small<N_, PP_, SINGLE_>), in, out, ch, S, p->resp, p->resp_index, p->tab2.tw0, p->tab2.tw1)
+#define BBT_SM_N(N_) BBT_SM(N_, 1, true) BBT_SM(N_, 1, false) BBT_SM(N_, 2, false) BBT_SM(N_, 4, false)
+            BBT_SM_N(256) BBT_SM_N(512) BBT_SM_N(1024) BBT_SM_N(2048) BBT_SM_N(4096)
+            BBT_SM(256, 8, false) BBT_SM(512, 8, false) BBT_SM(1024, 8, false) BBT_SM(2048, 8, false)
+#undef BBT_SM_N
+#undef BBT_SM
+            break;
+        case OSM_SMALL_BIG:
+#define BBT_SB(N_, SINGLE_)               \
+    if (l.n == N_ && l.single == SINGLE_) \
+        BBT_GO((k_osm_small_big<N_, SINGLE_>), in, out, ch, S, p->resp, p->resp_index, p->big_tw)
+            BBT_SB(8192, true) BBT_SB(8192, false) BBT_SB(16384, true) BBT_SB(16384, false)
+#undef BBT_SB
+            break;
+        case OSM_GEN_SMALL:
+            BBT_GO(k_gen_osm_small, in, out, ch, p->S, p->resp, p->resp_index, p->g2, p->wn2, p->g2r, p->wn2r)
+        case OSM_GEN_COL:
+            if (l.first) BBT_GO((k_gen_col<true>), in, out, work, ch, p->S, p->n2, p->gen_ct, p->g1, p->wn1)
+            BBT_GO((k_gen_col<false>), in, out, work, ch, p->S, p->n2, p->gen_ct, p->g1, p->wn1)
+        case OSM_GEN_ROW:
+            BBT_GO(k_gen_row, work, p->n1, p->resp, p->resp_index, p->npair, p->g2, p->wn2, p->g2r, p->wn2r, p->tlo,
+                   p->thi, p->tws)
+        case OSM_G2_SMALL:
+            return g2_launch(p->k2_small, grid, block, st, (const float2*)in, out, ch, p->S, (const cf*)p->resp,
+                             (const int*)p->resp_index, (const cf*)p->qw2, (const cf*)p->qw2r);
+        case OSM_G2_FIRST:
+        case OSM_G2_LAST:
+            return g2_launch(l.family == OSM_G2_FIRST ? p->k2_first : p->k2_last, grid, block, st, (const float2*)in, out,
+                             work, ch, p->S, p->n2, p->n2p, (const cf*)p->qw1);
+        case OSM_G2_ROW:
+            return g2_launch(p->k2_row, grid, block, st, work, p->n1, p->n2p, (const cf*)p->resp,
+                             (const int*)p->resp_index, p->npair, (const cf*)p->qw2, (const cf*)p->qw2r,
+                             (const cf*)p->tlo, (const cf*)p->thi, (const cf*)p->tws);
     }
-    if (FIRST && ch.in_plane) {
-        // pair-planar input: every pair is a two-stream array, the plain 16-column tiles read
-        // 256-byte runs of it (the arrangements below are for interleaved rows)
-        hipLaunchKernelGGL((k_osm_col256<FIRST, SPEC, 16>), dim3(row_len / 16 * p->npair, ch.nblk),
-                           dim3(256), 16 * lds1, st, in, out, work, ch, p->S, row_len, p->tab1.tw0, so);
-        return 0;
-    }
-    // Many streams: the lanes of a row go over groups of stream pairs so that the stream side
-    // moves whole lines.  Measured on MI355X (DESIGN, "column-pass tiles"):
-    //   pairs in eights   first pass 8 pairs x 8 columns (64 lanes, 1024 threads: 1 KiB of a row of
-    //                     the stream and 128-byte runs of work), last pass 8 pairs x 4 columns (512
-    //                     threads, no spills): config 4's share +4.2 %, 16 / 32 streams +5-7 %
-    //   pairs in fours    first pass from 8 pairs on 4 pairs x 16 columns (1024 threads; 16 streams
-    //                     +3 %, 8 streams -5 %), last pass 4 pairs x 4 columns (8 streams +11 %)
-    if (p->npair % 8 == 0) {
-        constexpr int F = FIRST ? 64 : 32;
-        if (ensure_dyn_lds((const void*)k_osm_col256<FIRST, SPEC, F, false, 8>, F * lds1)) return 1;
-        hipLaunchKernelGGL((k_osm_col256<FIRST, SPEC, F, false, 8>),
-                           dim3(row_len / (F / 8) * (p->npair / 8), ch.nblk), dim3(F * 16), F * lds1, st,
-                           in, out, work, ch, p->S, row_len, p->tab1.tw0, so);
-        return 0;
-    }
-    if constexpr (FIRST) {
-        if (p->npair % 4 == 0 && p->npair >= 8) {
-            if (ensure_dyn_lds((const void*)k_osm_col256<true, SPEC, 64, false, 4>, 64 * lds1)) return 1;
-            hipLaunchKernelGGL((k_osm_col256<true, SPEC, 64, false, 4>),
-                               dim3(row_len / 16 * (p->npair / 4), ch.nblk), dim3(1024), 64 * lds1, st, in,
-                               out, work, ch, p->S, row_len, p->tab1.tw0, so);
-            return 0;
-        }
-    } else if (p->npair % 4 == 0) {
-        hipLaunchKernelGGL((k_osm_col256<FIRST, SPEC, 16, false, 4>),
-                           dim3(row_len / 4 * (p->npair / 4), ch.nblk), dim3(256), 16 * lds1, st, in,
-                           out, work, ch, p->S, row_len, p->tab1.tw0, so);
-        return 0;
-    }
-    // Plain 16-column tiles.  The first pass (116 VGPRs, 34 KiB of LDS) fits four workgroups per
-    // CU, 464 registers per lane of a SIMD: no row-pass wave (162) of the other lane can join
-    // them.  Asking for 9 KiB more of (unused) LDS leaves three (348 + 162 = 510 of 512): config 2
-    // +2.4 %, headline +0.3 %, four pairs -0.5 % -- hence for one pair only.
-    const int col_pad = (FIRST && p->npair == 1) ? 9216 : 0;
-    if (col_pad && ensure_dyn_lds((const void*)k_osm_col256<FIRST, SPEC, 16>, 16 * lds1 + col_pad)) return 1;
-    hipLaunchKernelGGL((k_osm_col256<FIRST, SPEC, 16>), dim3(row_len / 16 * p->npair, ch.nblk),
-                       dim3(256), 16 * lds1 + col_pad, st, in, out, work, ch, p->S, row_len, p->tab1.tw0, so);
-    return 0;
-}
-
-static int osm_launch_pass(bbt_osm_plan* p, int pass, const float2* in, float2* out, const OsmChunk& ch,
-                           const SpecOut& so, float2* work, hipStream_t st) {
-    const int nch = so.n_chan;
-    OsmChunk pairs_view;               // one stream: the work buffers hold pairs of blocks
-    if (p->single) {
-        pairs_view = ch;
-        pairs_view.nblk = (ch.nblk + 1) / 2;
-    }
-    const OsmChunk& chw = p->single ? pairs_view : ch;       // what the row pass counts
-    const dim3 g16(p->n2 / 256 * p->npair, chw.nblk);        // (the same count with 8 pairs x 32 columns per workgroup)
-    const bool pp8 = p->n1 == 16 && !p->single && p->npair % 8 == 0;
-    if (pass == 0) {
-        if (p->n1 == 16 && p->single)
-            hipLaunchKernelGGL((k_osm_col16<true, false, true>), g16, dim3(256), 0, st, in, out, work, ch,
-                               1, p->n2, so);
-        else if (pp8)
-            hipLaunchKernelGGL((k_osm_col16<true, false, false, 8>), g16, dim3(256), 0, st, in, out, work, ch,
-                               p->S, p->n2, so);
-        else if (p->n1 == 16)
-            hipLaunchKernelGGL((k_osm_col16<true, false>), g16, dim3(256), 0, st, in, out, work, ch,
-                               p->S, p->n2, so);
-        else if (launch_col256<true, false>(p, in, out, work, ch, p->n2, so, st))
-            return 1;
-    } else if (pass == 1) {
-        if (launch_rowpass(p, work, chw, nch, st)) return 1;
-    } else if (p->n1 == 16) {
-        if (p->single && nch)
-            hipLaunchKernelGGL((k_osm_col16<false, true, true>), g16, dim3(256), 0, st, in, out,
-                               work, ch, 1, p->n2, so);
-        else if (p->single)
-            hipLaunchKernelGGL((k_osm_col16<false, false, true>), g16, dim3(256), 0, st, in, out,
-                               work, ch, 1, p->n2, so);
-        else if (nch && pp8)
-            hipLaunchKernelGGL((k_osm_col16<false, true, false, 8>), g16, dim3(256), 0, st, in, out,
-                               work, ch, p->S, p->n2, so);
-        else if (pp8)
-            hipLaunchKernelGGL((k_osm_col16<false, false, false, 8>), g16, dim3(256), 0, st, in, out,
-                               work, ch, p->S, p->n2, so);
-        else if (nch)
-            hipLaunchKernelGGL((k_osm_col16<false, true>), g16, dim3(256), 0, st, in, out,
-                               work, ch, p->S, p->n2, so);
-        else
-            hipLaunchKernelGGL((k_osm_col16<false, false>), g16, dim3(256), 0, st, in, out,
-                               work, ch, p->S, p->n2, so);
-    } else {
-        if (nch ? launch_col256<false, true>(p, in, out, work, ch, p->n2, so, st)
-                : launch_col256<false, false>(p, in, out, work, ch, p->n2, so, st))
-            return 1;
-    }
-    return 0;
+#undef BBT_GO
+    return fail("osm: no %s kernel for this plan (%d, %d pairs per workgroup, %d columns)", osm_family_name(l.family),
+                l.n, l.pp, l.F);
 }
 
 static int osm_run_chunk(bbt_osm_plan* p, const float2* in, float2* out, const OsmChunk& ch_given,
                          const SpecOut& so, float2* work, hipStream_t st, bool sample = true) {
-    const int nch = so.n_chan;   // 0: plain overlap-save output
-    OsmChunk ch_arg = ch_given;
-    ch_arg.in_plane = p->in_plane;
-    ch_arg.out_plane = p->out_plane;
+    OsmChunk ch = ch_given;
+    ch.in_plane = p->in_plane;
+    ch.out_plane = p->out_plane;
     hipEvent_t e[4] = {nullptr, nullptr, nullptr, nullptr};
     const bool timed = p->timing && sample;       // (events on this chunk's kernels)
     if (timed) {
@@ -1042,133 +927,47 @@ static int osm_run_chunk(bbt_osm_plan* p, const float2* in, float2* out, const O
         }
         HIP_TRY(hipEventRecord(e[0], st));
     }
-    const OsmChunk& ch = ch_arg;
+    OsmLaunchPlan lp;
+    lp.n = p->n;
+    lp.generic = p->generic;
+    lp.rtc = p->rtc;
+    lp.single = p->single;
+    lp.outer = p->outer;
+    lp.n1 = p->n1;
+    lp.n2 = p->n2;
+    lp.n2p = p->n2p;
+    lp.npair = p->npair;
+    lp.S = p->S;
+    lp.gen_ct = p->gen_ct;
+    lp.q1_threads = p->q1.threads();
+    lp.q1_ct = p->q1.ct;
+    lp.q2_threads = p->q2.threads();
+    lp.q2_ct = p->q2.ct;
+    lp.tw_col = p->tw_col;
+    OsmChunkFacts facts;
+    facts.nblk = ch.nblk;
+    facts.reg_count = ch.reg_count;
+    facts.n_chan = so.n_chan;       // 0: plain overlap-save output
+    facts.det = so.det != nullptr;
+    facts.in_plane = ch.in_plane != 0;
+    facts.timing = p->timing;
+    if (const char* refusal = osm_chunk_launches(lp, facts, p->knobs, &p->chunk_launches)) return fail("%s", refusal);
     OsmChunk pairs_view;               // one stream: the work buffers hold pairs of blocks
     if (p->single) {
         pairs_view = ch;
         pairs_view.nblk = (ch.nblk + 1) / 2;
     }
-    const OsmChunk& chw = p->single ? pairs_view : ch;       // what the row / middle passes count
-    if (p->generic && p->rtc) {
-        if (nch) return fail("osm: the fused channelizer needs a power-of-two block length");
-        if (p->n1 == 1) {
-            if (g2_launch(p->k2_small, dim3(ch.nblk * p->npair), dim3(p->q2.threads()), st, (const float2*)in, out, ch,
-                          p->S, (const cf*)p->resp, (const int*)p->resp_index, (const cf*)p->qw2, (const cf*)p->qw2r))
-                return 1;
-            if (timed) {
-                HIP_TRY(hipEventRecord(e[1], st));
-                HIP_TRY(hipEventRecord(e[2], st));
-            }
-        } else {
-            const int ct = p->gen_ct, tiles = (p->n2 + ct - 1) / ct;
-            const dim3 gcol((unsigned)tiles * p->npair * ch.nblk), bcol(p->q1.threads());
-            if (g2_launch(p->k2_first, gcol, bcol, st, (const float2*)in, out, work, ch, p->S, p->n2, p->n2p,
-                          (const cf*)p->qw1))
-                return 1;
-            if (timed) HIP_TRY(hipEventRecord(e[1], st));
-            if (g2_launch(p->k2_row, dim3((p->n1 + p->q2.ct - 1) / p->q2.ct, ch.nblk * p->npair), dim3(p->q2.threads()), st, work, p->n1, p->n2p,
-                          (const cf*)p->resp, (const int*)p->resp_index, p->npair, (const cf*)p->qw2,
-                          (const cf*)p->qw2r, (const cf*)p->tlo, (const cf*)p->thi, (const cf*)p->tws))
-                return 1;
-            if (timed) HIP_TRY(hipEventRecord(e[2], st));
-            if (g2_launch(p->k2_last, gcol, bcol, st, (const float2*)in, out, work, ch, p->S, p->n2, p->n2p,
-                          (const cf*)p->qw1))
-                return 1;
-        }
-    } else if (p->generic) {
-        if (nch) return fail("osm: the fused channelizer needs a power-of-two block length");
-        if (p->n1 == 1) {
-            const size_t lds = (size_t)p->n2 * sizeof(f4);
-            if (ensure_dyn_lds((const void*)k_gen_osm_small, lds)) return 1;
-            hipLaunchKernelGGL(k_gen_osm_small, dim3(ch.nblk * p->npair), dim3(gen_threads(p->n2)), lds,
-                               st, in, out, ch, p->S, p->resp, p->resp_index, p->g2, p->wn2, p->g2r, p->wn2r);
-            if (timed) {
-                HIP_TRY(hipEventRecord(e[1], st));
-                HIP_TRY(hipEventRecord(e[2], st));
-            }
-        } else {
-            const int ct = p->gen_ct, tiles = (p->n2 + ct - 1) / ct;
-            // (what k_gen_col transforms: a tile beyond it would come back untransformed in part)
-            ARG_TRY(ct >= 1 && (ct & (ct - 1)) == 0 && (long long)p->n1 * ct <= BBT_GEN_MAX_LEN,
-                    "osm: a column tile of %d x %d elements is more than the general kernels' %d (or not a power of two of columns)",
-                    p->n1, ct, BBT_GEN_MAX_LEN);
-            const size_t lds_c = (size_t)p->n1 * ct * sizeof(f4), lds_r = (size_t)p->n2 * sizeof(f4);
-            if (ensure_dyn_lds((const void*)k_gen_col<true>, lds_c) ||
-                ensure_dyn_lds((const void*)k_gen_col<false>, lds_c) ||
-                ensure_dyn_lds((const void*)k_gen_row, lds_r))
-                return 1;
-            const dim3 gcol(tiles * p->npair, ch.nblk), bcol(gen_threads(p->n1 * ct));
-            hipLaunchKernelGGL((k_gen_col<true>), gcol, bcol, lds_c, st, in, out, work, ch, p->S, p->n2,
-                               ct, p->g1, p->wn1);
-            if (timed) HIP_TRY(hipEventRecord(e[1], st));
-            hipLaunchKernelGGL(k_gen_row, dim3(p->n1, ch.nblk * p->npair), dim3(gen_threads(p->n2)),
-                               lds_r, st, work, p->n1, p->resp, p->resp_index, p->npair, p->g2, p->wn2, p->g2r, p->wn2r,
-                               p->tlo, p->thi, p->tws);
-            if (timed) HIP_TRY(hipEventRecord(e[2], st));
-            hipLaunchKernelGGL((k_gen_col<false>), gcol, bcol, lds_c, st, in, out, work, ch, p->S, p->n2,
-                               ct, p->g1, p->wn1);
-        }
-    } else if (p->n1 == 1) {
-        int rc = 0;
-        switch (p->n2) {
-            case 256: rc = launch_small<256>(p, in, out, ch, st); break;
-            case 512: rc = launch_small<512>(p, in, out, ch, st); break;
-            case 1024: rc = launch_small<1024>(p, in, out, ch, st); break;
-            case 2048: rc = launch_small<2048>(p, in, out, ch, st); break;
-            case 4096: rc = launch_small<4096>(p, in, out, ch, st); break;
-            case 8192: rc = launch_small_big<8192>(p, in, out, ch, st); break;
-            case 16384: rc = launch_small_big<16384>(p, in, out, ch, st); break;
-            default: return fail("osm: unsupported n_fft %lld", (long long)p->n);
-        }
-        if (rc) return rc;
-        if (timed) {
-            HIP_TRY(hipEventRecord(e[1], st));
-            HIP_TRY(hipEventRecord(e[2], st));
-        }
-    } else if (p->outer > 1) {
-        // three levels: outer 256-point column pass over rows of M = 16 * n2, then
-        // the two-level machinery in place on every outer row
-        // The three middle passes (outer twiddle + 16-point step, row pass, and back) act on
-        // every outer row by itself, in place: they go over the work buffer in pieces of
-        // BBT_OSM_MID_MIB (default 128 MiB), so that a piece can still be in the Infinity Cache
-        // when the next pass comes for it.  Measured on MI355X (config 4's share, two runs each):
-        // whole buffer 2.67 / 2.69, pieces of 32 MiB 2.57, 64 MiB 2.70 / 2.71, 128 MiB 2.75 / 2.75,
-        // 256 MiB 2.70 / 2.76 G complete samples/s -- +3 %, not the 1.5x fewer HBM bytes would give:
-        // the other lane's outer column passes stream 4 GiB through the cache meanwhile (making
-        // those accesses non-temporal cost 7 %, one lane 8 %).
-        const int m_len = 16 * p->n2;
-        const int rows_all = chw.nblk * p->npair * 256;
-        static const long long mid_bytes = [] { const char* e = getenv("BBT_OSM_MID_MIB"); return (long long)(e ? atoi(e) : 128) << 20; }();
-        const long long row_bytes = 16ll * p->n2 * 16;
-        int step = mid_bytes > 0 ? (int)std::max<long long>(1, mid_bytes / row_bytes) : rows_all;
-        if (p->timing) step = rows_all;            // (per-pass events: the passes one after the other)
-        if (launch_col256<true, false>(p, in, out, work, ch, m_len, so, st)) return 1;
-        for (int y0 = 0; y0 < rows_all; y0 += step) {
-            const int ny = std::min(step, rows_all - y0);
-            const dim3 gmid(p->n2 / 256, ny);
-            hipLaunchKernelGGL((k_osm_mid16<true>), gmid, dim3(256), 0, st, work, p->n2, (int)p->n,
-                               p->wroot, 0, y0);
-            if (timed) HIP_TRY(hipEventRecord(e[1], st));
-            if (launch_rowpass(p, work, chw, nch, st, y0, ny)) return 1;
-            if (timed) HIP_TRY(hipEventRecord(e[2], st));
-            hipLaunchKernelGGL((k_osm_mid16<false>), gmid, dim3(256), 0, st, work, p->n2, (int)p->n,
-                               p->wroot, nch ? 1 : 0, y0);
-        }
-        if (nch ? launch_col256<false, true>(p, in, out, work, ch, m_len, so, st)
-                : launch_col256<false, false>(p, in, out, work, ch, m_len, so, st))
-            return 1;
-    } else {
-        if (osm_launch_pass(p, 0, in, out, ch, so, work, st)) return 1;
-        if (timed) HIP_TRY(hipEventRecord(e[1], st));
-        if (osm_launch_pass(p, 1, in, out, ch, so, work, st)) return 1;
-        if (timed) HIP_TRY(hipEventRecord(e[2], st));
-        if (osm_launch_pass(p, 2, in, out, ch, so, work, st)) return 1;
+    const OsmChunk& chw = p->single ? pairs_view : ch;       // what the row pass counts
+    for (const OsmLaunch& l : p->chunk_launches) {
+        if (osm_dispatch(p, l, in, out, work, ch, chw, so, st)) return 1;
+        if (timed && (l.mark & 1)) HIP_TRY(hipEventRecord(e[1], st));
+        if (timed && (l.mark & 2)) HIP_TRY(hipEventRecord(e[2], st));
     }
     HIP_TRY(hipGetLastError());
     if (timed) {
         HIP_TRY(hipEventRecord(e[3], st));
         for (int i = 0; i < 4; ++i) p->ev.push_back(e[i]);
-        p->ev_nblk.push_back(ch_arg.nblk);
+        p->ev_nblk.push_back(ch.nblk);
         if (p->ev.size() >= 65536) return osm_flush_timing(p);   // (a flush waits for the events)
     }
     return 0;
@@ -1570,6 +1369,7 @@ int bbt_osm_plan_create(bbt_osm_plan** plan, int64_t n_fft, int n_stream, int n_
     p->lanes = geo.lanes;
     p->work_bytes = geo.work_bytes;
     p->timing_stride = knobs.timing_stride;
+    p->knobs = knobs;
     if (osm_make_lanes(p)) return bail(1);
     *plan = p;
     return 0;

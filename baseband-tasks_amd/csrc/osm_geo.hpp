@@ -46,6 +46,8 @@ struct OsmKnobs {
     bool has_chunk = false;     // BBT_OSM_CHUNK is set: `chunk` blocks per launch, and no longer regular runs
     int chunk = 0;
     int timing_stride = 4;      // BBT_OSM_TIMING_STRIDE: timing events on every such chunk of a lane
+    int small_cap = -1;         // BBT_SMALL_CAP (dev): pairs per workgroup of the one-kernel plans at most; -1: the rule
+    int mid_mib = 128;          // BBT_OSM_MID_MIB: three levels, the piece the middle passes take at a time (osm_launch.hpp)
 };
 static inline OsmKnobs osm_knobs_from_env() {
     OsmKnobs k;
@@ -59,6 +61,8 @@ static inline OsmKnobs osm_knobs_from_env() {
         k.chunk = atoi(env);
     }
     if (const char* env = getenv("BBT_OSM_TIMING_STRIDE")) k.timing_stride = std::max(1, atoi(env));
+    if (const char* env = getenv("BBT_SMALL_CAP")) k.small_cap = std::max(0, atoi(env));
+    if (const char* env = getenv("BBT_OSM_MID_MIB")) k.mid_mib = atoi(env);
     return k;
 }
 

@@ -1,11 +1,14 @@
 // Prints what the host rules decide without a device, as JSON lines, for tests/test_gen2_planner.py,
-// tests/test_osm_geo.py and tests/test_tune_geo.py:
+// tests/test_osm_geo.py, tests/test_osm_launches.py and tests/test_tune_geo.py:
 //   plan <pmax> <n> <ct> ...     a plan of the generic-length engine (csrc/gen2_host.hpp)
 //   split <N> ...                the measured split of a block and the plans of both kernels (csrc/osm_geo.hpp: osm_levels)
 //   route off|on|failed <N> ...  what a two-level block runs with on the general LDS Stockham kernels (csrc/gen_host.hpp)
 //   source <N> | source2 <N>     the translation unit an overlap-save plan compiles for a block (osm_g2_source)
 //   osm 0|1|failed <n_fft> <n_stream> ...   levels and buffers of a plan: BBT_RTC=0, compiled, compilation failed
 //   parts <run> <chunk> <cap> <lanes> <fork> ...   how a regular run is cut into launches (osm_run_parts)
+//   launches 0|1|failed <n_fft> <n_stream> <nblk> <reg_count> <n_chan> <det> <in_plane> <timing> <mid_mib> ...
+//                                the kernel launches of one chunk of that plan (csrc/osm_launch.hpp: osm_chunk_launches),
+//                                or the refusal; mid_mib: BBT_OSM_MID_MIB, 128 unless set
 //   chan [dir=<d>] <n_chan> <n_stream> ...   a channelizer plan (csrc/chan_geo.hpp): its kind or the refusal, the candidates
 //                                a timed plan compares, and the untimed choice (-1: none) with the default knobs, with
 //                                BBT_G2_TUNE=0, with BBT_G2_CHAN_WIDE too, and with 116 remembered
@@ -17,6 +20,7 @@
 #include <cstdlib>
 #include <cstring>
 #include "chan_geo.hpp"
+#include "osm_launch.hpp"
 #include "pfb_geo.hpp"
 using namespace bbt;
 
@@ -135,6 +139,73 @@ int main(int argc, char** argv) {
             int64_t parts, per;
             osm_run_parts(atoll(argv[i]), atoi(argv[i + 1]), atoi(argv[i + 2]), atoi(argv[i + 3]), atoi(argv[i + 4]) != 0, &parts, &per);
             printf("{\"parts\": %lld, \"per\": %lld}\n", (long long)parts, (long long)per);
+        }
+    } else if (!strcmp(argv[1], "launches")) {
+        OsmKnobs knobs;
+        knobs.rtc = !strcmp(argv[2], "0") ? 0 : 1;
+        const bool rtc_ok = !strcmp(argv[2], "1");
+        std::vector<OsmLaunch> list;
+        for (int i = 3; i + 8 < argc; i += 9) {
+            OsmGeo g;
+            std::string text;
+            if (!osm_levels(atoll(argv[i]), atoi(argv[i + 1]), knobs, &g, &text)) {
+                printf("{\"error\": \"%s\"}\n", text.c_str());
+                continue;
+            }
+            osm_buffers(&g, g.generic && g.compiled && rtc_ok, knobs);
+            OsmLaunchPlan lp;
+            lp.n = g.n;
+            lp.generic = g.generic;
+            lp.rtc = g.generic && g.compiled && rtc_ok;
+            lp.single = g.single;
+            lp.outer = g.outer;
+            lp.n1 = g.n1;
+            lp.n2 = g.n2;
+            lp.n2p = g.n2p;
+            lp.npair = g.npair;
+            lp.S = g.S;
+            lp.gen_ct = g.gen_ct;
+            lp.q1_threads = g.q1.threads();
+            lp.q1_ct = g.q1.ct;
+            lp.q2_threads = g.q2.threads();
+            lp.q2_ct = g.q2.ct;
+            lp.tw_col = !g.generic && g.n1 >= 256 && g.outer == 1;       // (bbt_hip.hip: osm_pow2_tables)
+            OsmChunkFacts c;
+            c.nblk = atoi(argv[i + 2]);
+            c.reg_count = atoi(argv[i + 3]);
+            c.n_chan = atoi(argv[i + 4]);
+            c.det = atoi(argv[i + 5]) != 0;
+            c.in_plane = atoi(argv[i + 6]) != 0;
+            c.timing = atoi(argv[i + 7]) != 0;
+            knobs.mid_mib = atoi(argv[i + 8]);
+            if (const char* refusal = osm_chunk_launches(lp, c, knobs, &list)) {
+                printf("{\"error\": \"%s\"}\n", refusal);
+                continue;
+            }
+            printf("{\"chunk\": %d, \"npair\": %d, \"outer\": %d, \"n1\": %d, \"n2\": %d, \"fusable\": %s, \"launches\": [", g.chunk,
+                   g.npair, g.outer, g.n1, g.n2, osm_fusable(g.generic, g.single, g.outer, g.n1, g.n2, c.n_chan) ? "true" : "false");
+            for (size_t j = 0; j < list.size(); ++j) {
+                const OsmLaunch& l = list[j];
+                const char* const tf[] = {"false", "true"};
+                printf("%s{\"kernel\": \"%s\", \"targs\": [", j ? ", " : "", osm_family_name(l.family));
+                // (the template arguments as a trace demangles them)
+                switch (l.family) {
+                    case OSM_COL16: printf("\"%s\", \"%s\", \"%s\", \"%d\"", tf[l.first], tf[l.spec], tf[l.single], l.pp); break;
+                    case OSM_COL256:
+                        printf("\"%s\", \"%s\", \"%d\", \"%s\", \"%d\", \"%s\", \"%d\"", tf[l.first], tf[l.spec], l.F, tf[l.det], l.pp,
+                               tf[l.single], l.n);
+                        break;
+                    case OSM_ROWPASS: printf("\"%d\", \"%d\"", l.n, l.nch); break;
+                    case OSM_MID16: case OSM_GEN_COL: printf("\"%s\"", tf[l.first]); break;
+                    case OSM_SMALL: printf("\"%d\", \"%d\", \"%s\"", l.n, l.pp, tf[l.single]); break;
+                    case OSM_SMALL_BIG: printf("\"%d\", \"%s\"", l.n, tf[l.single]); break;
+                    default: break;
+                }
+                printf("], \"grid\": [%u, %u], \"threads\": %d, \"lds\": %lld, \"raise_lds\": %s, \"row_len\": %d, \"y0\": %d, "
+                       "\"ny\": %d, \"mid_mode\": %d, \"tw\": %s, \"mark\": %d}",
+                       l.gx, l.gy, l.threads, (long long)l.lds, tf[l.raise_lds], l.row_len, l.y0, l.ny, l.mid_mode, tf[l.tw], l.mark);
+            }
+            printf("]}\n");
         }
     } else if (!strcmp(argv[1], "chan")) {
         int direction = -1;
