@@ -35,6 +35,8 @@ from . import periodicity
 from .ffa import (FFASearch, ffa_search_samples, ffa_transform_samples, ffa_shift, ffa_scales, ffa_period,
                   ffa_candidates, ffa_plan)
 from . import ffa
+from .correlation import Correlate, correlate_samples, baseline_pairs
+from . import correlation
 from .conversion import Real2Complex
 from .shaping import (ChangeSampleShapeBase, ChangeSampleShape, Reshape, Transpose, ReshapeAndTranspose,
                       GetItem, GetSlice)

@@ -42,6 +42,7 @@
 #include "accel_kernels.hpp"
 #include "rank_kernels.hpp"
 #include "rmed_kernels.hpp"
+#include "corr_kernels.hpp"
 #include "r2c_kernels.hpp"
 #include "gather_kernels.hpp"
 #include "pack_kernels.hpp"
@@ -51,7 +52,7 @@
 
 using namespace bbt;
 
-#define BBT_VERSION 170
+#define BBT_VERSION 171
 
 // ---------------------------------------------------------------------------
 // errors
@@ -3443,7 +3444,7 @@ extern "C" int bbt_shift_execute(bbt_shift_plan* p, const void* in_dev, void* ou
 }
 
 // ---------------------------------------------------------------------------
-// what the sections of the search chain share (dmt, sps, ffa, hsum, lspec, accel, rank, rmed)
+// what the sections of the search chain share (dmt, sps, ffa, hsum, lspec, accel, rank, rmed, corr)
 
 // A tiling or routing knob from the environment: the value of `name` if it is one of `allowed`, else 0,
 // which stands for the section's default.  The contract of every knob below: it is read at every call,
@@ -4271,6 +4272,102 @@ extern "C" int bbt_rmed_execute(bbt_rmed_plan* p, const float* in_dev, int64_t i
     const float* x_out = in_dev + (g.out_first - g.in_first) * E;
     hipLaunchKernelGGL(k_rmed_apply, dim3((unsigned)wg_apply), block, 0, st, x_out, (const unsigned*)m, out_dev, g);
     HIP_TRY(hipGetLastError());
+    return 0;
+}
+
+// ---------------------------------------------------------------------------
+// cross-products of up to 64 inputs: Correlate (corr_kernels.hpp; the cutting is corr_geo.hpp's)
+struct bbt_corr_plan {
+    long long A = 0, E = 0, inner = 0, n = 0;
+    int average = 0;
+    long long carried = -1;          // the sample up to which `carry` holds the sums of an unfinished block, or -1
+    PlanScratch scratch;             // [segment][element][baseline] of a piece, float32 pairs
+    PlanScratch carry;               // [element][baseline], float64 pairs
+};
+
+// BBT_CORR_PACK: elements that share a 32 x 32 tile (1 ... 8, at most 32 / (2 n_inputs)); BBT_CORR_WAVES: waves
+// of a workgroup (1, 2, 4).
+static int corr_env_pack() { return env_knob("BBT_CORR_PACK", {1, 2, 3, 4, 5, 6, 7, 8}); }
+static int corr_env_waves() { return env_knob("BBT_CORR_WAVES", {1, 2, 4}); }
+
+extern "C" int bbt_corr_plan_destroy(bbt_corr_plan* p) {
+    if (!p) return 0;
+    p->scratch.release();
+    p->carry.release();
+    delete p;
+    return 0;
+}
+
+extern "C" int bbt_corr_plan_create(bbt_corr_plan** plan, int64_t n_inputs, int64_t n_elem, int64_t inner, int64_t n,
+                                    int average) {
+    ARG_TRY(plan, "bbt_corr_plan_create: null argument");
+    *plan = nullptr;
+    const char* err = corr_sizes(n_inputs, n_elem, n);
+    if (!err && (inner < 1 || n_elem % inner)) err = "inner must divide n_elem";
+    ARG_TRY(!err, "bbt_corr_plan_create: %s (n_inputs=%lld, n_elem=%lld, inner=%lld, n=%lld)", err ? err : "",
+            (long long)n_inputs, (long long)n_elem, (long long)inner, (long long)n);
+    bbt_corr_plan* p = new bbt_corr_plan;
+    p->A = n_inputs, p->E = n_elem, p->inner = inner, p->n = n, p->average = average != 0;
+    *plan = p;
+    return 0;
+}
+
+// For the piece [first, first + count) of a stream: the elements that share a tile, the tiles of a wave, the
+// waves of a workgroup, the LDS bytes of a workgroup, the scratch bytes and the segments of the piece.  No
+// device.
+extern "C" int bbt_corr_info(int64_t n_inputs, int64_t n_elem, int64_t n, int64_t first, int64_t count, int* pack,
+                             int* tiles, int* waves, int64_t* lds_bytes, int64_t* scratch_bytes, int64_t* n_seg) {
+    CorrGeo g = {};
+    const char* err = corr_geo(n_inputs, n_elem, n, first, count, corr_env_pack(), corr_env_waves(), &g);
+    ARG_TRY(!err, "bbt_corr_info: %s (n_inputs=%lld, n_elem=%lld, n=%lld, first=%lld, count=%lld)", err ? err : "",
+            (long long)n_inputs, (long long)n_elem, (long long)n, (long long)first, (long long)count);
+    if (pack) *pack = g.pack;
+    if (tiles) *tiles = g.n_tile;
+    if (waves) *waves = g.waves;
+    if (lds_bytes) *lds_bytes = g.lds_bytes;
+    if (scratch_bytes) *scratch_bytes = g.scratch_bytes;
+    if (n_seg) *n_seg = g.n_seg;
+    return 0;
+}
+
+// in_dev: samples [first, first + count) of the stream, whole segments.  The blocks that end in the piece
+// are written to out_dev, which begins at block out_block0 and holds n_out_blocks.  A piece that begins
+// inside a block must follow the piece that ended there.
+extern "C" int bbt_corr_execute(bbt_corr_plan* p, const void* in_dev, int64_t first, int64_t count, void* out_dev,
+                                int64_t out_block0, int64_t n_out_blocks, bbt_stream stream) {
+    ARG_TRY(p && in_dev && out_dev, "bbt_corr_execute: null argument");
+    ARG_TRY(((((uintptr_t)in_dev) | ((uintptr_t)out_dev)) & 7) == 0, "bbt_corr_execute: arrays must be 8-byte aligned");
+    CorrGeo g = {};
+    const char* err = corr_geo(p->A, p->E, p->n, first, count, corr_env_pack(), corr_env_waves(), &g);
+    ARG_TRY(!err, "bbt_corr_execute: %s (first=%lld, count=%lld)", err ? err : "", (long long)first, (long long)count);
+    ARG_TRY(g.seg0 == 0 || p->carried == first,
+            "bbt_corr_execute: a piece that begins inside a block must follow the piece that ended there (first=%lld)",
+            (long long)first);
+    ARG_TRY(out_block0 >= 0 && n_out_blocks >= 0 && (g.blk1 == g.blk0 || (out_block0 <= g.blk0 && g.blk1 <= out_block0 + n_out_blocks)),
+            "bbt_corr_execute: the output [%lld, %lld) does not hold the blocks [%lld, %lld) that end in the piece",
+            (long long)out_block0, (long long)(out_block0 + n_out_blocks), (long long)g.blk0, (long long)g.blk1);
+    const long long n_val = 2 * g.E * g.B;
+    const long long wg_finish = (n_val + 255) / 256;
+    ARG_TRY(wg_finish < (1ll << 31), "bbt_corr_execute: too many values for one launch");
+    const bool ends_inside = first + count != g.blk1 * g.n;
+    if (p->scratch.reserve((size_t)g.scratch_bytes)) return 1;
+    if ((g.seg0 || ends_inside) && p->carry.reserve((size_t)n_val * 8)) return 1;
+    hipStream_t st = (hipStream_t)stream;
+    const dim3 grid((unsigned)g.n_wg), block(64 * g.waves);
+    const size_t lds = (size_t)g.lds_bytes;
+    const float* x = (const float*)in_dev;
+    float* sc = (float*)p->scratch.ptr;
+    switch (g.T) {
+    case 1: hipLaunchKernelGGL((k_corr_gram<1>), grid, block, lds, st, x, sc, g); break;
+    case 2: hipLaunchKernelGGL((k_corr_gram<2>), grid, block, lds, st, x, sc, g); break;
+    case 3: hipLaunchKernelGGL((k_corr_gram<3>), grid, block, lds, st, x, sc, g); break;
+    default: hipLaunchKernelGGL((k_corr_gram<4>), grid, block, lds, st, x, sc, g); break;
+    }
+    HIP_TRY(hipGetLastError());
+    hipLaunchKernelGGL(k_corr_finish, dim3((unsigned)wg_finish), dim3(256), 0, st, (const float*)sc, (double*)p->carry.ptr,
+                       (float*)out_dev, g, p->inner, (long long)out_block0, p->average);
+    HIP_TRY(hipGetLastError());
+    p->carried = ends_inside ? first + count : -1;
     return 0;
 }
 

@@ -145,6 +145,10 @@ SIGNATURES = {
     'bbt_rmed_info': [_i64, _i64, _i64, _i64, _i64, _i64, C.POINTER(_int), C.POINTER(_int), C.POINTER(_int), _pi64, _pi64,
                       _pi64, _pi64],
     'bbt_rmed_execute': [_vp, _vp, _i64, _i64, _vp, _i64, _i64, _i64, _int, _vp],
+    'bbt_corr_plan_create': [_pvp, _i64, _i64, _i64, _i64, _int],
+    'bbt_corr_plan_destroy': [_vp],
+    'bbt_corr_info': [_i64, _i64, _i64, _i64, _i64, C.POINTER(_int), C.POINTER(_int), C.POINTER(_int), _pi64, _pi64, _pi64],
+    'bbt_corr_execute': [_vp, _vp, _i64, _i64, _vp, _i64, _i64, _vp],
     'bbt_fir_plan_create': [_pvp, _int, _int, _vp],
     'bbt_fir_plan_destroy': [_vp],
     'bbt_fir_execute': [_vp, _vp, _vp, _i64, _vp],
@@ -179,7 +183,7 @@ SIGNATURES = {
 }
 
 #: oldest libbbt_hip.so whose entry points and argument meanings this binding assumes
-MIN_LIB_VERSION = 170
+MIN_LIB_VERSION = 171
 
 _lib = None
 _lock = threading.Lock()
@@ -2122,6 +2126,59 @@ class RmedPlan(_Plan):
                              "needed, n_in >= 1, n_out >= 1")
         check(lib().bbt_rmed_execute(self._h, in_dev.ptr_to_read(), in_first, n_in, out_dev.ptr, out_first, n_out,
                                      n_rows, RMED_DETREND if detrend else RMED_BASELINE, _stream))
+
+
+#: bounds of the correlator and the segment of its rule (csrc/corr_geo.hpp)
+CORR_MIN_INPUTS, CORR_MAX_INPUTS, CORR_MAX_N, CORR_SEG = 2, 64, 1 << 24, 1024
+
+
+def corr_info(n_inputs, n_elem=1, n=1, first=0, count=None):
+    """For the piece ``[first, first + count)`` (default: one block) of a stream correlated in blocks of ``n``:
+    the elements that share a tile now (BBT_CORR_PACK), the tiles a wave holds, the waves of a workgroup
+    (BBT_CORR_WAVES), the LDS bytes of a workgroup, the scratch bytes and the segments of the piece.  No
+    device is needed."""
+    pack, tiles, waves = _int(0), _int(0), _int(0)
+    lds, scratch, n_seg = _i64(0), _i64(0), _i64(0)
+    count = int(n) if count is None else int(count)
+    check(lib().bbt_corr_info(int(n_inputs), int(n_elem), int(n), int(first), count, C.byref(pack), C.byref(tiles),
+                              C.byref(waves), C.byref(lds), C.byref(scratch), C.byref(n_seg)))
+    return dict(pack=pack.value, tiles=tiles.value, waves=waves.value, lds_bytes=lds.value,
+                scratch_bytes=scratch.value, n_seg=n_seg.value)
+
+
+class CorrPlan(_Plan):
+    """The cross-products ``x_i conj(x_j)``, ``i <= j``, of the ``n_inputs`` adjacent inputs of a complex64 stream
+    of samples of ``n_elem`` elements, integrated over blocks of ``n`` samples (bbt_corr_* in
+    include/bbt_hip.h; `correlation.correlate_samples` restates the values in NumPy).  ``inner``: the elements
+    of a sample that lie behind the baselines in the output.  The plan owns the scratch of the segment
+    values and the float64 carry of a block that a piece leaves unfinished."""
+    _destroy = 'bbt_corr_plan_destroy'
+
+    def __init__(self, n_inputs, n_elem, n, inner=1, average=True):
+        super().__init__()
+        self.n_inputs, self.n_elem, self.n, self.inner = int(n_inputs), int(n_elem), int(n), int(inner)
+        self.average = bool(average)
+        self.n_baselines = self.n_inputs * (self.n_inputs + 1) // 2
+        check(lib().bbt_corr_plan_create(C.byref(self._h), self.n_inputs, self.n_elem, self.inner, self.n,
+                                         int(self.average)))
+
+    def info(self, first=0, count=None):
+        """`corr_info` for a piece of this plan."""
+        return corr_info(self.n_inputs, self.n_elem, self.n, first, count)
+
+    def execute(self, in_dev, first, count, out_dev, out_block0, n_out_blocks):
+        """``in_dev``: complex64, at least ``count * n_elem * n_inputs`` values, samples ``[first, first + count)`` of
+        the stream, whole segments; ``out_dev``: complex64, ``n_out_blocks * n_elem * n_baselines`` values at least,
+        for blocks ``[out_block0, out_block0 + n_out_blocks)``, of which those that end in the piece are written."""
+        first, count, out_block0, n_out_blocks = int(first), int(count), int(out_block0), int(n_out_blocks)
+        if in_dev.dtype != np.complex64 or out_dev.dtype != np.complex64:
+            raise TypeError("CorrPlan.execute: complex64 DeviceArrays are needed")
+        if (count < 1 or first < 0 or n_out_blocks < 0 or in_dev.size < count * self.n_elem * self.n_inputs
+                or out_dev.size < n_out_blocks * self.n_elem * self.n_baselines):
+            raise ValueError("CorrPlan.execute: complex64 DeviceArrays of count * n_elem * n_inputs and n_out_blocks * "
+                             "n_elem * n_baselines values are needed, count >= 1")
+        check(lib().bbt_corr_execute(self._h, in_dev.ptr_to_read(), first, count, out_dev.ptr, out_block0,
+                                     n_out_blocks, _stream))
 
 
 COMM_ID_BYTES = 128

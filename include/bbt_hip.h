@@ -53,6 +53,7 @@ typedef struct bbt_hsum_plan bbt_hsum_plan;
 typedef struct bbt_lspec_plan bbt_lspec_plan;
 typedef struct bbt_accel_plan bbt_accel_plan;
 typedef struct bbt_rmed_plan bbt_rmed_plan;
+typedef struct bbt_corr_plan bbt_corr_plan;
 typedef struct bbt_fir_plan bbt_fir_plan;
 typedef struct bbt_r2c_plan bbt_r2c_plan;
 typedef struct bbt_gather_plan bbt_gather_plan;
@@ -792,6 +793,44 @@ int bbt_rmed_info(int64_t width, int64_t scrunch, int64_t n_elem, int64_t n_rows
                   int64_t* in_count);
 int bbt_rmed_execute(bbt_rmed_plan* plan, const float* in_dev, int64_t in_first, int64_t n_in, float* out_dev,
                      int64_t out_first, int64_t n_out, int64_t n_rows, int mode, bbt_stream stream);
+
+/* ---- cross-products of up to 64 inputs: Correlate ----------------------------------
+ * The stream is x[t][e][a], t < N, e < n_elem, a < A = n_inputs (2 ... 64), complex64, input fastest.  Blocks
+ * of n samples (1 ... 2^24) are counted from sample 0.  The B = A (A + 1) / 2 baselines (i, j), i <= j, are in
+ * row-major order, (0,0), (0,1), ... (0,A-1), (1,1), ...; the value of one is sum_t x_i(t) conj(x_j(t)) over the
+ * block, divided by n if `average`.
+ *
+ * The rule, fixed so that no value depends on how the work is cut: a block is cut into segments of SEG =
+ * 1024 samples from its first sample, the last possibly shorter.  Per segment and baseline four float32
+ * chains run in sample order from +0, one fused multiply-add per sample: rr += re_i re_j, ii += im_i im_j, ir
+ * += im_i re_j, ri += re_i im_j; then Re = rr + ii and Im = ir - ri, one rounded float32 operation each.  The
+ * segment values are added in float64 in segment order and divided by n in float64 if averaged; each
+ * part is rounded once to float32.  The imaginary part of an autocorrelation is exactly +0.
+ *
+ * bbt_corr_execute takes a PIECE: in_dev holds samples [first, first + count) of the stream, whole
+ * segments -- it begins at a segment's first sample and ends at a segment's or a block's end.  The blocks
+ * that end in the piece are written to out_dev, complex64, which begins at block out_block0 and holds
+ * n_out_blocks blocks of n_elem B values: with `inner` the number of elements of a sample that lie behind
+ * the inputs' axis in the caller's layout, element e = outer * inner + in goes to [block][outer][baseline][in].
+ * A block that a piece leaves unfinished is carried in float64 in the plan; the piece that begins inside
+ * a block must be the one that follows, else the call is refused.  One plan serves one stream at a time.
+ *
+ * The matrix cores make the chains: a wave owns one segment of a group of `pack` adjacent elements and
+ * accumulates the upper triangle of 32 x 32 tiles of the group's real Gram matrix with v_mfma_f32_32x32x2_f32
+ * (1 tile up to 16 inputs, where several elements share it; 3, 6, 10 tiles up to 32, 48, 64).  The segment
+ * values pass through a float32 scratch the plan owns, count / SEG * n_elem * B * 8 bytes; a second kernel
+ * adds them.  No atomics.  BBT_CORR_PACK = 1 ... 8 (at most 32 / (2 A) elements fit) and BBT_CORR_WAVES = 1, 2
+ * or 4, read from the environment at every call, only change the speed.  bbt_corr_info, for a piece: the
+ * elements of a tile, the tiles of a wave, the waves and the LDS bytes of a workgroup, the scratch bytes
+ * and the segments.  It needs no device.  Every refusal -- a null or misaligned pointer (8 bytes), a size
+ * out of range, a piece that is not whole segments or does not follow, an output that does not hold the
+ * finished blocks -- comes before anything is launched.  Asynchronous on `stream`. */
+int bbt_corr_plan_create(bbt_corr_plan** plan, int64_t n_inputs, int64_t n_elem, int64_t inner, int64_t n, int average);
+int bbt_corr_plan_destroy(bbt_corr_plan* plan);
+int bbt_corr_info(int64_t n_inputs, int64_t n_elem, int64_t n, int64_t first, int64_t count, int* pack, int* tiles,
+                  int* waves, int64_t* lds_bytes, int64_t* scratch_bytes, int64_t* n_seg);
+int bbt_corr_execute(bbt_corr_plan* plan, const void* in_dev, int64_t first, int64_t count, void* out_dev,
+                     int64_t out_block0, int64_t n_out_blocks, bbt_stream stream);
 
 /* ---- real-valued streams ------------------------------------------------------
  * float32 streams run through the complex kernels (the reference's rfft/irfft

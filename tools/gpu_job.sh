@@ -16,6 +16,7 @@
 #   sq      [CMD=..]          SQ counters (two passes of 8) of a command (default: headline, 96 blocks)
 #   ffa     [ARGS=..] [ROW=n20_d64]   tools/bench_ffa.py $ARGS, then one row under a kernel trace: fold passes against the S/N pass
 #   rmed    [ARGS=..] [ROW=w65_s16]  tools/bench_rmed.py $ARGS, then one row under a kernel trace: the scrunch, the selection and the last pass
+#   corr    [ARGS=..] [ROW=a16]      tools/bench_corr.py $ARGS, then one row under a kernel trace: the Gram kernel against the finishing pass
 #   gloo2                     bench.py --full rehearsal of two ranks sharing this GPU (gloo)
 #   evidence                  round-end: suite, profiles of every config, timeline, SQ counters, bench
 #                             lines, next rows, generic lengths, host path (then: tools/summarise.sh)
@@ -131,6 +132,13 @@ rmed)
     ( cd /tmp
       timeout -k 10 400 rocprofv3 --kernel-trace --stats -d $OUT/prof/rmed -o run -- python3 $R/tools/bench_rmed.py --child --reps 1 ${ROW:-w65_s16} > $OUT/prof/rmed.log 2>&1; say "rmed trace rc=$?" )
     python3 tools/rocprof_db.py stats $OUT/prof/rmed/run_results.db $OUT/rmed_kernel_stats.csv ;;
+corr)
+    timeout -k 10 1100 python3 tools/bench_corr.py --out $OUT/corr_bench.jsonl $ARGS 2> $OUT/corr_bench.err; rc=$?; say "corr bench rc=$rc"
+    [ $rc -eq 0 ] || { tail -5 $OUT/corr_bench.err; exit 1; }
+    mkdir -p $OUT/prof
+    ( cd /tmp
+      timeout -k 10 400 rocprofv3 --kernel-trace --stats -d $OUT/prof/corr -o run -- python3 $R/tools/bench_corr.py --child --reps 1 ${ROW:-a16} > $OUT/prof/corr.log 2>&1; say "corr trace rc=$?" )
+    python3 tools/rocprof_db.py stats $OUT/prof/corr/run_results.db $OUT/corr_kernel_stats.csv ;;
 gloo2)
     gloo2 ;;
 evidence)
