@@ -2836,6 +2836,18 @@ static std::vector<cf> r2c_response(int64_t M, double scale) {
     return h;
 }
 
+// bytes of each work buffer of the three-step route: 256 MiB, or what the environment's BBT_R2C_WORK_KIB asks
+// for, in KiB, fractions allowed (a developer knob, read when a plan is made: tests make a call of a few
+// groups run in several batches; no value of the output depends on it)
+static int64_t r2c_work_bytes() {
+    const char* e = getenv("BBT_R2C_WORK_KIB");
+    if (e && *e) {
+        const double kib = atof(e);
+        if (kib > 0. && kib <= (double)(1 << 22)) return (int64_t)(kib * 1024.);
+    }
+    return int64_t(256) << 20;
+}
+
 extern "C" {
 
 int bbt_r2c_plan_create(bbt_r2c_plan** plan, int64_t n_out, int n_stream) {
@@ -2889,7 +2901,7 @@ int bbt_r2c_plan_create_ex(bbt_r2c_plan** plan, int64_t n_out, int n_stream, int
                              why.c_str()));
         }
         // work buffers of at most 256 MiB each (one block at least)
-        p->cap = std::max<int64_t>(1, (int64_t(256) << 20) / (n_out * 16));
+        p->cap = std::max<int64_t>(1, r2c_work_bytes() / (n_out * 16));
     }
     if (hipEventCreateWithFlags(&p->ev_done, hipEventDisableTiming) != hipSuccess)
         return bail(fail("bbt_r2c_plan_create: hipEventCreateWithFlags failed"));
@@ -2920,6 +2932,8 @@ int bbt_r2c_plan_info(const bbt_r2c_plan* p, int* one_pass, int64_t* workspace_b
 int bbt_r2c_execute(bbt_r2c_plan* p, const void* in_dev, void* out_dev, int64_t n_frames, bbt_stream stream) {
     ARG_TRY(p && in_dev && out_dev, "bbt_r2c_execute: null argument");
     ARG_TRY(n_frames >= 0, "bbt_r2c_execute: n_frames=%lld", (long long)n_frames);
+    ARG_TRY((uintptr_t)in_dev % 4 == 0, "bbt_r2c_execute: in_dev is not aligned to its float32 samples (4 bytes)");
+    ARG_TRY((uintptr_t)out_dev % 8 == 0, "bbt_r2c_execute: out_dev is not aligned to its complex64 samples (8 bytes)");
     if (n_frames == 0) return 0;
     std::lock_guard<std::mutex> lock(p->mu);
     hipStream_t st = (hipStream_t)stream;

@@ -465,7 +465,13 @@ int bbt_sk_excise(const void* x_dev, void* out_dev, int64_t n_block, int64_t n, 
  *   n_stream   S >= 1, any (one stream: four consecutive frames share a transform)
  * in_dev: (n_frames * 2 M, S) float32; out_dev: (n_frames * M, S) complex64 -- the same number
  * of bytes, but they must not overlap (the even input rows are read after other workgroups have
- * written their output; overlapping ranges are refused).  Asynchronous on
+ * written their output; overlapping ranges are refused).  in_dev must be aligned to its float32
+ * samples (4 bytes) and out_dev to its complex64 samples (8 bytes); a call that is not is refused
+ * before anything is launched.  The one-pass route moves 16 bytes per access where S is a multiple
+ * of 4, and 8 where it is even, only if BOTH pointers are 16-byte aligned; else one float at a
+ * time, with the same bits (the three-step route's kernels take one float at a time always).  The
+ * three-step route's work buffers take at most 256 MiB each (the environment's BBT_R2C_WORK_KIB,
+ * read when the plan is made, sets another budget: a developer knob).  Asynchronous on
  * `stream`.  A plan runs one execute call at a time (a mutex on the host; on the device a call
  * first waits for the end of the previous one, which may have run on another stream); calls on
  * different plans are independent.  one_pass: 1 for the one-pass route; workspace_bytes: device

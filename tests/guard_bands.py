@@ -11,7 +11,10 @@ payload plus `PAD` words, so that a store a full row beyond either end is still 
 TWO OFFSETS.  ``skew`` is the payload's address modulo 16: 0, the alignment every array of the pool has,
 or 4, the least the entry points accept; three of them (Accelerate, SpectralKurtosis / Excise, Modulate)
 pick another instantiation from it.  complex64 arrays of the spectral-kurtosis entry points, which ask
-for pointers aligned to their elements, take 8 instead.  The address is asserted, not assumed.
+for pointers aligned to their elements, take 8 instead.  The address is asserted, not assumed.  Any skew
+below 16 that is a multiple of the item size (of 4 for items wider than that) is taken: 1 and 2 for the
+one- and two-byte elements of the gather plans (test_shaping_guard_gpu.py).  The front band's pattern ends
+with a whole word at the payload's first byte, whatever the skew.
 
 TWO POISONS, one per run for all its bands: the quiet NaN 0x7fc0beef and +inf.  The searches leave a NaN
 out of their total order, so a stray NaN summand can lose silently; a stray +inf wins its block or spoils
@@ -41,32 +44,36 @@ def _poison_bytes(poison, dtype, count):
 
 class Guarded:
     """One allocation: ``front`` words of poison, a poisoned payload of ``shape`` and ``dtype``, ``back`` words
-    of poison.  ``array`` is the payload's view.  ``skew``: the payload's address modulo 16, a multiple of 4."""
+    of poison.  ``array`` is the payload's view.  ``skew``: the payload's address modulo 16, a multiple of the
+    item size (of 4 for wider items); ``front`` counts the front band's whole words, ``front_bytes`` all of it."""
 
     def __init__(self, shape, dtype, poison, skew=0):
         shape = tuple(int(d) for d in shape)
         self.dtype = np.dtype(dtype)
-        assert poison in POISONS.values() and skew in (0, 4, 8, 12) and len(shape) >= 1
+        assert poison in POISONS.values() and len(shape) >= 1
+        assert 0 <= skew < 16 and skew % min(self.dtype.itemsize, 4) == 0, (skew, self.dtype)
         self.poison, self.skew = poison, skew
         self.nbytes = int(np.prod(shape, dtype=np.int64)) * self.dtype.itemsize
         self.row_bytes = self.nbytes // shape[0] if shape[0] else 0
         band = -(-self.row_bytes // 4) + PAD
         # the front band: at least `band` words, and the payload skew bytes past a multiple of 16
         self.front = -(-band // 4) * 4 + skew // 4
+        self.front_bytes = 4 * self.front + skew % 4
         # the back band begins at the word boundary at or after the payload's end
         self.tail = -self.nbytes % 4
         self.back = band
-        total = 4 * self.front + self.nbytes + self.tail + 4 * self.back
+        total = self.front_bytes + self.nbytes + self.tail + 4 * self.back
         self.base = hip.DeviceArray((total,), np.uint8)
         assert self.base.ptr % 16 == 0, 'the pool hands out 16-byte aligned blocks'
-        self._fill = np.concatenate([_poison_bytes(poison, np.uint32, 4 * self.front),
+        # (the front band's pattern is anchored at its end: the last four bytes before the payload are one word)
+        self._fill = np.concatenate([_poison_bytes(poison, np.uint32, 4 * self.front + 4)[4 - skew % 4:],
                                      _poison_bytes(poison, self.dtype, self.nbytes),
                                      _poison_bytes(poison, self.dtype, self.tail),
                                      _poison_bytes(poison, np.uint32, 4 * self.back)])
         if self.dtype.itemsize == 1:
             self._fill[:] = BYTE_POISON
         self.base.copy_from_host(self._fill)
-        self.array = hip.DeviceArray(shape, self.dtype, ptr=self.base.ptr + 4 * self.front, owner=self.base)
+        self.array = hip.DeviceArray(shape, self.dtype, ptr=self.base.ptr + self.front_bytes, owner=self.base)
         # the property under test, stated
         assert self.array.ptr % 16 == skew and self.array.nbytes == self.nbytes
         assert 4 * min(self.front, self.back) >= self.row_bytes + 4 * PAD
@@ -81,7 +88,9 @@ class Guarded:
         if host.dtype.itemsize == 1:
             found = int(np.count_nonzero(host.view(np.uint8) == BYTE_POISON))
         else:
-            found = int(np.count_nonzero(host.reshape(-1).view(np.uint32) == poison))
+            # (the payload's whole words; two-byte data may end with half a one)
+            words = host.reshape(-1).view(np.uint8)[:host.nbytes // 4 * 4].view(np.uint32)
+            found = int(np.count_nonzero(words == poison))
         assert planted is None or found == planted, f'the payload holds the poison {poison:#x} {found} times'
         g.array.copy_from_host(host)
         return g
@@ -91,7 +100,7 @@ class Guarded:
         first touched word relative to the payload, in words and in leading-axis rows -- and returns the
         payload."""
         got = self.base.to_host()
-        begin, end = 4 * self.front, 4 * self.front + self.nbytes
+        begin, end = self.front_bytes, self.front_bytes + self.nbytes
         band = np.ones(got.shape[0], bool)
         band[begin:end] = False
         touched = np.flatnonzero(band & (got != self._fill))

@@ -65,6 +65,30 @@ def _across_skews(key, skew, run, same):
 @pytest.mark.parametrize('shape, dtype', [((5, 7), F32), ((3, 2, 2), C64), ((9, 4), np.dtype(np.uint8)), ((1,), F32)])
 def test_helper_catches_a_word_on_either_side(shape, dtype, skew, poison):
     """No kernel of the project runs: plain copies inside the allocation stand for the stray store."""
+    _helper_catches(shape, dtype, skew, poison)
+
+
+#: skews that are multiples of the item size and not of 4 (the gather plans' one- and two-byte elements), and 8 / 12
+ELEMENT_SKEWS = [((9, 4), np.dtype(np.uint8), 1), ((9, 4), np.dtype(np.uint8), 2), ((9, 4), np.dtype(np.uint8), 3),
+                 ((9, 4), np.dtype(np.uint8), 13), ((5, 2), np.dtype(np.int16), 2), ((5, 2), np.dtype(np.int16), 6),
+                 ((5, 2), np.dtype(np.int16), 14), ((5, 7), F32, 8), ((5, 7), F32, 12), ((3, 2, 2), C64, 8),
+                 ((1,), F32, 12), ((2, 3), np.dtype(np.complex128), 8)]
+
+
+@both_poisons
+@pytest.mark.parametrize('shape, dtype, skew', ELEMENT_SKEWS, ids=[f'{d.name}-off{s}' for _, d, s in ELEMENT_SKEWS])
+def test_helper_catches_a_word_at_element_skews(shape, dtype, skew, poison):
+    """The same at every other kind of skew `Guarded` takes; the band before the payload ends with a whole word."""
+    _helper_catches(shape, dtype, skew, poison)
+    g = Guarded(shape, dtype, poison, skew)
+    assert g.front_bytes == 4 * g.front + skew % 4 and g.array.ptr - g.base.ptr == g.front_bytes
+    before = g.base.to_host()[g.front_bytes - 4:g.front_bytes].view(np.uint32)[0]
+    assert before == (0xa5a5a5a5 if dtype.itemsize == 1 else poison)
+    with pytest.raises(AssertionError):
+        Guarded(shape, dtype, poison, skew + 1 if dtype.itemsize > 1 else 16)
+
+
+def _helper_catches(shape, dtype, skew, poison):
     g = Guarded(shape, dtype, poison, skew)
     assert g.array.ptr % 16 == skew and g.array.shape == shape and g.array.dtype == dtype
     assert min(g.front, g.back) * 4 >= g.row_bytes + 4 * PAD
