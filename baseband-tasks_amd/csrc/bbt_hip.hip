@@ -2534,13 +2534,13 @@ extern "C" int bbt_phase_runs(const void* pieces_dev, int64_t n_piece, int n_coe
     HIP_TRY(hipMemsetAsync(counts_dev, 0, (size_t)(n_row * n_phase) * 8, st));
     hipLaunchKernelGGL(k_phase_count, dim3((unsigned)nt_s), dim3(256), 0, st, P, (long long)n_phase, tile_s);
     hipLaunchKernelGGL(k_scan_tiles, dim3(1), dim3(256), 0, st, tile_s, (long long)nt_s, scalars, (long long)run_cap,
-                       scalars + 1);
+                       (const long long*)nullptr, scalars + 1);
     hipLaunchKernelGGL(k_phase_scatter, dim3((unsigned)nt_s), dim3(256), 0, st, P, (long long)n_phase,
                        (const long long*)tile_s, rows, rows + n_row, rows + 2 * n_row, (long long)n_row,
                        (long long)n_cell, (long long)slot0, (long long)run_cap, begin_t, slot_t, grid, scalars + 1);
     hipLaunchKernelGGL(k_grid_count, dim3((unsigned)nt_c), dim3(256), 0, st, (const int*)grid, (long long)n_cell, tile_c);
     hipLaunchKernelGGL(k_scan_tiles, dim3(1), dim3(256), 0, st, tile_c, (long long)nt_c, scalars + 2,
-                       (long long)run_cap, scalars + 1);
+                       (long long)run_cap, (const long long*)scalars, scalars + 1);
     hipLaunchKernelGGL(k_grid_compact, dim3((unsigned)nt_c), dim3(256), 0, st, (const int*)grid, (long long)n_cell,
                        (const long long*)tile_c, (const long long*)begin_t, (const long long*)slot_t,
                        (const long long*)scalars, (long long)run_cap, (const long long*)(scalars + 1),

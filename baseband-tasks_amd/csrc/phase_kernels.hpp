@@ -23,8 +23,13 @@
 //      does not depend on the order)
 //   5. k_slot_ptr:      slot_ptr[j] = first position whose slot is >= j (binary search)
 // Everything but the counts is a pure function of the arguments (scans and unique cells, no
-// atomics); the counts are integer sums.  A k outside its row's grid (a phase that decreases) or
-// more runs than the caller allowed for sets status and writes nothing out of bounds.
+// atomics); the counts are integer sums.  Status is a sum of bits, and with any of them set nothing is
+// compacted or searched: the table is empty, and nothing is written out of bounds.
+//   1  more runs than the caller allowed for
+//   2  a k outside its row's grid (a phase that ran below the row's first bin or beyond its last)
+//   4  two runs in one cell (fewer occupied cells than runs): a (row, k) that came back
+//   8  a k below that of the sample before it in the same row (a phase that steps back), whether or not
+//      it lands on a cell of its own: fold_table.piece_table refuses exactly these phases
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -81,10 +86,12 @@ __device__ __forceinline__ int phase_piece_of(const PhasePieces& P, long long i)
 
 // The four samples of this thread: k, row and whether each starts a run.  Samples beyond `end`
 // start nothing.  (The thread re-evaluates the sample before its first: no exchange needed.)
-__device__ __forceinline__ void phase_flags(const PhasePieces& P, long long base, long long begin, long long end,
+// Returns whether one of them has a k below that of the sample before it in the same row.
+__device__ __forceinline__ bool phase_flags(const PhasePieces& P, long long base, long long begin, long long end,
                                             long long n_phase, long long k[4], int piece[4], bool start[4]) {
     long long k_prev = 0, row_prev = -1;
     int p = 0;
+    bool back = false;
     if (base < end) {
         p = phase_piece_of(P, base > begin ? base - 1 : base);
         if (base > begin) {
@@ -104,9 +111,15 @@ __device__ __forceinline__ void phase_flags(const PhasePieces& P, long long base
         k[t] = phase_bin(P, p, i, n_phase);
         const long long r = P.row[p];
         start[t] = r != row_prev || k[t] != k_prev;
+        back = back || (r == row_prev && k[t] < k_prev);
         k_prev = k[t];
         row_prev = r;
     }
+    return back;
+}
+
+__device__ __forceinline__ void phase_status(long long* status, unsigned long long bit) {
+    atomicOr((unsigned long long*)status, bit);
 }
 
 // Sum of v over the 256 threads of the workgroup, and this thread's exclusive prefix.
@@ -140,8 +153,10 @@ __global__ __launch_bounds__(256) void k_phase_count(PhasePieces P, long long n_
 }
 
 // In place: count[t] -> sum of count[0 .. t-1]; *total = the sum of all; status |= 1 if it exceeds cap.
+// With `expect` (the occupied cells against the runs; every run was scattered if neither bit 1 nor
+// bit 2 is set): status |= 4 if the sum is not *expect.
 __global__ __launch_bounds__(256) void k_scan_tiles(long long* count, long long n, long long* total, long long cap,
-                                                    long long* status) {
+                                                    const long long* expect, long long* status) {
     __shared__ long long lds[256];
     long long carry = 0;
     for (long long base = 0; base < n; base += 256) {
@@ -154,7 +169,8 @@ __global__ __launch_bounds__(256) void k_scan_tiles(long long* count, long long 
     }
     if (threadIdx.x == 0) {
         *total = carry;
-        if (carry > cap) *status = *status | 1;
+        if (carry > cap) phase_status(status, 1);
+        if (expect && carry != *expect && (*status & 3) == 0) phase_status(status, 4);
     }
 }
 
@@ -169,7 +185,7 @@ __global__ __launch_bounds__(256) void k_phase_scatter(PhasePieces P, long long 
     long long k[4];
     int piece[4];
     bool start[4];
-    phase_flags(P, base, begin, end, n_phase, k, piece, start);
+    if (phase_flags(P, base, begin, end, n_phase, k, piece, start)) phase_status(status, 8);
     long long total;
     long long g = tile_off[blockIdx.x] +
                   block_scan_256((long long)start[0] + start[1] + start[2] + start[3], lds, total);
@@ -181,7 +197,7 @@ __global__ __launch_bounds__(256) void k_phase_scatter(PhasePieces P, long long 
         const long long rel = row_ok ? k[t] - k0[r] : -1;
         const long long cyc = rel >= 0 ? rel / n_phase : -1;
         if (g >= run_cap || cyc < 0 || cyc >= n_cycle[r]) {
-            *status = 2;                                   // (every writer writes the same value)
+            phase_status(status, 2);
         } else {
             const long long bin = rel - cyc * n_phase;
             const long long cell = cell0[r] + bin * n_cycle[r] + cyc;
@@ -190,7 +206,7 @@ __global__ __launch_bounds__(256) void k_phase_scatter(PhasePieces P, long long 
                 slot_t[g] = slot0 + r * n_phase + bin;
                 grid[cell] = (int)(g + 1);
             } else {
-                *status = 2;
+                phase_status(status, 2);
             }
         }
         ++g;

@@ -253,7 +253,8 @@ def piece_table(row_edges, row_pieces, n_phase, c0, c1):
 
     ``row_pieces(r, lo, hi)``: the pieces of row ``r`` for its samples [lo, hi) (absolute
     indices), as (m_begin, m_end, coeff, dt0, step, ref_int, ref_frac) with ``m`` counted from
-    ``row_edges[r]``.
+    ``row_edges[r]``.  A row whose unwrapped bin decreases from one run to the next is refused
+    (ValueError), as the table kernel refuses it: `plan_pieces` sees the ends of a row only.
     """
     row_edges = np.asarray(row_edges, dtype=np.int64)
     r0, r1 = piece_rows(row_edges, c0, c1)
@@ -274,7 +275,10 @@ def piece_table(row_edges, row_pieces, n_phase, c0, c1):
                 ks.append(k[new])
                 prev = k[-1]
         b = np.concatenate(starts)
-        slots.append((r - r0) * n_phase + np.concatenate(ks) % n_phase)
+        k = np.concatenate(ks)
+        if np.any(k[1:] < k[:-1]):                       # (the table kernel refuses the same phases: status 8)
+            raise ValueError("phase must increase with time")
+        slots.append((r - r0) * n_phase + k % n_phase)
         begins.append(b)
         ends.append(np.concatenate((b[1:], [hi])).astype(np.int64))
     n_row = r1 - r0

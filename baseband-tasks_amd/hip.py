@@ -863,7 +863,7 @@ def phase_runs(plan, n_phase, slot0=0, n_slot=None):
     s_begin, s_end, run_cap = int(plan['lo'][0]), int(plan['lo'][-1]), int(plan['run_cap'])
     need = C.c_int64()
     check(lib().bbt_phase_runs_work(s_end - s_begin, n_cell, run_cap, C.byref(need)))
-    work = DeviceArray((need.value // 8 + 2,), np.int64)
+    work = DeviceArray((need.value,), np.uint8)                  # (exactly: no slack for the layout to lean on)
     slot_ptr = DeviceArray((n_slot + 1,), np.int64)
     runs = DeviceArray((2, run_cap), np.int64)
     counts = DeviceArray((n_chunk_slot,), np.int64)

@@ -355,7 +355,8 @@ class Fold(_RunTableTask):
 
     #: where the run tables of a phase that offers polynomial pieces (``fold_pieces``, see
     #: INTEGRATION.md) are made: 'device' (the table kernel), 'host' (NumPy, every sample), or
-    #: None: the environment's BBT_FOLD_TABLE, else 'device'.  Both give the same table.
+    #: None: the environment's BBT_FOLD_TABLE, else 'device'.  Both give the same table, and both
+    #: refuse (ValueError) a phase whose bin steps back inside a row.
     table_route = None
 
     def _route(self):

@@ -384,9 +384,12 @@ int bbt_fold_runs(const void* in_dev, void* out_dev, int64_t n_in, int64_t n_ele
  *   outputs     slot_ptr[n_slot + 1] with row r, bin b at slot slot0 + r * n_phase + b;
  *               run_begin / run_end [run_cap] (the first info[0] are the runs, slot by slot, in
  *               time order within a slot); counts[n_row * n_phase] samples per slot of the chunk.
- *   info        host int64[2]: the number of runs, and a status: 0, or nonzero if the runs
- *               exceed run_cap or a bin falls outside its row's cycles (a phase that decreases);
- *               the table is then empty.  The call waits for the stream.
+ *   info        host int64[2]: the number of runs, and a status: 0, or a sum of 1 (the runs exceed
+ *               run_cap), 2 (a bin falls outside its row's cycles), 4 (two runs of one row and bin:
+ *               fewer occupied cells than runs) and 8 (a sample's bin is below that of the sample
+ *               before it in the same row: a phase that steps back, which the host twin refuses
+ *               too); the table is then empty (slot_ptr all zeros, run_begin / run_end untouched).
+ *               The call waits for the stream.
  *   work        device scratch of bbt_phase_runs_work(s_end - s_begin, n_cell, run_cap) bytes.
  * The table depends on the arguments only (scans, one cell per run); the counts are integer
  * sums. */

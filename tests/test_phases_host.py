@@ -7,8 +7,8 @@ import numpy as np
 import pytest
 
 import baseband_tasks_amd as bt
-from baseband_tasks_amd.fold_table import (phase_difference, phase_parts, piece_table, polynomial_bins,
-                                           unwrapped_bin)
+from baseband_tasks_amd.fold_table import (phase_difference, phase_parts, piece_table, plan_pieces,
+                                           polynomial_bins, unwrapped_bin)
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 GOLDEN_DIR = os.path.join(ROOT, 'tests', 'golden')
@@ -260,6 +260,30 @@ def test_piece_table_is_the_per_sample_table():
         covered = np.concatenate([np.arange(b, e) for b, e in zip(rb[sp[j]:sp[j + 1]], re[sp[j]:sp[j + 1]])] or
                                  [np.zeros(0, np.int64)])
         np.testing.assert_array_equal(covered, np.flatnonzero(slot == j))
+
+
+def test_piece_table_refuses_a_phase_that_steps_back():
+    """Two linear pieces of 3 bins a sample, the second starting 6 bins back: the row's last bin is above its
+    first, and its two ends are all that `plan_pieces` sees.  `piece_table` sees every sample and refuses, as
+    the table kernel does (test_phase_runs_guard_gpu.py)."""
+    n_phase, step = 8, 3. / 8.
+    edges = np.array([0, 24])
+
+    def row_pieces(back):
+        ref_int = np.round(2. - back / 8.)
+        both = [(0, 12, [0., 1.], 0., step, 2., 0.), (12, 24, [0., 1.], 0., step, ref_int, (2. - back / 8.) - ref_int)]
+        return lambda r, lo, hi: [(max(a, lo), min(b, hi)) + tuple(piece) for a, b, *piece in both if a < hi and b > lo]
+    k = np.concatenate([polynomial_bins(*piece, np.arange(a, b), n_phase) for a, b, *piece in row_pieces(6)(0, 0, 24)])
+    np.testing.assert_array_equal(k, np.concatenate((16 + 3 * np.arange(12), 46 + 3 * np.arange(12))))
+    assert plan_pieces(edges, row_pieces(6), n_phase, 0, 24)[2]['run_cap'] == 24           # (the plan passes it)
+    for back in (6, 5, 4):                    # (onto bins the first piece visited, stepped over, and one bin back)
+        with pytest.raises(ValueError, match='phase must increase with time'):
+            piece_table(edges, row_pieces(back), n_phase, 0, 24)
+    # standing still, or a later chunk that begins after the step, is no step back
+    r0, n_row, sp, rb, re, cnt = piece_table(edges, row_pieces(3), n_phase, 0, 24)
+    assert cnt.sum() == 24 and len(rb) == 23
+    r0, n_row, sp, rb, re, cnt = piece_table(edges, row_pieces(6), n_phase, 12, 24)
+    assert cnt.sum() == 12 and len(rb) == 12
 
 
 def test_polyco_phase_offers_the_protocol():

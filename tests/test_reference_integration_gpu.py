@@ -3,11 +3,11 @@ what the accelerated `Integrate` covers: whole-stream, from-a-start and
 integer-step integration of `Square` output, averaged or as sums with counts
 (reference baseband_tasks/tests/test_integration.py:17-168 and 256-263).
 
-Integration over time intervals, pulse phase (`Fold`, `Stack`) and the
-non-integer ratio case (171-255, 265-520) need the reference's host-side
-`phase` machinery and are outside SURVEY 8(f); they raise
-NotImplementedError here.  The reference's streams are float64; the kernels
-sum in float32, so comparisons use rtol 1e-5.
+Integration in pulse phase (``Integrate(phase=...)``, `Fold`, `PulseStack`;
+171-255, 265-520) has tests of its own: test_fold_gpu.py, test_phases_gpu.py.
+Integration over time intervals, a non-integer step without a phase, is
+outside the accelerated path and raises NotImplementedError.  The reference's
+streams are float64; the kernels sum in float32, so comparisons use rtol 1e-5.
 """
 import numpy as np
 import pytest
